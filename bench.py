@@ -11,7 +11,9 @@ timed file steps -- the kernels are the same).  Workload = BASELINE.json configs
 Appendix C (seed 19, md5 pinned), vocab_size=32000.  N>1: one process per GPU (torchrun); every rank reads ITS byte range of the SAME
 pinned file, cut at whitespace (strong scaling -- the only way the N-GPU model can be compared with the reference's), pair-count
 deltas travel over RCCL each round.  `--scaling weak` gives every rank its own 1 GB instead (HBM-resident only; no pin exists for those
-corpora).  Rank 0 prints ONE JSON line.
+corpora).  Rank 0 prints ONE JSON line: the headline, config, parity and rooflines, with the other blocks cut to their figures; the
+whole record goes to stderr as a `detail:` line.  `--dump-outputs DIR` writes what the timed paths returned in their last step (the
+trained model's arrays, a seeded sample of the encoded ids) to DIR/*.npy, so that two builds can be compared output for output.
 
 Parity is part of the line: the md5 of every model the GPU writes (configs[1], the Zipf corpus of configs[2]) and the
 FNV of all 10 M encoded sentences (configs[3]) are compared with tests/golden/full_size_pins.json -- outputs of the
@@ -137,7 +139,14 @@ def main():
     ap.add_argument("--no-touched-pass", action="store_true", help="skip the untimed K4 measurement pass (profiling runs: one training per process)")
     ap.add_argument("--cpu-sample-mb", type=int, default=0, help="0 = the full corpus")
     ap.add_argument("--cpu-runs", type=int, default=3, help="runs of the reference's train_bpe per corpus (the median is reported)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed paths returned in their last step to DIR/<name>.npy (float64 / float32): the model of the last timed "
+                         "training (char2id, rules, special ids) and a fixed, seeded sample of 65 536 sentences of the last timed encode (ids, lengths)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     # stdout carries ONE line, the JSON: libraries that print banners there (RCCL does when a communicator is created) go to stderr
     real_stdout = os.dup(1)
@@ -185,7 +194,7 @@ def main():
     tmpdir = tempfile.mkdtemp(prefix="yttm_bench_")
     strong = world > 1 and args.scaling == "strong"
     ctx = dict(L=L, _lib=_lib, torch=torch, np=np, gen=gen, dev=dev, local_rank=local_rank, rank=rank, world=world, dist=dist, args=args,
-               pins=pins, quiet=quiet, tmpdir=tmpdir, strong=strong)
+               pins=pins, quiet=quiet, tmpdir=tmpdir, strong=strong, dump={})
 
     def barrier():
         if dist is not None:
@@ -216,6 +225,8 @@ def main():
         out["rccl_ranks"] = world
         out["config"]["parallelism"] = "one process per GPU; the corpus cut into %d byte ranges at white space; every rank keeps the whole pair table; per round ONE collective: an RCCL all-gather of per-pair delta blocks" % world
     model_path = main_res["model_path"]
+    if args.dump_outputs and rank == 0:  # (read now: the model file of the last timed file -> model step, before anything else runs)
+        ctx["dump"].update(_model_arrays(np, model_path))
     host = main_res.pop("host", None)
     if main_res.get("first_call_s") is not None and not ctx.get("_first_call_done"):
         # what `value` leaves out: the FIRST call of the process -- code objects loaded, ~6 GB of hipMalloc for the pool, the upload
@@ -290,8 +301,12 @@ def main():
     shutil.rmtree(tmpdir, ignore_errors=True)
     bad = [k for k, v in out["parity"].items() if v is False]
     if rank == 0:
+        if args.dump_outputs:
+            _write_dump(np, args.dump_outputs, ctx["dump"])
         sys.stdout.flush()
-        os.write(real_stdout, (json.dumps(out) + "\n").encode())
+        # the whole record (every block, ~20 KB) on stderr; stdout gets the result line, kept to a few KB so that a driver can parse it
+        log("detail: " + json.dumps(out))
+        os.write(real_stdout, (json.dumps(_result_line(out)) + "\n").encode())
         if bad:
             log("PARITY FAILURE:", bad)
         # the LAST line of stderr (a driver that keeps only the tail of the log still shows which pins were checked and how they came out)
@@ -300,6 +315,60 @@ def main():
         dist.destroy_process_group()
     if bad:
         sys.exit(3)
+
+
+def _result_line(out):
+    """The stdout line: headline, config, parity and rooflines whole; `kernels`, `hbm_resident`, `e2e` and the per-block details of
+    `encode`, `encode_dropout`, `extra` and `cpu_baseline` cut to their figures (the whole record is the `detail:` line on stderr)."""
+    def figures(d, keys=("value", "unit", "ms_per_step", "kernel_ms", "value_host_to_host", "fnv1a64", "train_seconds", "cores", "gpu_over_cpu",
+                         "gpu_hbm_resident_over_cpu", "error", "skipped")):
+        return {k: d[k] for k in keys if k in d} if isinstance(d, dict) else d
+    line = {k: v for k, v in out.items() if k not in ("kernels", "hbm_resident", "e2e")}
+    for k in ("encode", "encode_dropout"):
+        if k in line:
+            line[k] = figures(line[k])
+    if "cpu_baseline" in line:
+        line["cpu_baseline"] = figures(out["cpu_baseline"])
+        if "det_oracle" in out["cpu_baseline"]:
+            line["cpu_baseline"]["det_oracle"] = figures(out["cpu_baseline"]["det_oracle"])
+    if "extra" in line:
+        line["extra"] = {k: figures(v) for k, v in line["extra"].items()}
+    return line
+
+
+def _model_arrays(np, path):
+    """A model file (host_model.cpp BPEState::dump: "n_chars n_rules", n_chars lines "codepoint id", n_rules lines "x y z", then
+    "unk pad bos eos") as the arrays a caller of the trainer receives, float64 (every value is an integer below 2^32)."""
+    with open(path) as f:
+        n_chars, n_rules = (int(x) for x in f.readline().split())
+        v = np.array(f.read().split(), dtype=np.int64)
+    if v.size != 2 * n_chars + 3 * n_rules + 4:
+        raise RuntimeError("%s: %d numbers after the header, expected %d" % (path, v.size, 2 * n_chars + 3 * n_rules + 4))
+    return {"train_char2id": v[: 2 * n_chars].reshape(n_chars, 2).astype(np.float64),
+            "train_rules": v[2 * n_chars: 2 * n_chars + 3 * n_rules].reshape(n_rules, 3).astype(np.float64),
+            "train_special_ids": v[2 * n_chars + 3 * n_rules:].astype(np.float64)}
+
+
+def _encode_sample(np, ids, off, n_sent, n_sample=65536, seed=0):
+    """A fixed, seeded sample of the encoded sentences: their ids one after the other and their lengths (float32: ids < 2^24)."""
+    rng = np.random.default_rng(seed)
+    idx = np.sort(rng.choice(n_sent, size=min(n_sent, n_sample), replace=False)).astype(np.int64)
+    start = off[:-1].astype(np.int64)[idx]
+    lens = off[1:].astype(np.int64)[idx] - start
+    first = np.cumsum(lens) - lens
+    pos = np.repeat(start - first, lens) + np.arange(int(lens.sum()), dtype=np.int64)
+    return {"encode_sample_sentences": idx.astype(np.float64), "encode_sample_lengths": lens.astype(np.float32),
+            "encode_sample_ids": ids[pos].astype(np.float32)}
+
+
+def _write_dump(np, out_dir, arrays, limit=64 << 20):
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        raise RuntimeError("--dump-outputs: %d bytes, more than the %d allowed" % (total, limit))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("dump: %s <- %s (%.1f MB)" % (out_dir, ", ".join(sorted(arrays)), total / 1e6))
 
 
 def _make_corpus(ctx, corpus, size_mb):
@@ -789,6 +858,8 @@ def _bench_encode(ctx, model_path, main_res):
     ids = np.zeros(n_ids.value, dtype=np.int32)
     off = np.zeros(n_sent + 1, dtype=np.uint64)
     L.yttm_encode_fetch(h, ids.ctypes.data_as(_lib.i32p), off.ctypes.data_as(_lib.u64p), n_sent, err, _lib.ERRLEN)
+    if args.dump_outputs and rank == 0:  # (the ids of the last timed step of configs[3]: `res["encode"]` above)
+        ctx["dump"].update(_encode_sample(np, ids, off, n_sent))
     pin = ctx["pins"].get("c4_10m")
     fnv_ok = None
     if rank == 0 and pin and main_res["pin"] is not None and main_res["pin"]["model_md5"] == pin["model_md5"] and main_res["model_ok"]:

@@ -32,14 +32,15 @@ def test_python_binding_lists_the_same_symbols():
                                          "yttm_train_bpe_from_device_comm", "yttm_comm_callback_create"}
 
 
-def test_no_gpu_means_loud_failure():
+def test_no_gpu_means_loud_failure(tmp_path):
     """Without a GPU the product must fail loudly, never fall back to a CPU path."""
     if os.path.exists("/dev/kfd"):
         return
+    corpus, model = str(tmp_path / "t.txt"), str(tmp_path / "t.model")
     code = ("import os,sys; os.environ.pop('YTTM_AMD_LIB',None); sys.path.insert(0,%r); import youtokentome_amd as y;\n"
-            "open('/tmp/_abi_t.txt','w').write('aa bb ab')\n"
-            "try:\n    y.BPE.train('/tmp/_abi_t.txt','/tmp/_abi_t.model',20)\n    print('TRAINED')\nexcept ValueError as e:\n    print('ERR', e)\n" % ROOT)
-    r = subprocess.run(["python", "-c", code], capture_output=True, text=True)
+            "open(%r,'w').write('aa bb ab')\n"
+            "try:\n    y.BPE.train(%r,%r,20)\n    print('TRAINED')\nexcept ValueError as e:\n    print('ERR', e)\n" % (ROOT, corpus, corpus, model))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
     assert "TRAINED" not in r.stdout
     assert "ERR" in r.stdout and "GPU" in r.stdout
 

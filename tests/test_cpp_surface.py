@@ -14,6 +14,7 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
 
 import pytest
 
@@ -36,7 +37,8 @@ def _stress(args, lib=None, timeout=900):
         env["YTTM_AMD_LIB"] = lib
     else:
         env.pop("YTTM_AMD_LIB", None)
-    r = subprocess.run([STRESS] + args, cwd="/tmp", env=env, capture_output=True, text=True, timeout=timeout)
+    with tempfile.TemporaryDirectory() as work:  # (the harness writes its model files into the working directory)
+        r = subprocess.run([STRESS] + args, cwd=work, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, "stress %s failed (rc %d):\n%s" % (" ".join(args), r.returncode, r.stderr[-3000:])
     return r.stderr
 

@@ -308,23 +308,32 @@ def test_very_long_words(tmp_path):
     S.check_very_long_words(tmp_path, lengths=(2047, 2048, 2049, 5000, 20000, 70000))
 
 
-@pytest.mark.skipif(not refbin.available("det"), reason="oracle/_ref not present")
 def test_medium_corpus_vs_reference_binary(tmp_path):
     """30 MB 'abcd ' corpus, vocab 8000: too big for the oracle's comfort, checked against the unmodified reference
-    (-DDETERMINISTIC_QUEUE) running on the host cores."""
+    (-DDETERMINISTIC_QUEUE): its answers are pinned in tests/golden/medium_corpus_pin.json, and where oracle/_ref is present
+    the reference also runs here on the host cores and must give them."""
+    import hashlib
+    import json
     import youtokentome_amd as yttm
+    pin = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "medium_corpus_pin.json")))
     text = gen.abcd_corpus(30_000_000, seed=21)
+    assert hashlib.md5(text).hexdigest() == pin["corpus_md5"]
     corpus = str(tmp_path / "m.txt")
     open(corpus, "wb").write(text)
     m_gpu, m_ref = str(tmp_path / "gpu.model"), str(tmp_path / "ref.model")
     yttm.BPE.train(corpus, m_gpu, 8000)
-    refbin.train(corpus, m_ref, 8000, n_threads=8, kind="det")
-    assert filecmp.cmp(m_gpu, m_ref, shallow=False)
+    assert hashlib.md5(open(m_gpu, "rb").read()).hexdigest() == pin["model_md5"]
+    live = refbin.available("det")
+    if live:
+        refbin.train(corpus, m_ref, 8000, n_threads=8, kind="det")
+        assert filecmp.cmp(m_gpu, m_ref, shallow=False)
     # encode 200k sentences: ids identical to the reference encoder
     lines = str(tmp_path / "enc.txt")
     sent_bytes = gen.abcd_corpus(200_000 * 129, seed=5, line=128)
+    assert hashlib.md5(sent_bytes).hexdigest() == pin["sentences_md5"]
     open(lines, "wb").write(sent_bytes)
-    want = refbin.encode_bench(m_ref, lines, n_threads=8)
+    want = refbin.encode_bench(m_ref, lines, n_threads=8) if live else pin
+    assert (want["ids"], want["fnv1a64"]) == (pin["ids"], pin["fnv1a64"])
     bpe = yttm.BPE(m_gpu)
     offs = np.arange(200_001, dtype=np.uint64) * 129
     ids, off = bpe.bpe_cython.encode_packed(sent_bytes, offs)

@@ -2,8 +2,11 @@
 oracle/Makefile).  Train parity target = the -DDETERMINISTIC_QUEUE build; encode parity =
 any build; dropout at n_threads=1 in a fresh process is bit-exact.
 
-Skipped when oracle/_ref is absent (e.g. a checkout without /root/reference and without the prebuilt binaries)."""
-import filecmp
+Every answer of the reference is also committed as a digest (tests/golden/oracle_vs_ref_digests.json: md5 of the model file or of
+the ids, or the error message; written by tests/golden/make_ref_digests.py): the oracle is always compared with the digest, and where
+oracle/_ref is built the reference binary runs too and must give the committed digest."""
+import hashlib
+import json
 import os
 import random
 
@@ -13,7 +16,29 @@ import gen
 import oracle_lib as O
 import refbin
 
-pytestmark = pytest.mark.skipif(not refbin.available("det"), reason="oracle/_ref not built")
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vs_ref_digests.json")
+PINNED = json.load(open(DIGESTS)) if os.path.exists(DIGESTS) else {}
+LIVE = refbin.available("det")
+RECORDED = {}  # what the live reference answered, by case (make_ref_digests.py writes it out)
+
+
+def _digest(fn):
+    """md5 of what fn returns (bytes, or ids as their repr), or the message of the ValueError it raises."""
+    try:
+        v = fn()
+    except ValueError as e:
+        return "err:" + str(e)
+    return "md5:" + hashlib.md5(v if isinstance(v, bytes) else repr(v).encode()).hexdigest()
+
+
+def _reference(key, fn):
+    """The reference's answer to case `key`: the live binary where oracle/_ref is built (it must agree with the committed digest), else the digest."""
+    if LIVE:
+        got = RECORDED[key] = _digest(fn)
+        assert PINNED.get(key, got) == got, "the reference binary's answer to %s differs from the committed digest" % key
+        return got
+    assert key in PINNED, "no committed digest for %s (tests/golden/make_ref_digests.py)" % key
+    return PINNED[key]
 
 
 def _cmp_train(tmp_path, text, vocab, coverage=1.0, ids=(0, 1, 2, 3), n_threads=1, name="c"):
@@ -23,19 +48,24 @@ def _cmp_train(tmp_path, text, vocab, coverage=1.0, ids=(0, 1, 2, 3), n_threads=
     m_ref = str(tmp_path / f"{name}.ref.model")
     m_ora = str(tmp_path / f"{name}.ora.model")
     pad, unk, bos, eos = ids
-    ref_err = ora_err = None
-    try:
+
+    def ref():
         refbin.train(corpus, m_ref, vocab, coverage, n_threads, pad, unk, bos, eos, kind="det")
-    except ValueError as e:
-        ref_err = str(e)
-    try:
+        return open(m_ref, "rb").read()
+
+    def ora():
         O.train(text, m_ora, vocab, coverage, pad, unk, bos, eos)
-    except ValueError as e:
-        ora_err = str(e)
-    assert ref_err == ora_err
-    if ref_err is None:
-        assert filecmp.cmp(m_ref, m_ora, shallow=False), f"model files differ for {name}"
-    return m_ref if ref_err is None else None
+        return open(m_ora, "rb").read()
+    want = _reference("train/" + name, ref)
+    got = _digest(ora)
+    assert got == want, f"model files (or errors) differ for {name}: {got} vs {want}"
+    return m_ora if got.startswith("md5:") else None
+
+
+def _cmp_encode(key, want_fn, got_fn):
+    want = _reference("encode/" + key, want_fn)
+    got = _digest(got_fn)
+    assert got == want, f"encode {key}: {got} vs {want}"
 
 
 def test_readme_corpus_c1(tmp_path):
@@ -74,10 +104,10 @@ def test_invalid_utf8_with_coverage(tmp_path):
 
 def test_config_errors(tmp_path):
     text = b"aaa bbb abab"
-    for kw in [dict(coverage=0.0), dict(coverage=1.5), dict(ids=(0, 300, 2, 3)), dict(ids=(0, 1, 1, 3)),
-               dict(ids=(-2, 1, 2, 3)), dict(vocab=5)]:
+    for i, kw in enumerate([dict(coverage=0.0), dict(coverage=1.5), dict(ids=(0, 300, 2, 3)), dict(ids=(0, 1, 1, 3)),
+                            dict(ids=(-2, 1, 2, 3)), dict(vocab=5)]):
         vocab = kw.pop("vocab", 50)
-        _cmp_train(tmp_path, text, vocab, kw.get("coverage", 1.0), kw.get("ids", (0, 1, 2, 3)), name="err")
+        _cmp_train(tmp_path, text, vocab, kw.get("coverage", 1.0), kw.get("ids", (0, 1, 2, 3)), name=f"err{i}")
 
 
 def _sentences(rng, n, alphabet="abcde  "):
@@ -103,17 +133,12 @@ def test_encode_ids_vs_ref(tmp_path):
         pad, unk, bos_id, eos_id = ids
         for bos, eos, rev in [(0, 0, 0), (1, 1, 0), (0, 0, 1), (1, 1, 1)]:
             if (bos and bos_id == -1) or (eos and eos_id == -1):
-                with pytest.raises(ValueError) as e1:
-                    refbin.encode(model, lines, 1, bos, eos, rev)
-                with pytest.raises(ValueError) as e2:
-                    m.encode(sents, bos, eos, rev)
-                assert str(e1.value) == str(e2.value)
+                want = _reference(f"encode/e{ci}/{bos}{eos}{rev}", lambda: refbin.encode(model, lines, 1, bos, eos, rev))
+                assert want.startswith("err:")
+                assert _digest(lambda: m.encode(sents, bos, eos, rev)) == want
                 continue
-            want = refbin.encode(model, lines, 1, bos, eos, rev)
-            got = m.encode(sents, bos, eos, rev)
-            assert got == want
-            want8 = refbin.encode(model, lines, 8, bos, eos, rev)
-            assert got == want8
+            _cmp_encode(f"e{ci}/{bos}{eos}{rev}", lambda: refbin.encode(model, lines, 1, bos, eos, rev), lambda: m.encode(sents, bos, eos, rev))
+            _cmp_encode(f"e{ci}/{bos}{eos}{rev}/8", lambda: refbin.encode(model, lines, 8, bos, eos, rev), lambda: m.encode(sents, bos, eos, rev))
 
 
 def test_encode_dropout_bit_exact_single_thread(tmp_path):
@@ -126,7 +151,6 @@ def test_encode_dropout_bit_exact_single_thread(tmp_path):
         f.write(b"\n".join(sents) + b"\n")
     m = O.Model(model)
     for p in [0.1, 0.5, 1.0]:
-        want = refbin.encode(model, lines, 1, dropout=p)  # fresh process: mt19937 default seed 5489
         O.rng_reset()
-        got = m.encode(sents, dropout_prob=p)
-        assert got == want
+        _cmp_encode(f"dropout/{p}", lambda: refbin.encode(model, lines, 1, dropout=p),  # fresh process: mt19937 default seed 5489
+                    lambda: m.encode(sents, dropout_prob=p))
