@@ -28,8 +28,6 @@ GpuCtx::GpuCtx(int device) : device_(device) {
   hot_target_ = (unsigned int)C.hot_target.u;  // measured at 1 GB: 4096..16384 equal on the abcd corpus, 8192 best on Zipf text (4279 rounds)
   hot_min_ = (unsigned int)C.hot_min.u;
   fuse_enabled_ = C.no_fuse.u == 0;
-  // class-B tiles of a word-mode round: one stream (default, round 6) or beside k_words on a second one (YTTM_CLASSB_BESIDE=1: round 5's protocol)
-  classb_overlap_ = C.classb_beside.set && C.classb_beside.u == 1;
   idx_enabled_ = C.no_index.u == 0;  // (no pair index: no word mode either)
   idx_agg_min_ = C.index_agg_min.u;  // (fill pass of an index build: postings from which on a workgroup sums them per key in LDS first; tests: 0)
   hot_target_words_ = (unsigned int)C.hot_target_words.u;  // (measured at 1 GB, word mode: 8192 -> 6 rebuilds, candidate family 21.0 ms; 32768 -> 3, 16.9 ms; round 4: 32768 -> 3, 14.6 ms; 65536 -> 2, 12.5; 131072 -> 2, 15.0)
@@ -80,15 +78,12 @@ GpuCtx::~GpuCtx() {
   tl_stream = strm();
   tl_device = device_;
   (void)hipStreamSynchronize(strm());
-  if (st_b_) (void)hipStreamSynchronize(st_b_);
   drop_spec();
   for (hipEvent_t e : all_events_) (void)hipEventDestroy(e);
-  if (ev_fork_) (void)hipEventDestroy(ev_fork_);
-  if (ev_join_) (void)hipEventDestroy(ev_join_);
   DFREE(d_text_owned_); DFREE(d_hist_); DFREE(d_chunk_segs_); DFREE(d_counters_); DFREE(d_cpmap_); DFREE(d_rules_);
   free_class(cls_[0]); free_class(cls_[1]); free_class(cls_[2]);
   DFREE(d_stats_); DFREE(d_round_); DFREE(d_recv_); DFREE(d_hot_slots_); DFREE(d_hot_n_); DFREE(d_top_slots_); DFREE(d_top_n_);
-  DFREE(d_xstat_); DFREE(d_bloom_); DFREE(d_maybe_); DFREE(d_maybe_n_); DFREE(d_bsync_);
+  DFREE(d_xstat_); DFREE(d_bloom_); DFREE(d_maybe_); DFREE(d_maybe_n_);
   DFREE(db_.keys); DFREE(db_.touched); DFREE(d_send2_[0]); DFREE(d_send2_[1]);
   free_table(pt_);
   free_index();
@@ -98,18 +93,9 @@ GpuCtx::~GpuCtx() {
   if (h_pin_) (void)hipHostFree(h_pin_);
   if (st_raw_ && pool_give_stream(device_, st_raw_)) st_raw_ = nullptr;  // (synchronised above: nothing is pending on it)
   if (st_raw_) (void)hipStreamDestroy(st_raw_);
-  if (st_b_ && pool_give_stream(device_, st_b_)) st_b_ = nullptr;
-  if (st_b_) (void)hipStreamDestroy(st_b_);
 }
 
 void GpuCtx::sync() { HIP_CHECK(hipStreamSynchronize(strm())); }
-void GpuCtx::join_class_b() {
-  if (!classb_unjoined_ || !st_b_) return;
-  if (!ev_join_) HIP_CHECK(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-  HIP_CHECK(hipEventRecord(ev_join_, st_b_));
-  HIP_CHECK(hipStreamWaitEvent(strm(), ev_join_, 0));
-  classb_unjoined_ = false;
-}
 void GpuCtx::read_stats(int first, int n, unsigned long long *out) {
   HIP_CHECK(hipMemcpyAsync(out, d_stats_ + first, (size_t)n * 8, hipMemcpyDeviceToHost, strm()));
   sync();
@@ -196,7 +182,7 @@ void GpuCtx::resolve_timers() {
 void GpuCtx::merge_apply(const uint32_t *xyz, uint32_t k, const unsigned long long *rule_counts, const unsigned long long *next_tau_cnt,
                          uint32_t next_tau_mx, uint32_t next_want) {
   HIP_CHECK(hipSetDevice(device_));
-  tl_stream = st_raw_;  // (not strm(): naming the stream queues nothing -- see st_touched_)
+  tl_stream = strm();
   tl_device = device_;
   if (!k) return;
   if (!n_tiles && !multi()) return;  // a rank without words still takes part in the exchange
@@ -375,65 +361,10 @@ void GpuCtx::merge_apply(const uint32_t *xyz, uint32_t k, const unsigned long lo
     if (multi()) return ci == 0 && word_mode_ ? &xa : nullptr;  // (the tile kernels have nothing to do in a tail)
     return sa.on ? &sa : nullptr;
   };
-  // Word mode on one GPU with class-B tiles (words of 257 .. 2 048 tokens: long clauses of unsegmented scripts): the round is two launches
-  // in a row, the class-B tiles (~31 us on the CJK-shaped corpus) and then k_words (~120 us).  DEFAULT since round 6: just that, on the main
-  // stream.  YTTM_CLASSB_BESIDE=1 (`beside` below) is round 5's protocol, kept and tested: they share nothing until the tail, so class B
-  // goes to a second stream and its last workgroup raises a flag the tail waits for (ScanArgs::peer_flag; tools/micro/two_streams.hip: the
-  // whole of the shorter kernel comes off the round IN A MICRO-BENCHMARK; in the trainer it measured 14 ms slower per CJK training than one
-  // stream once the second stream was a real one and not, by accident, the NULL stream: profiles/r6_classb_order.txt).  No join: the main stream's next kernel starts after k_words has ended, k_words' tail
-  // has waited for the flag, and the flag is stored behind everything class B wrote -- stream order on the main stream IS the join.  The
-  // fork: when nothing was queued on the main stream since the host read the last round's mailbox (st_clean: the common round), all that
-  // can still run there is that round's tail folding the statistics rows -- by exchanges, so that this launch may add to them meanwhile --
-  // and class B starts at once; otherwise (a list refill, a repack, a rule table on its way) it waits for an event, which costs the
-  // round ~35 us of cross-queue latency and is why it is not the rule.
-  const bool beside = classb_overlap_ && !multi() && sa.on == 1u && word_mode_ && cls_[0].n_tiles && cls_[1].n_tiles && !cls_[2].n_tiles;
-  auto prep_b_beside = [&]() {  // the second stream, and the fork event when the main stream holds more than the last round's tail
-      bool st_clean = !st_touched_;
-      if (!st_b_) {  // first class-B launch beside k_words of this context: the second stream, the fork event, the flag block -- each once
-        st_b_ = pool_take_stream(device_);
-        // (the pool holds a stream only if a finished context gave one back: never the legacy NULL stream -- it would serialise with the
-        // embedding application's default-stream work and the tail's bounded spin on peer_flag could run out)
-        if (!st_b_) HIP_CHECK(hipStreamCreateWithFlags(&st_b_, hipStreamNonBlocking));
-        if (!ev_fork_)
-          HIP_CHECK(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));  // (destroyed by ~GpuCtx: not one of the pooled timing events)
-        if (!d_bsync_) {
-          d_bsync_ = dmalloc<unsigned int>(4);
-          HIP_CHECK(hipMemsetAsync(d_bsync_, 0, 16, strm()));
-        }
-        st_clean = false;
-      }
-      if (!st_clean) {
-        HIP_CHECK(hipEventRecord(ev_fork_, strm()));
-        HIP_CHECK(hipStreamWaitEvent(st_b_, ev_fork_, 0));
-      }
-  };
-  auto launch_b_beside = [&]() {
-      ScanArgs sb{};
-      sb.on = 4u;
-      sb.done_ctr = d_bsync_;
-      sb.peer_flag = d_bsync_ + 1;
-      sb.round_id = sa.round_id;
-      const BatchArgs tba = first_ba();
-      launch_merge_apply(1, cls_[1].ts, kpt, db_, d_rules_, cap - 1, self_x, self_z, z_base, d_stats_, &tba, &sb, d_bloom_, st_b_);
-      classb_overlapped++;
-      classb_unjoined_ = true;
-  };
+  // Class B, then class A (tiles, or word mode's k_words), on the context's one stream: stream order is the only synchronisation between
+  // the round's launches, and the last of them carries the tail (tail_of).
   for (int ci = 1; ci >= 0; ci--) {
     if (!cls_[ci].n_tiles) continue;
-    if (ci == 1 && beside) {
-      if (!d_bsync_) {
-        d_bsync_ = dmalloc<unsigned int>(4);
-        HIP_CHECK(hipMemsetAsync(d_bsync_, 0, 16, strm()));
-      }
-      sa.peer_flag = d_bsync_ + 1;
-      // Submitted BEFORE k_words, whose tail waits for the flag: two HIP streams may share one hardware queue, where kernels run in submission
-      // order (measured, round 6: submitted behind k_words the class-B launch never started -- the tail's bounded spin ran out and the round
-      // was reported unpublished; profiles/r6_classb_order.txt).
-      prep_b_beside();
-      launch_b_beside();
-      continue;
-    }
-    if (ci == 1) join_class_b();  // (class B on the main stream again behind rounds that ran it beside)
     if (ci == 0 && word_mode_) {
       // the batch's rules -> worklist of words (k_wgather; it also allots the new tokens' instance lists), then the words (k_words)
       WordClass &c = cls_[0];
@@ -487,6 +418,7 @@ void GpuCtx::merge_apply(const uint32_t *xyz, uint32_t k, const unsigned long lo
     }
     const BatchArgs tba = first_ba();
     launch_merge_apply(ci, cls_[ci].ts, kpt, db_, d_rules_, cap - 1, self_x, self_z, z_base, d_stats_, &tba, tail_of(ci), d_bloom_, strm());
+    if (ci == 1 && word_mode_) classb_word_rounds++;
   }
   launch_giant(true, cls_[2].ts, cls_[2].slot, kpt, db_, d_rules_, cap - 1, self_x, self_z, cls_[2].d_scratch, d_stats_, strm());
   if (dev_timing) kt.launches[KT_MERGE]++;

@@ -102,7 +102,7 @@ class GpuCtx {
   unsigned long long last_live() const { return last_live_; }
   int last_top_bin() const { return (int)last_top_bin_; }  // no bin above this one is in use
   unsigned long long index_builds = 0, word_rounds = 0, word_switch_round = 0, word_all_rounds = 0, word_fused_rounds = 0;  // K4 rounds whose worklist came from the pair index
-  unsigned long long classb_overlapped = 0;   // word-mode rounds whose class-B tiles ran beside k_words on a second stream
+  unsigned long long classb_word_rounds = 0;  // word-mode rounds that launched class-B tiles (before k_words)
   unsigned long long k3_radix = 0;            // 1: K3 of class A ran by radix partition (k_pairradix.hip)
   unsigned long long front_end_chunks = 0;    // > 0: the corpus was taken in this many chunks (front_end_chunked)
   bool corpus_resident() const { return !chunked_; }  // false: only the distinct words' bytes are in HBM
@@ -177,17 +177,6 @@ class GpuCtx {
   uint32_t *d_bloom_ = nullptr;   // pair filter of a batch that does not travel in the kernel arguments
   const char *trace_rounds_ = nullptr, *dbg_cand_ = nullptr;
   bool fuse_enabled_ = true;  // YTTM_NO_FUSE=1: always the separate scan kernel (tuning hook / tests)
-  // word mode, single GPU, YTTM_CLASSB_BESIDE=1: the class-B tiles' launch of a round runs on a second stream beside k_words (merge_apply; ScanArgs::peer_flag)
-  bool classb_overlap_ = false;      // YTTM_CLASSB_BESIDE
-  hipStream_t st_b_ = nullptr;
-  hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
-  // A class-B launch on st_b_ is joined with the main stream by the tail's wait for peer_flag: that orders what the TAIL reads (atomics,
-  // write-through stores).  The tiles' plain in-place token rewrites are only guaranteed visible at that kernel's END, and nothing on the main
-  // stream depends on its end -- so before the main stream next touches class-B tiles itself (a repack, a class-B launch that is not beside,
-  // a download) it waits for an event recorded behind the last beside-launch.  Off the common path: a beside-round never calls it.
-  bool classb_unjoined_ = false;
-  void join_class_b();
-  unsigned int *d_bsync_ = nullptr;  // [0] the class-B launch's ticket, [1] the round it has finished
   uint32_t id_min_ = 0, id_max_ = 0;  // id range of the alphabet (K3)
   uint32_t max_id_ = 0xffffffffu;  // largest token id in the tiles (unknown until the word table is built)
   unsigned long long scanned_cum_ = 0, live_tokens_last_ = 0, touched_cum_ = 0, touched_last_ = ~0ull >> 2;  // (first round: dense)
@@ -201,15 +190,9 @@ class GpuCtx {
   int device_;
   std::shared_ptr<const Config> cfg_;
   double xchg_margin_ = 3.0;
-  // The context's stream.  Every use goes through strm(), which notes that something may have been queued since the host last read a
-  // round's mailbox (poll_mailbox clears the note: whatever was queued before the kernel that published is over, and that kernel is past
-  // everything but its statistics fold) -- merge_apply asks before it puts a launch on the second stream (class-B tiles beside k_words).
+  // The context's stream: every launch and copy of the context goes to it, in order.
   hipStream_t st_raw_ = nullptr;
-  mutable bool st_touched_ = true;
-  hipStream_t strm() const {
-    st_touched_ = true;
-    return st_raw_;
-  }
+  hipStream_t strm() const { return st_raw_; }
   Comm *comm_ = nullptr;
 
   // corpus

@@ -241,7 +241,6 @@ void GpuCtx::poll_mailbox(uint32_t round_id) {
     touched_last_ = touched - touched_cum_;
     touched_cum_ = touched;
   }
-  st_touched_ = false;  // (whatever was queued before the kernel that published is over; that kernel is past everything but its statistics fold)
   const unsigned long long sites = *(const unsigned long long *)(h + 88);  // (published by scan_top only; one round old, like the token counts)
   if (sites > sites_cum_) {
     sites_last_ = sites - sites_cum_;

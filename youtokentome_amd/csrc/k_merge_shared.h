@@ -42,10 +42,8 @@ __device__ inline void global_emit(const PairTable &pt, const DeltaBuf &db, unsi
 // are serial), and one workgroup folds the rows into the totals when somebody needs them (fold_blk_stats).
 constexpr int BLK_BASE = 32, BLK_ROWS = 1536;  // >= the largest grid of k_filter / k_tiles<.., true>  // j: 0..3 = the K4 counters, 4 = pair-table slots claimed
 __device__ inline void blk_add(unsigned long long *stats, int j, unsigned long long v) {
-  // (the row is this workgroup's alone; the store is write-through because the round's tail may read it from another XCD before
-  // any cache write-back -- see round_tail)
-  // (round 5: an atomic add, not load + store: two launches of a round may run side by side -- ScanArgs::peer_flag -- and share a row, and
-  // the tail of the round before may still be folding the rows; an atomic on a line nobody else touches costs what the write-through store did)
+  // (the row is this workgroup's alone, and the round's tail may read it from another XCD before any cache write-back -- see round_tail --
+  // so the update must leave the XCD: an atomic add, which on a line nobody else touches costs what a write-through store does)
   unsigned long long *p = &stats[BLK_BASE + 8 * (blockIdx.x % BLK_ROWS) + j];
   if (v) atomicAdd(p, v);
 }
@@ -148,13 +146,9 @@ __device__ inline int cand_bin(unsigned long long c) {
 //       __syncthreads() before any thread reads;
 //   C3  everything C reads of P1 is read with agent-scope atomic loads (ld_agent, __hip_atomic_load relaxed/agent): F3.  Plain loads in the tail
 //       touch only kernel arguments, LDS and data no workgroup of this launch wrote.
-// Two launches of one round side by side (class-B tiles on a second stream, ScanArgs::peer_flag): the peer's last workgroup -- after the same P1/P2
-// and its own ticket -- stores the round's number with an agent-scope RELEASE store; C polls it with agent-scope ACQUIRE loads (bounded) before C2.
-// The peer's plain tile stores are NOT covered by that; they are ordered for later launches by an event the host records on the second stream and
-// waits for before the main stream touches class-B tiles again (gpu_ctx.cpp).
 // Towards the host: candidates, histogram and header are plain stores into pinned host memory, then __threadfence_system() + __syncthreads(),
 // then ONE system-scope release store of the round id; the host spins on that word and issues an acquire fence before reading the rest.
-// After the publish C folds the statistics rows with atomic exchanges (the NEXT round's class-B launch may already be adding to them).
+// After the publish C folds the statistics rows with atomic exchanges (an atomic on a line nobody else touches costs what a write-through store does).
 //
 // The candidate scan of a merge round: ONE workgroup reads the top list (PairTable::top_slots, about a thousand entries).
 // Run by the LAST workgroup of the apply kernel to finish (ScanArgs, yttm_kernels.h; every other workgroup has published its
@@ -183,26 +177,6 @@ __device__ inline void scan_top(const PairTable &pt, const ScanArgs &sa, unsigne
   unsigned long long *facc = reinterpret_cast<unsigned long long *>(lds + CAND_BINS + 40);  // [5] fold accumulators
   unsigned int *sub = lds + CAND_BINS + 64;   // [64] counts inside the boundary bin
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (sa.peer_flag) {
-    // The round's other launch (the class-B tiles, on a second stream) must be over: its last workgroup stores the round's number behind an
-    // agent-scope release.  It was submitted BEFORE this launch, so it runs whatever this workgroup does; the spin is bounded all the same
-    // -- a peer that never signals leaves the round unpublished, which the host reports (poll_mailbox), instead of a hung device.
-    if (tid == 0) {
-      unsigned int ok = 0;
-      for (unsigned int spins = 0; spins < (1u << 24); spins++) {
-        if (__hip_atomic_load(sa.peer_flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == sa.round_id) { ok = 1; break; }
-#if defined(__HIP_DEVICE_COMPILE__)
-        __builtin_amdgcn_s_sleep(8);
-#endif
-      }
-      lh[0] = ok;
-    }
-    __syncthreads();
-    const unsigned int ok = lh[0];
-    __syncthreads();
-    if (!ok) return;
-    __threadfence();  // (acquire for every thread: nothing of the peer's is stale in this CU's caches)
-  }
   const unsigned long long tm0 = (unsigned long long)wall_clock64();
   for (int b = tid; b < CAND_BINS; b += NT) lh[b] = 0;
   if (tid < 68) sub[tid] = 0;
@@ -433,7 +407,7 @@ __device__ inline void scan_top(const PairTable &pt, const ScanArgs &sa, unsigne
   // ---- 4. the statistics rows, AFTER the host has its candidates: the fold is off the round's critical path (the key count
   // and the token totals in the header are therefore one round old; the host allows for that)
   {  // statistics rows (left by the workgroups of this and earlier launches, write-through): all loads in flight together
-    constexpr int RPT = NT >= 512 ? (BLK_ROWS + NT - 1) / NT : 3;  // rows per thread in flight together (a one-wave workgroup -- class-B tiles -- takes its rows in groups)
+    constexpr int RPT = NT >= 512 ? (BLK_ROWS + NT - 1) / NT : 3;  // rows per thread in flight together (a class-B workgroup of APPLY_WPB_B waves takes its rows in groups)
     unsigned long long a[5] = {0, 0, 0, 0, 0};
     for (int b0 = 0; b0 < BLK_ROWS; b0 += RPT * NT) {
       unsigned long long v[RPT][5];
@@ -449,8 +423,7 @@ __device__ inline void scan_top(const PairTable &pt, const ScanArgs &sa, unsigne
         const int b = b0 + tid + r * NT;
 #pragma unroll
         for (int jj = 0; jj < 5; jj++) {
-          // (taken by an exchange: the NEXT round's class-B launch may already be adding to the row -- gpu_ctx.cpp merge_apply puts it on a
-          // second stream without waiting for this kernel's end -- and what it adds after the exchange belongs to the next fold)
+          // (taken by an exchange: an atomic on a line nobody else touches costs what a write-through store does)
           if (v[r][jj]) a[jj] += atomicExch(&stats[BLK_BASE + 8 * b + jj], 0ull);
         }
       }

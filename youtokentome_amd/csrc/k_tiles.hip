@@ -47,7 +47,7 @@ __global__ __launch_bounds__(WPB * 64, SLOT == TILE_SLOT_B ? 1 : MERGE ? (WPB ==
     for (int s = (int)threadIdx.x; s < (int)(FLAG_LDS_IDS / 16); s += WPB * 64) A.flagbits[s] = DIRECT ? 0xffffffffu : 0u;
     for (unsigned int i = threadIdx.x; i <= rule_mask; i += WPB * 64) rkeys[i] = PT_EMPTY;
     __syncthreads();
-    for (unsigned int j = threadIdx.x; j < ba.k; j += WPB * 64) {  // (class B: one wave per workgroup)
+    for (unsigned int j = threadIdx.x; j < ba.k; j += WPB * 64) {  // (class B: APPLY_WPB_B waves per workgroup)
       const uint32_t x = ba.xy[2 * j], y = ba.xy[2 * j + 1];
       if (x != y) {
         if (DIRECT) {
@@ -284,12 +284,7 @@ __global__ __launch_bounds__(WPB * 64, SLOT == TILE_SLOT_B ? 1 : MERGE ? (WPB ==
     __syncthreads();
     if (threadIdx.x == 0) is_last = atomicAdd(sa.done_ctr, 1u) == gridDim.x - 1;
     __syncthreads();
-    if (is_last && sa.on == 4u) {  // beside another launch of the round, which has the tail: say that this one is over (ScanArgs::peer_flag)
-      if (threadIdx.x == 0) {
-        *sa.done_ctr = 0;
-        __hip_atomic_store(sa.peer_flag, sa.round_id, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    } else if (is_last) {
+    if (is_last) {
       __threadfence();  // (acquire: nothing stale in this CU's caches)
       static_assert(sizeof(WL) >= (CAND_BINS + 160) * sizeof(unsigned int), "tile buffers double as the tail's scratch");
       const RuleProbe zprobe{LDSR ? rkeys : nullptr, LDSR ? nullptr : rules, rule_mask};
