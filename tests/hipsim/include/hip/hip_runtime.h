@@ -51,6 +51,7 @@ void sync_block();
 unsigned long long wave_ballot(bool pred);
 unsigned long long wave_shfl(unsigned long long v, int src_lane);
 void wave_barrier();
+unsigned long long wave_uniform(unsigned long long v);  // rendezvous: aborts unless every live lane passes v
 }  // namespace hipsim
 
 #define threadIdx (hipsim::g_threadIdx)
@@ -147,11 +148,15 @@ static inline T atomicExch(T *p, T v) { T o = *p; *p = v; return o; }
 #define __hip_atomic_store(p, v, order, scope) (*(p) = (v))
 #define __builtin_amdgcn_fence(order, scope) ((void)0)
 #define __builtin_amdgcn_wave_barrier() hipsim::wave_barrier()
-// wave-uniform values: readfirstlane is the identity here (the value is the same in every lane by contract); the mask
-// builtins index the uniform mask with the lane id
-#define __builtin_amdgcn_readfirstlane(v) (v)
+// wave-uniform values: by contract the same in every lane.  v_readfirstlane broadcasts the first active lane's 32 bits and
+// inverse_ballot reads the mask from a scalar register, so a lane-varying value would be quietly replaced by one lane's: here
+// both are wave ops that abort when the live lanes disagree (then the mask is indexed with the lane id)
+static inline int __builtin_amdgcn_readfirstlane(int v) { return (int)(uint32_t)hipsim::wave_uniform((uint32_t)v); }
 #define __builtin_amdgcn_readlane(v, l) __shfl((int)(v), (int)(l))
-static inline bool __builtin_amdgcn_inverse_ballot_w64(unsigned long long m) { return (m >> (threadIdx.x & 63u)) & 1ull; }
+static inline bool __builtin_amdgcn_inverse_ballot_w64(unsigned long long m) {
+  m = hipsim::wave_uniform(m);
+  return (m >> (threadIdx.x & 63u)) & 1ull;
+}
 static inline unsigned __builtin_amdgcn_mbcnt_lo(unsigned lo, unsigned acc) {
   const unsigned l = threadIdx.x & 63u;
   return acc + (unsigned)__builtin_popcount(l >= 32 ? lo : (lo & ((1u << l) - 1u)));

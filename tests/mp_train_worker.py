@@ -73,8 +73,8 @@ def main():
         print("ERR", err.value.decode())
         sys.exit(3)
     expect = os.environ.get("YTTM_TEST_EXPECT", "")
-    if rank == 0 and os.environ.get("YTTM_TEST_EXPECT_RANK0"):  # (checks that only hold on a rank that is sure to have words)
-        expect = ",".join(filter(None, [expect, os.environ["YTTM_TEST_EXPECT_RANK0"]]))
+    if os.environ.get("YTTM_TEST_EXPECT_RANK%d" % rank):  # (checks that only hold on one rank: one sure to have words, one short of memory)
+        expect = ",".join(filter(None, [expect, os.environ["YTTM_TEST_EXPECT_RANK%d" % rank]]))
     for want in filter(None, expect.split(",")):  # e.g. "word_rounds>0,word_fused_rounds==0": checks on this rank's report
         import json
         import re

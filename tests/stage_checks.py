@@ -650,3 +650,46 @@ def check_dropout_distribution(model_path, sentences, p, vocab):
     chi = (((hg[mask] - hw[mask]) ** 2) / (hg[mask] + hw[mask])).sum() / max(1, mask.sum() - 1)
     assert chi < 1.5, chi
     return lg.mean(), lw.mean(), ks, chi
+
+
+# ---- path hooks: the differential test of every hook of kind "path" (its cases: tests/test_sim_stages.py PATH_HOOK_CASES) -------------
+def path_hook_corpus(scale=1, disjoint_only=False):
+    if disjoint_only:
+        return gen.disjoint_words_corpus(200), 4 + 1300  # (200 words: batches of 129 .. 256 rules at any scale)
+    rng = random.Random(17)
+    long_words = ["".join(rng.choice("ab") for _ in range(n)) for n in (300, 700)]  # (class B)
+    text = gen.disjoint_words_corpus(200 * scale) + gen.readme_corpus(80 * scale, 90, "abcdef ", seed=5) + (" ".join(long_words) + "\n").encode()
+    return text, 4 + len(set(text.decode())) + 400
+
+
+def check_path_hook(hook, work, expect, tmp_path, scale=1):
+    """One path hook's case (its environment set by the caller): the oracle's model or ids, and where the report can show it, that the path
+    was taken (expect: "key==n,key>n" on the training's report)."""
+    import ctypes as C
+    import re
+    from youtokentome_amd import _lib
+    if work.startswith("train"):
+        text, vocab = path_hook_corpus(scale, work == "train_disjoint")
+        L = _lib.load()
+        corpus, m_gpu, m_ora = str(tmp_path / "c.txt"), str(tmp_path / "g.model"), str(tmp_path / "o.model")
+        open(corpus, "wb").write(text)
+        err, rep = C.create_string_buffer(2048), C.create_string_buffer(16384)
+        if work != "train_memory":
+            rc = L.yttm_train_bpe_ex(corpus.encode(), m_gpu.encode(), vocab, 1.0, 1, 0, 1, 2, 3, 0, rep, 16384, err, 2048)
+        else:
+            rc = L.yttm_train_bpe_from_memory(text, len(text), m_gpu.encode(), vocab, 1.0, 0, 1, 2, 3, 0, rep, 16384, err, 2048)
+        assert rc == 0, err.value
+        O.train(text, m_ora, vocab)
+        assert filecmp.cmp(m_gpu, m_ora, shallow=False), hook
+        r = json.loads(rep.value.decode())
+        for want in filter(None, expect.split(",")):
+            key, op, val = re.match(r"(\w+)(>|==)(\d+)$", want).groups()
+            assert (r[key] > int(val)) if op == ">" else (r[key] == int(val)), (hook, want, r[key])
+    elif work == "encode":
+        check_encode_mixed_shapes(n_sent=60 * scale, seed=83)
+        check_encode_word_cache(n_sent=40 * scale, seed=89)
+    else:
+        rng = random.Random(91)
+        sents = ["".join(rng.choice("abcd  ") for _ in range(rng.randint(0, 70))) for _ in range(40)] + ["", " ", "abcd" * 80]
+        check_dropout_extremes(os.path.join(G, "train_readme_small.model"), sents)
+        check_dropout_heap_equals_array()

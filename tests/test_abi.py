@@ -87,3 +87,25 @@ def test_environment_hooks_are_one_table():
                     used |= set(re.findall(r"\b(YTTM_[A-Z0-9_]+)\b", open(os.path.join(base, f), errors="replace").read()))
     unknown = sorted(n for n in used - known if not n.startswith(("YTTM_TEST_EXPECT", "YTTM_TEST_FREE_BYTES_RANK")))
     assert not unknown, unknown
+
+
+def test_every_path_hook_has_a_differential_test():
+    """A hook of kind "path" selects a code path that must give the same result (yttm_config.h): each must be named by a test of the suite
+    (tests/test_*.py -- tools and soak scripts do not count), or the path it selects is never compared with the default one."""
+    src = os.path.join(ROOT, "youtokentome_amd", "csrc")
+    if not os.path.exists(LIB):
+        subprocess.run(["make", "-C", src, "-j8"], check=True, capture_output=True)
+    lib = ctypes.CDLL(LIB)
+    lib.yttm_config_table.restype = ctypes.c_char_p
+    paths = []
+    for row in lib.yttm_config_table().decode().splitlines():
+        cols = [c.strip() for c in row.strip().strip("|").split("|")]
+        if len(cols) >= 3 and cols[0].startswith("`YTTM_") and cols[2] == "path":
+            paths.append(cols[0].strip("`"))
+    assert len(paths) >= 20, paths
+    tests = ""
+    for f in sorted(os.listdir(os.path.join(ROOT, "tests"))):
+        if f.startswith("test_") and f.endswith(".py"):
+            tests += open(os.path.join(ROOT, "tests", f), errors="replace").read()
+    untested = [h for h in paths if not re.search(r"\b%s\b" % h, tests)]
+    assert not untested, untested

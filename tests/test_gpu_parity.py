@@ -11,6 +11,7 @@ import gen
 import oracle_lib as O
 import refbin
 import stage_checks as S
+from test_sim_stages import PATH_HOOK_CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -222,6 +223,16 @@ def test_k4_word_mode(tmp_path, monkeypatch):
             assert hashlib.md5(open(model, "rb").read()).hexdigest() == pin["model_md5"], pin_name + " (RCCL)"
     finally:
         L.yttm_comm_destroy(comm)
+
+
+@pytest.mark.parametrize("hook", sorted(PATH_HOOK_CASES))
+def test_path_hook(hook, tmp_path, monkeypatch):
+    """The differential test of every "path" hook (tests/test_sim_stages.py) on the MI355X, on a corpus four times the emulator's."""
+    value, env, work, expect = PATH_HOOK_CASES[hook]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.setenv(hook, value)
+    S.check_path_hook(hook, work, expect, tmp_path, scale=4)
 
 
 @pytest.mark.parametrize("name", S.golden_train_names())

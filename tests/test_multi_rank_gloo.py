@@ -262,3 +262,25 @@ def test_delta_table_overflow_stops_every_rank(tmp_path, sim_lib):
     for p, (o, e) in zip(procs, outs):
         assert p.returncode == 3, (p.returncode, o, e[-2000:])
         assert "ERR" in o and "delta exchange" in o, o
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_radix_pair_count_on_every_rank(tmp_path, sim_lib, world):
+    """K3 by radix partition (k_pairradix.hip) forced on every rank (YTTM_K3_RADIX_MIN=0): k3r_final hands the counts of pairs a rank does not
+    own to the delta exchange, so the other ranks' tables are only right if those records travel.  Alphabets of 66, 300 and 1 500 symbols and a
+    CJK-shaped corpus, every rank reporting k3_radix==1; then rank 1 short of device memory (YTTM_TEST_FREE_BYTES_RANK1) counts with the
+    general kernel while the others take radix -- the oracle's model on the whole corpus either way."""
+    import stage_checks as S
+    cases = [(t, 4 + 600 + len(set(t.decode("utf-8", "replace")))) for t in S.texts_by_alphabet_size(sizes=(66, 300, 1500), n_words=300, seed=world)]
+    cjk = gen.cjk_corpus_fast(30000, seed=world)
+    cases.append((cjk, 4 + 600 + len(set(cjk.decode("utf-8", "replace")))))  # (the vocabulary must exceed the alphabet: else no merge at all)
+    env = {"YTTM_K3_RADIX_MIN": "0", "YTTM_TEST_EXPECT": "k3_radix==1"}
+    mixed = {"YTTM_K3_RADIX_MIN": "0", "YTTM_TEST_FREE_BYTES_RANK1": "65536", "YTTM_TEST_EXPECT_RANK0": "k3_radix==1", "YTTM_TEST_EXPECT_RANK1": "k3_radix==0"}
+    for i, (text, vocab) in enumerate(cases):
+        corpus, m_ora = str(tmp_path / f"c{i}.txt"), str(tmp_path / f"ora{i}.model")
+        open(corpus, "wb").write(text)
+        O.train(text, m_ora, vocab, 1.0)
+        for j, extra in enumerate((env, mixed) if i in (1, 3) else (env,)):
+            m_mp = str(tmp_path / f"mp{i}_{j}.model")
+            run_world(corpus, m_mp, vocab, 1.0, world, sim_lib, extra)
+            assert filecmp.cmp(m_mp, m_ora, shallow=False), (i, extra)

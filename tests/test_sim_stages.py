@@ -571,3 +571,51 @@ def test_k3_radix_partition(tmp_path, monkeypatch):
     monkeypatch.delenv("YTTM_TEST_FREE_BYTES")
     monkeypatch.setenv("YTTM_K3_RADIX_MIN", "1000000000000")
     S.check_word_table_and_pairs(S.texts_by_alphabet_size(sizes=(130,), n_words=300)[0])
+
+
+# Every hook of kind "path" (yttm_config.h: selects a code path that must give the same result) and how its differential test sets it
+# (tests/test_abi.py fails when a path hook is named in no test).  hook -> (value, other hooks the case needs, workload, report checks).
+# "train": a corpus with more than 64 symbols (K3 beyond its small-alphabet kernels, radix when forced), a first merge batch of more than
+# 128 disjoint rules (gen.disjoint_words_corpus) and words of class B, against the oracle's model; "train_memory": the same from host
+# memory; "train_disjoint": nothing but disjoint words (word-mode batches of 129 .. 256 rules); "encode": ids against the oracle's;
+# "dropout": the extremes against the oracle and dropout's heap against its array.
+FORCE_WORDS = {"YTTM_WORD_MIN_TILES": "0", "YTTM_WORD_MIN_TOKENS": "0", "YTTM_WORD_DIV": "0"}
+OVERLAP = {"YTTM_FE_OVERLAP_MIN": "0", "YTTM_FE_PART_KB": "4", "YTTM_IO_CHUNK_KB": "4"}
+PATH_HOOK_CASES = {
+    "YTTM_PLAIN_UPLOAD": ("1", {}, "train_memory", ""),
+    "YTTM_K1_WIDE": ("1", {}, "train", ""),
+    "YTTM_FE_NO_OVERLAP": ("1", OVERLAP, "train", "front_end_overlapped==0"),
+    "YTTM_FE_NO_SPEC": ("1", OVERLAP, "train", "front_end_overlapped==0"),
+    "YTTM_FE_CHUNK_SERIAL": ("1", {"YTTM_FE_CHUNK_KB": "8"}, "train", "front_end_chunks>1"),
+    "YTTM_WORD_TABLE_FULL": ("1", {}, "train", ""),
+    "YTTM_K3_RADIX_MIN": ("0", {}, "train", "k3_radix==1"),
+    "YTTM_K3_GENERAL": ("1", {"YTTM_K3_RADIX_MIN": "0"}, "train", "k3_radix==0"),
+    "YTTM_NO_EXTEND": ("1", {}, "train", "batch_extensions==0"),
+    "YTTM_NO_BATCH_SPLIT": ("1", FORCE_WORDS, "train_disjoint", "batch_splits==0,word_fused_rounds>100"),
+    "YTTM_NO_REFINE": ("1", {}, "train", ""),
+    "YTTM_NO_FUSE": ("1", {}, "train", "fused_rounds==0"),
+    "YTTM_NO_BATCH_ARGS": ("1", {}, "train", ""),
+    "YTTM_K4_DIRECT": ("0", {}, "train", ""),
+    "YTTM_WORD_MODE": ("0", FORCE_WORDS, "train", "word_rounds==0"),
+    "YTTM_NO_INDEX": ("1", FORCE_WORDS, "train", "index_builds==0,word_rounds==0"),
+    "YTTM_WORDS_FUSE_MAX": ("0", FORCE_WORDS, "train", "word_fused_rounds==0,word_rounds>0"),
+    "YTTM_REPLICATE_MAX_TOKENS": ("0", {}, "train", ""),
+    "YTTM_ENCODE_CACHE": ("1", {}, "encode", ""),
+    "YTTM_DROPOUT_HEAP_FROM": ("1", {}, "dropout", ""),
+    "YTTM_DROPOUT_HBM_QUEUES": ("1", {}, "dropout", ""),
+    "YTTM_DROPOUT_NO_PACK": ("1", {}, "dropout", ""),
+    "YTTM_K5_LANE_WORDS": ("0", {}, "encode", ""),
+    "YTTM_K5_LANE_SENT": ("0", {}, "encode", ""),
+    "YTTM_K5_CLASSES": ("1", {}, "encode", ""),
+}
+
+
+@pytest.mark.parametrize("hook", sorted(PATH_HOOK_CASES))
+def test_path_hook(hook, tmp_path, monkeypatch):
+    """Every path hook set away from its default, one at a time: the oracle's model (or ids), and where the report can show it, proof that
+    the path was taken."""
+    value, env, work, expect = PATH_HOOK_CASES[hook]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.setenv(hook, value)
+    S.check_path_hook(hook, work, expect, tmp_path)

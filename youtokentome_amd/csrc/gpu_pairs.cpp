@@ -106,15 +106,15 @@ void GpuCtx::pair_count() {
   uint32_t *rx_scratch = nullptr;
   unsigned long long *rx_buf1 = nullptr, *rx_buf2 = nullptr;
   // (its scratch -- two 8-byte records per class-A token -- must fit what is free with room to spare: else the general kernel, never an out-of-memory)
-  const bool radix = cls_[0].n_tiles && pair_count_radix_takes(n_ids, cls_[0].n_tokens0) && cls_[0].n_tokens0 >= cfg_->k3_radix_min.u && !cfg_->k3_general.set &&
-                     16ull * (cls_[0].n_tokens0 + 1) + (64ull << 20) <= free_device_bytes() / 4 * 3;
+  bool radix = cls_[0].n_tiles && pair_count_radix_takes(n_ids, cls_[0].n_tokens0) && cls_[0].n_tokens0 >= cfg_->k3_radix_min.u && !cfg_->k3_general.set &&
+               16ull * (cls_[0].n_tokens0 + 1) + (64ull << 20) <= free_device_bytes() / 4 * 3;
   if (radix) {
     rx_scratch = dmalloc<uint32_t>(pair_count_radix_scratch_u32(n_ids));
     rx_buf1 = dmalloc<unsigned long long>(cls_[0].n_tokens0 + 1);
     rx_buf2 = dmalloc<unsigned long long>(cls_[0].n_tokens0 + 1);
     HIP_CHECK(hipMemsetAsync(rx_scratch, 0, (size_t)n_ids * 4, strm()));
-    launch_pair_count_radix(cls_[0].ts, pt_, db_, id_min_, n_ids, rx_scratch, rx_buf1, rx_buf2, cls_[0].n_tokens0, strm());
-    k3_radix = 1;
+    radix = launch_pair_count_radix(cls_[0].ts, pt_, db_, id_min_, n_ids, rx_scratch, rx_buf1, rx_buf2, cls_[0].n_tokens0, strm());  // (false: nothing launched)
+    k3_radix = radix ? 1 : 0;
   }
   for (int ci = radix ? 1 : 0; ci < 2; ci++) launch_pair_count(ci, cls_[ci].ts, pt_, db_, id_min_, n_ids, strm());
   launch_giant(false, cls_[2].ts, cls_[2].slot, pt_, db_, nullptr, 0, 0xffffffffu, 0, cls_[2].d_scratch, d_stats_, strm());

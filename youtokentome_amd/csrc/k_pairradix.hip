@@ -77,7 +77,8 @@ __device__ inline void k3r_tile(const TileSet &ts, uint32_t tile, uint32_t *lw /
     const unsigned long long sel = (D & E & 0x5555555555555555ull) | (~D & E & 0xaaaaaaaaaaaaaaaaull);
     cont = (E >> 63) != 0ull;
     cont_even = cont && !(sel >> 63);
-    if (adj && (!eq || lane_bit(sel))) emit(c, a, t1, lw[k]);
+    const bool in_sel = lane_bit(sel);  // (read in converged code: sel is a wave-uniform mask)
+    if (adj && (!eq || in_sel)) emit(c, a, t1, lw[k]);
   }
 }
 
@@ -244,14 +245,16 @@ __global__ __launch_bounds__(K3R_NT) void k3r_final(const unsigned long long *__
 constexpr unsigned int K3R_GRID_MAX = 1024;  // (tile_grid(.., 4 waves, 4 per CU))
 size_t pair_count_radix_scratch_u32(uint32_t n_ids) { return (size_t)3 * n_ids + 256 + 8 + (size_t)2 * 256 * K3R_GRID_MAX; }  // hA | offA (+1) | cur2 | wgcnt | wgoff
 bool pair_count_radix_takes(uint32_t n_ids, unsigned long long n_tokens) { return n_ids > 64u && n_ids <= K3R_MAX_IDS && n_tokens < (1ull << 31); }
-void launch_pair_count_radix(const TileSet &ts, const PairTable &pt, const DeltaBuf &db, uint32_t id_min, uint32_t n_ids, uint32_t *scratch,
+bool launch_pair_count_radix(const TileSet &ts, const PairTable &pt, const DeltaBuf &db, uint32_t id_min, uint32_t n_ids, uint32_t *scratch,
                              unsigned long long *buf1, unsigned long long *buf2, unsigned long long n_tokens, hipStream_t st) {
-  if (!ts.n_tiles || !n_ids) return;
+  if (!ts.n_tiles || !n_ids) return true;
   const uint32_t s1 = k3r_shift1(n_ids), nb1 = ((n_ids - 1u) >> s1) + 1u;
   uint32_t *hA = scratch, *offA = scratch + n_ids, *cur2 = offA + n_ids + 1, *wgcnt = cur2 + n_ids + 7, *wgoff = wgcnt + (size_t)256 * K3R_GRID_MAX;
   // (hA = scratch[0 .. n_ids) arrives zeroed: the caller's memset)
-  const unsigned int g = tile_grid(ts.n_tiles, K3R_WAVES, 4);  // (<= K3R_GRID_MAX)
-  static_assert(K3R_GRID_MAX == 256u * 4u, "tile_grid(n, waves, 4 per CU) <= 1024");
+  const unsigned int g = tile_grid(ts.n_tiles, K3R_WAVES, 4);
+  // wgcnt / wgoff hold 256 level-1 groups x K3R_GRID_MAX workgroups: a larger grid (or more groups) would write past them -- the caller
+  // then counts with the general kernel
+  if (g > K3R_GRID_MAX || nb1 > 256u) return false;
   hipLaunchKernelGGL((k3r_hist<TILE_SLOT_A>), dim3(g), dim3(K3R_NT), 0, st, ts, id_min, n_ids, hA, s1, nb1, wgcnt);
   hipLaunchKernelGGL(k3r_offsets, dim3(1), dim3(K3R_NT), 0, st, (const uint32_t *)hA, n_ids, offA, cur2);
   hipLaunchKernelGGL(k3r_wgoffsets, dim3(nb1), dim3(K3R_NT), 0, st, (const uint32_t *)wgcnt, g, s1, (const uint32_t *)offA, wgoff);
@@ -260,5 +263,6 @@ void launch_pair_count_radix(const TileSet &ts, const PairTable &pt, const Delta
   const unsigned int g2 = (unsigned int)std::min<unsigned long long>(2048, n_tokens / K3R_CHUNK + 1), g3 = (unsigned int)std::min<unsigned long long>(2048, n_tokens / K3R_FCHUNK + 1);
   hipLaunchKernelGGL(k3r_scatter2, dim3(g2), dim3(K3R_NT), 0, st, (const unsigned long long *)buf1, (const uint32_t *)offA, n_ids, s1, cur2, buf2);
   hipLaunchKernelGGL(k3r_final, dim3(g3), dim3(K3R_NT), 0, st, (const unsigned long long *)buf2, (const uint32_t *)offA, id_min, n_ids, pt, db);
+  return true;
 }
 }  // namespace yttm

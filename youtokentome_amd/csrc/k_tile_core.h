@@ -848,10 +848,11 @@ __device__ inline void process_tile(WaveLds<SLOT> &W, AggLds &A, const TileSet &
           const unsigned long long smc = uni64(W.sitemask[c]);
           const int left = n - c * 64;
           const unsigned long long am = (left >= 64 ? ~0ull : (1ull << left) - 1ull) & ~((smc << 1) | (sm_prev >> 63));
-          if (lane_bit(am)) {
+          const bool surv = lane_bit(am), site = lane_bit(smc);
+          if (surv) {
             const uint32_t np = abase + lanes_below(am);
             const uint32_t t0 = W.tk[p];
-            dst[np] = lane_bit(smc) ? (NEWTOK(p) | (t0 & TOK_WS)) : (t0 & ~(L_ISX | L_ISY));
+            dst[np] = site ? (NEWTOK(p) | (t0 & TOK_WS)) : (t0 & ~(L_ISX | L_ISY));
           }
           abase += (uint32_t)__popcll(am);
           sm_prev = smc;

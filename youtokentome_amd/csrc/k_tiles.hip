@@ -485,7 +485,8 @@ __global__ __launch_bounds__(256) void k_pair_count_dense(TileSet ts, PairTable 
       const unsigned long long sel = (D & E & 0x5555555555555555ull) | (~D & E & 0xaaaaaaaaaaaaaaaaull);
       cont = (E >> 63) != 0ull;
       cont_even = cont && !(sel >> 63);
-      if (adj && (!eq || lane_bit(sel))) atomicAdd(&dense[base + (((a << sh) + t1) << lc)], (unsigned long long)lw[k]);
+      const bool in_sel = lane_bit(sel);  // (read in converged code: sel is a wave-uniform mask)
+      if (adj && (!eq || in_sel)) atomicAdd(&dense[base + (((a << sh) + t1) << lc)], (unsigned long long)lw[k]);
     }
     if (t + n_waves < ts.n_tiles) {
 #pragma unroll

@@ -357,7 +357,8 @@ __device__ inline unsigned long long lanemask_lt() { return (1ull << lane_id()) 
 // shuffle, is the same in every lane: it keeps it in vector registers and turns every loop and branch on it into exec-mask
 // code.  uni() moves it to scalar registers (v_readfirstlane); 64-bit masks then shift and count on the scalar unit,
 // lane_bit() selects a lane's bit of a uniform mask with one v_cndmask and lanes_below() counts the bits below the lane
-// with v_mbcnt.  MUST only be used on values that are uniform across the wave.
+// with v_mbcnt.  MUST only be used on values that are uniform across the wave, and uni() / lane_bit() where every live
+// lane of the wave calls them (not under a lane-dependent branch): the emulator (tests/hipsim) checks both.
 __device__ inline uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ inline int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ inline unsigned long long uni64(unsigned long long v) {
