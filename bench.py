@@ -1,23 +1,32 @@
 #!/usr/bin/env python3
 """bench.py -- BPE.train MB/s (+ encode sentences/s) on MI355X, vocab 32000  (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W            the headline alone
+    python bench.py --gpus N --steps K --warmup W --full     the headline and everything else below
 
 A "step" = one full BPE.train() -- SURVEY.md 8d's metric: file bytes / wall from the call to the model file closed.  The corpus FILE
 sits in the page cache (like the CPU baseline's input); a step is yttm_train_bpe_comm(path -> model): open, pread into pinned chunks,
-H2D, char histogram -> word dedup -> pair count -> merge loop -> model file.  That is `value`.  The same steps with the corpus ALREADY
-RESIDENT IN HBM are timed right after and reported beside it (`value_hbm_resident`; the kernel table and the roofline come from the
-timed file steps -- the kernels are the same).  Workload = BASELINE.json configs[1]: the 1 GB random 'abcd ' corpus of SURVEY.md
-Appendix C (seed 19, md5 pinned), vocab_size=32000.  N>1: one process per GPU (torchrun); every rank reads ITS byte range of the SAME
-pinned file, cut at whitespace (strong scaling -- the only way the N-GPU model can be compared with the reference's), pair-count
-deltas travel over RCCL each round.  `--scaling weak` gives every rank its own 1 GB instead (HBM-resident only; no pin exists for those
-corpora).  Rank 0 prints ONE JSON line: the headline, config, parity and rooflines, with the other blocks cut to their figures; the
-whole record goes to stderr as a `detail:` line.  `--dump-outputs DIR` writes what the timed paths returned in their last step (the
-trained model's arrays, a seeded sample of the encoded ids) to DIR/*.npy, so that two builds can be compared output for output.
+H2D, char histogram -> word dedup -> pair count -> merge loop -> model file.  That is `value`.  Workload = BASELINE.json configs[1]:
+the 1 GB random 'abcd ' corpus of SURVEY.md Appendix C (seed 19, md5 pinned), vocab_size=32000.  N>1: one process per GPU (torchrun);
+every rank reads ITS byte range of the SAME pinned file, cut at whitespace (strong scaling -- the only way the N-GPU model can be
+compared with the reference's), pair-count deltas travel over RCCL each round.  `--scaling weak` gives every rank its own 1 GB instead
+(HBM-resident only; no pin exists for those corpora).  Rank 0 prints ONE JSON line: the headline, config, parity and rooflines, with the
+other blocks cut to their figures; the whole record goes to stderr as a `detail:` line.  `--dump-outputs DIR` writes what the timed
+paths returned in their last step (the trained model's arrays, a seeded sample of the encoded ids) to DIR/*.npy, so that two builds can
+be compared output for output.
 
-Parity is part of the line: the md5 of every model the GPU writes (configs[1], the Zipf corpus of configs[2]) and the
-FNV of all 10 M encoded sentences (configs[3]) are compared with tests/golden/full_size_pins.json -- outputs of the
-UNMODIFIED reference (tests/golden/make_full_pins.py) -- and a mismatch makes the process exit non-zero.
+A plain run does what the headline needs and no more: it generates the corpus, warms up, times the K steps, compares the md5 of the
+model the last step wrote with the reference's (tests/golden/full_size_pins.json; a mismatch makes the process exit non-zero), writes
+the dump if asked (its encoded sample comes from one untimed encode of configs[3] by the path the full run dumps) and prints the line,
+whose `kernels` and `roofline` are what the timed steps report themselves.  Everything else this file measures and checks runs only
+with `--full` (the --no-* options trim a full run):
+
+The same steps with the corpus ALREADY RESIDENT IN HBM, timed right after the file steps and reported beside them (`value_hbm_resident`;
+the kernel table and the roofline come from the timed file steps -- the kernels are the same).
+
+Parity: the md5 of every corpus and of every model the GPU writes (configs[1], the Zipf corpus of configs[2]) and the FNV of all 10 M
+encoded sentences (configs[3]) are compared with tests/golden/full_size_pins.json -- outputs of the UNMODIFIED reference
+(tests/golden/make_full_pins.py) -- and a mismatch makes the process exit non-zero.
 
 Also on the line: `roofline` (dominant kernel; `achieved` = the contract's algorithmic bytes 8*T_touched + 8*W_touched, counted at word
 granularity by a separate untimed measurement pass, over the kernel's time by HIP events -- the device-clock figure of the timed steps beside it),
@@ -41,6 +50,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md) -- what `frac` is of
 HBM_COPY_GBS = 6290.0  # the measured float4-copy ceiling of the same guide ("report fraction of both") -- `frac_of_measured_copy`
 PINS = os.path.join(ROOT, "tests", "golden", "full_size_pins.json")
+ENCODE_LINE = 128  # configs[3]: sentences of 128 chars
 
 
 def log(*a):
@@ -121,6 +131,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)  # (five: the mean of two file -> model steps moved by 4 % with one slow upload among them)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline: the HBM-resident steps, the measurement passes behind the roofline, encode, the other "
+                         "corpora, the beyond-2^32 block, the CPU baseline and every comparison with the reference (a plain run checks the model md5 alone)")
     ap.add_argument("--size-mb", type=int, default=1000, help="corpus MB (1000 = BASELINE configs[1])")
     ap.add_argument("--vocab", type=int, default=32000)
     ap.add_argument("--corpus", default="abcd", choices=["abcd", "zipf", "cjk"])  # (zipf / cjk as the main workload: tools/profile_round.sh variants)
@@ -207,7 +220,7 @@ def main():
     ctx["comm"] = comm_handle
 
     # ---- main workload: configs[1] ------------------------------------------------------------------------------------
-    main_res = _bench_train(ctx, args.corpus, args.size_mb, args.steps, args.warmup, measure_touched=(world == 1 and not args.no_touched_pass), keep_host=True)
+    main_res = _bench_train(ctx, args.corpus, args.size_mb, args.steps, args.warmup, measure_touched=(args.full and world == 1 and not args.no_touched_pass), keep_host=True)
     out = {
         "metric": "bpe_train_throughput", "value": main_res["value"], "unit": "MB/s", "n_gpus": n_gpus, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": main_res["ms_per_step"], "higher_is_better": True,
@@ -235,7 +248,7 @@ def main():
                                                           "what": "the first yttm_train_bpe_comm(path -> model) of this process on the same file (an untimed warm-up step): cold device-memory pool, pinned chunks, streams, code objects"}
 
     # ---- encode: configs[3] (and [4]: dropout) with the model just trained --------------------------------------------------
-    if not args.no_encode:
+    if args.full and not args.no_encode:
         enc = _bench_encode(ctx, model_path, main_res)
         out["encode"] = enc["encode"]
         out["encode_dropout"] = enc["dropout"]
@@ -245,9 +258,11 @@ def main():
             out.setdefault("e2e", {}).update(enc["e2e"])
             # (what compares with the reference's encode_as_ids -- host strings in, host ids out -- is this one, not the device-resident rate)
             out["encode"]["value_host_to_host"] = enc["e2e"]["encode_host_to_host"]["value"]
+    elif args.dump_outputs and rank == 0 and not args.no_encode:
+        ctx["dump"].update(_encode_for_dump(ctx, model_path))
 
     # ---- configs[2]: the Zipf corpus -- thousands of short rounds, per-round latency is the whole game ----------------------
-    if not args.no_extra and args.corpus == "abcd":
+    if args.full and not args.no_extra and args.corpus == "abcd":
         z = _bench_train(ctx, "zipf", args.size_mb, args.steps, args.warmup, measure_touched=False, keep_host=(world == 1))
         zhost = z.pop("host", None)
         out["extra"] = {"zipf": {"metric": "bpe_train_throughput", "value": z["value"], "unit": "MB/s", "ms_per_step": z["ms_per_step"],
@@ -284,7 +299,7 @@ def main():
         zhost = None
 
     # ---- beyond 2^32: more than 4 GiB of text; a word seen more than 2^32 times (file -> model, pinned against the reference) ------------
-    if world == 1 and not args.no_big and args.corpus == "abcd" and args.size_mb == 1000:
+    if args.full and world == 1 and not args.no_big and args.corpus == "abcd" and args.size_mb == 1000:
         out.setdefault("extra", {})
         for name in (("c3_8gb", "c8_heavy_word") if args.big_zipf else ("c8_heavy_word",)):
             b = _bench_big(ctx, name)
@@ -296,7 +311,7 @@ def main():
                 out["parity"][name + "_corpus_md5_matches"] = b.pop("_corpus_ok")
 
     # ---- CPU baseline: the unmodified reference on this box's host cores (rank 0, N=1 only) --------------------------------
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = _cpu_baseline(ctx, host, zhost, model_path, out)
     shutil.rmtree(tmpdir, ignore_errors=True)
     bad = [k for k, v in out["parity"].items() if v is False]
@@ -387,7 +402,7 @@ def _make_corpus(ctx, corpus, size_mb):
         host = gen.zipf_corpus_fast(nbytes, seed=7 + seed_off, vocab=400000)
     pin = ctx["pins"].get(pin_name(corpus, size_mb)) if shared and args.vocab == 32000 else None
     corpus_ok = None
-    if pin is not None:
+    if pin is not None and args.full:
         corpus_ok = hashlib.md5(host).hexdigest() == pin["corpus_md5"]
     total = len(host)
     full = host if shared else None  # (the file of the file -> model steps: one file, every rank reads its byte range of it)
@@ -402,8 +417,9 @@ def _bench_train(ctx, corpus, size_mb, steps, warmup, measure_touched, keep_host
     rank, world, dev, local_rank, dist = ctx["rank"], ctx["world"], ctx["dev"], ctx["local_rank"], ctx["dist"]
     t0 = time.time()
     host, pin, corpus_ok, total_bytes, full = _make_corpus(ctx, corpus, size_mb)
-    d_corpus = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(dev)
-    n_local = d_corpus.numel()
+    # the shard in HBM: what the steps beside the file steps (--full) and the timed steps of --scaling weak (no file) read
+    d_corpus = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(dev) if (args.full or full is None) else None
+    n_local = len(host)
     if not ctx["strong"]:
         total_bytes = n_local * world
     tag = os.environ.get("MASTER_PORT", str(os.getpid()))
@@ -464,7 +480,7 @@ def _bench_train(ctx, corpus, size_mb, steps, warmup, measure_touched, keep_host
         ctx["barrier"]()
         dt = max_over_ranks(time.perf_counter() - t0)
         hbm = None
-        if corpus_path:  # the same steps without the read and the upload: input resident in HBM when the timed region starts
+        if corpus_path and args.full:  # the same steps without the read and the upload: input resident in HBM when the timed region starts
             train_step(0)
             ctx["barrier"]()
             t0 = time.perf_counter()
@@ -581,8 +597,8 @@ def _bench_train(ctx, corpus, size_mb, steps, warmup, measure_touched, keep_host
            "rounds_closed_exhausted": r.get("rounds_exhausted"), "word_mode_from_round": r.get("word_switch_round") or None, "word_mode_rounds": r.get("word_rounds"), "word_mode_one_launch_rounds": r.get("word_fused_rounds"),
            "index_builds": r.get("index_builds"), "batch_splits": r.get("batch_splits"), "batch_extensions": r.get("batch_extensions"),
            "hot_rebuilds": r.get("hot_rebuilds"), "top_refills": r.get("top_refills"), "repacks": r.get("repacks"),
-           "input": ("file in the page cache -> yttm_train_bpe_comm(path, model): open + pread into pinned chunks + H2D + train + model file closed (SURVEY.md 8d); "
-                     "the HBM-resident figure is `value_hbm_resident`") if corpus_path else "resident in HBM before the timed region (--scaling weak: one corpus per rank, no single file)",
+           "input": ("file in the page cache -> yttm_train_bpe_comm(path, model): open + pread into pinned chunks + H2D + train + model file closed (SURVEY.md 8d)"
+                     + ("; the HBM-resident figure is `value_hbm_resident`" if hbm else "")) if corpus_path else "resident in HBM before the timed region (--scaling weak: one corpus per rank, no single file)",
            "front_end_under_the_upload": bool(r.get("front_end_overlapped")),  # (K1, K2a, K2b ran on the parts of the file as they landed: their time is in phases_s.upload)
            "model_md5": model_md5, "pinned_model_md5": pin["model_md5"] if pin else None}
     if ctx["comm"] is not None:
@@ -778,15 +794,21 @@ def _encode_traffic(args, world, cached):
     return (sum(per.values()) if per else None), "static: profiles/%s, per batch of 10^7 sentences: %s" % (os.path.basename(f), per)
 
 
-def _bench_encode(ctx, model_path, main_res):
-    L, _lib, torch, np, gen, args = ctx["L"], ctx["_lib"], ctx["torch"], ctx["np"], ctx["gen"], ctx["args"]
-    rank, world, dev, local_rank, dist = ctx["rank"], ctx["world"], ctx["dev"], ctx["local_rank"], ctx["dist"]
-    n_sent = args.encode_sentences
-    line = 128
-    host = gen.abcd_corpus(n_sent * (line + 1), seed=123 + rank, line=line, survey_stream=True)  # SURVEY.md's C4 stream
-    n_sent = len(host) // (line + 1)
+def _encode_input(ctx):
+    """configs[3]'s sentences (SURVEY.md's C4 stream: ENCODE_LINE chars and a newline each) on the host, and in HBM with their offsets."""
+    torch, dev = ctx["torch"], ctx["dev"]
+    host = ctx["gen"].abcd_corpus(ctx["args"].encode_sentences * (ENCODE_LINE + 1), seed=123 + ctx["rank"], line=ENCODE_LINE, survey_stream=True)
+    n_sent = len(host) // (ENCODE_LINE + 1)
     d_bytes = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(dev)
-    d_off = (torch.arange(n_sent + 1, dtype=torch.int64, device=dev) * (line + 1))
+    d_off = (torch.arange(n_sent + 1, dtype=torch.int64, device=dev) * (ENCODE_LINE + 1))
+    return host, n_sent, d_bytes, d_off
+
+
+def _bench_encode(ctx, model_path, main_res):
+    L, _lib, torch, np, args = ctx["L"], ctx["_lib"], ctx["torch"], ctx["np"], ctx["args"]
+    rank, world, dev, local_rank, dist = ctx["rank"], ctx["world"], ctx["dev"], ctx["local_rank"], ctx["dist"]
+    line = ENCODE_LINE
+    host, n_sent, d_bytes, d_off = _encode_input(ctx)
     err = C.create_string_buffer(_lib.ERRLEN)
     h = C.c_void_p()
     # every rank loads the model written by rank 0's trainer (identical on all ranks by construction)
@@ -910,6 +932,32 @@ def _bench_encode(ctx, model_path, main_res):
     del d_bytes, d_off
     torch.cuda.empty_cache()
     return res
+
+
+def _encode_for_dump(ctx, model_path):
+    """--dump-outputs of a plain run: the sample _bench_encode dumps, from ONE untimed encode of configs[3]'s sentences by the path whose
+    ids it dumps (the word cache, set as it sets it).  Encoding without dropout is deterministic: the ids do not depend on the calls before."""
+    L, _lib, torch, np = ctx["L"], ctx["_lib"], ctx["torch"], ctx["np"]
+    _, n_sent, d_bytes, d_off = _encode_input(ctx)
+    err = C.create_string_buffer(_lib.ERRLEN)
+    h = C.c_void_p()
+    if L.yttm_encoder_create(model_path.encode(), 1, ctx["local_rank"], C.byref(h), err, _lib.ERRLEN) != 0:
+        raise RuntimeError(err.value.decode())
+    try:
+        L.yttm_encoder_set_cache(h, 2, 8 << 20)
+        n_ids, kms = C.c_uint64(), C.c_double()
+        if L.yttm_encode_device(h, C.c_void_p(d_bytes.data_ptr()), C.c_void_p(d_off.data_ptr()), n_sent, d_bytes.numel(), ENCODE_LINE + 1, 0, 0, 0, 0.0,
+                                C.byref(n_ids), C.byref(kms), err, _lib.ERRLEN) != 0:
+            raise RuntimeError(err.value.decode())
+        ids = np.zeros(n_ids.value, dtype=np.int32)
+        off = np.zeros(n_sent + 1, dtype=np.uint64)
+        if L.yttm_encode_fetch(h, ids.ctypes.data_as(_lib.i32p), off.ctypes.data_as(_lib.u64p), n_sent, err, _lib.ERRLEN) != 0:
+            raise RuntimeError(err.value.decode())
+    finally:
+        L.yttm_encoder_destroy(h)
+    del d_bytes, d_off
+    torch.cuda.empty_cache()
+    return _encode_sample(np, ids, off, n_sent)
 
 
 def _dropout_distribution(np, ids, off, m, pin):

@@ -28,7 +28,7 @@ P
     zipf) timeout 400 bash tools/profile_round.sh r6_zipf zipf > gpurun_out/r6_profile_zipf.log 2>&1; head -5 profiles/r6_zipf_kernel_stats.csv ;;
     encode) timeout 600 bash tools/profile_round.sh r6_encode10m encode > gpurun_out/r6_profile_encode.log 2>&1; grep "k5" profiles/r6_encode10m_kernel_stats.csv | head -8 ;;
     comm)
-      YTTM_BENCH_FORCE_COMM=1 timeout 600 python bench.py --no-cpu-baseline --no-e2e --no-big > profiles/r6_forced_comm_bench.json 2> gpurun_out/r6_forced_comm.err
+      YTTM_BENCH_FORCE_COMM=1 timeout 600 python bench.py --full --no-cpu-baseline --no-e2e --no-big > profiles/r6_forced_comm_bench.json 2> profiles/r6_forced_comm.err
       python - <<'P'
 import json
 d = json.loads(open("profiles/r6_forced_comm_bench.json").read().strip().splitlines()[-1])

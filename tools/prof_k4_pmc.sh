@@ -2,7 +2,7 @@
 # SQ counters of the K4 kernels (tuning aid; separate --pmc passes, no trace domains). usage: bash tools/prof_k4_pmc.sh
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
-CMD="python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-encode"
+CMD="python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-encode"
 i=0
 for grp in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA" "SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_INSTS_VMEM_WR"; do
   i=$((i+1))

@@ -3,7 +3,7 @@
 # usage (GPU box): bash tools/prof_k4_valu.sh   -> gpurun_out/valu_rounds.txt, gpurun_out/valu_pmc/
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
-CMD="python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-encode"
+CMD="python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-encode"
 YTTM_TRACE_ROUNDS=$R/gpurun_out/valu_rounds.txt timeout 400 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES \
   --kernel-include-regex "k_tiles" --output-format csv -d $R/gpurun_out/valu_pmc -- $CMD > $R/gpurun_out/valu_pmc.log 2>&1
 python - <<'PY'
