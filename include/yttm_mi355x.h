@@ -72,6 +72,13 @@ int yttm_encode_device(yttm_encoder *enc, const void *d_bytes, const void *d_off
                        uint64_t total_bytes, uint64_t max_sentence_bytes, int bos, int eos, int reverse,
                        double dropout_prob, uint64_t *n_ids, double *kernel_ms, char *err, int errlen);
 int yttm_encode_fetch(yttm_encoder *enc, int32_t *ids, uint64_t *out_offsets, uint64_t n_sent, char *err, int errlen);
+/* The result of the last yttm_encode_device, device to device into memory the caller owns (a framework's tensors): ragged
+ * (int32 ids[n_ids], uint64 out_offsets[n_sent+1]), or as a row-major int32 matrix [n_sent, width] whose row tails hold pad_value, plus
+ * int32 lengths[n_sent] (k_enc_pad).  *longest = the longest row; width < longest is an error (code 1) and writes nothing: no row is
+ * truncated.  The reference has no counterpart: its encode_as_ids fills vector<vector<int>>, bpe.h:36-39, bpe.cpp:1736-1755. */
+int yttm_encode_copy_device(yttm_encoder *enc, void *d_ids, void *d_out_offsets, uint64_t n_sent, char *err, int errlen);
+int yttm_encode_copy_padded(yttm_encoder *enc, void *d_matrix, void *d_lengths, uint64_t n_sent, uint64_t width, int32_t pad_value,
+                            uint64_t *longest, char *err, int errlen);
 
 /* Word-level encode cache (SURVEY.md 8f "N4"; the reference has no counterpart: bpe.cpp:1497-1632 encodes every word occurrence).
  * mode 0: every batch goes straight through the encode kernel; 1: distinct words are encoded once whenever that is possible
@@ -88,6 +95,21 @@ int yttm_subword_to_id(yttm_encoder *enc, const char *token);
  *                                                                     bpe.h:52-54, bpe.cpp:1828; yttm.pyx:136-158 */
 int yttm_decode(yttm_encoder *enc, const int32_t *ids, const uint64_t *offsets, uint64_t n_sent, const int32_t *ignore_ids,
                 uint64_t n_ignore, char **blob, uint64_t **out_offsets, char *err, int errlen);
+/* Device-resident batch decode.  ids/offsets already in HBM (int32[n_ids], uint64[n_sent+1]); ignore_ids is a host array.  The text stays in HBM
+ * inside the encoder until yttm_decode_fetch / yttm_decode_copy_device takes it (char bytes[*n_bytes], uint64 out_offsets[n_sent+1]); it does not
+ * replace a pending yttm_encode_device result, nor the other way round.  An id outside [0, vocab_size) that is not ignored fails the call with
+ * the message and code (1) of yttm_decode, naming the first such id in sentence order, then position order.  kernel_ms (optional) = HIP-event
+ * time of measure + scan + write.  The caller makes ids/offsets visible first (synchronises the stream that wrote them).
+ * replaces: BaseEncoder::decode, bpe.h:52-54, bpe.cpp:1828-1861 (on id_to_subword(id, &s, true), bpe.cpp:1774-1807) */
+int yttm_decode_device(yttm_encoder *enc, const void *d_ids, const void *d_offsets, uint64_t n_sent, uint64_t n_ids, const int32_t *ignore_ids,
+                       uint64_t n_ignore, uint64_t *n_bytes, double *kernel_ms, char *err, int errlen);
+/* the same for a padded matrix: row i = d_ids[i*row_stride .. i*row_stride + len_i), len_i = d_lengths ? d_lengths[i] : width
+ * (d_lengths: int32[n_sent] in HBM or NULL; a length outside [0, width] counts as 0 or width); row_stride >= width.  bpe.cpp:1828-1861 */
+int yttm_decode_device_padded(yttm_encoder *enc, const void *d_ids, uint64_t n_sent, uint64_t width, uint64_t row_stride, const void *d_lengths,
+                              const int32_t *ignore_ids, uint64_t n_ignore, uint64_t *n_bytes, double *kernel_ms, char *err, int errlen);
+/* the text of the last yttm_decode_device[_padded]: to host arrays / to device memory the caller owns.  bpe.cpp:1828-1841 (the batch loop) */
+int yttm_decode_fetch(yttm_encoder *enc, char *bytes, uint64_t *out_offsets, uint64_t n_sent, char *err, int errlen);
+int yttm_decode_copy_device(yttm_encoder *enc, void *d_bytes, void *d_out_offsets, uint64_t n_sent, char *err, int errlen);
 /* int vocab_size() const                                              bpe.h:62, bpe.cpp:1692; yttm.pyx:160-161 */
 int yttm_vocab_size(yttm_encoder *enc);
 /* vector<string> vocabulary() const                                   bpe.h:64, bpe.cpp:1884; yttm.pyx:163-165 */

@@ -59,6 +59,7 @@ class _Core:
         if rc != 0:
             raise ValueError(err.value.decode())  # yttm.pyx:61-62
         self._h = h
+        self.device = device
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -95,6 +96,67 @@ class _Core:
         off_a = _take(off, n + 1, C.c_uint64, np.uint64)
         ids_a = _take(ids, int(off_a[-1]), C.c_int32, np.int32)
         return ids_a, off_a
+
+    # ---- raw device layer (include/yttm_mi355x.h): integer device pointers and sizes, no framework.  youtokentome_amd/tensor.py puts torch
+    # tensors on top; the emulator tests pass numpy arrays (there host pointers are device pointers).  The caller makes its inputs visible
+    # first; every call returns after the encoder's stream has synchronised.
+    def _check(self, rc, err):
+        if rc != 0:
+            raise ValueError(err.value.decode())
+
+    def encode_device_raw(self, d_bytes, d_offsets, n_sent, total_bytes, max_sentence_bytes, bos=False, eos=False, reverse=False, dropout_prob=0.0):
+        """-> (n_ids, kernel_ms); the ids stay in the encoder until copy_encode_* / yttm_encode_fetch takes them"""
+        n, ms, err = C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_encode_device(self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n_sent, total_bytes, max_sentence_bytes, int(bos),
+                                                   int(eos), int(reverse), float(dropout_prob), C.byref(n), C.byref(ms), err, _lib.ERRLEN), err)
+        return n.value, ms.value
+
+    def copy_encode_device(self, d_ids, d_out_offsets, n_sent):
+        err = _err()
+        self._check(_lib.load().yttm_encode_copy_device(self._h, C.c_void_p(d_ids), C.c_void_p(d_out_offsets), n_sent, err, _lib.ERRLEN), err)
+
+    def encode_longest(self, n_sent):
+        """longest row of the pending encode result (asks for a matrix of width 0: nothing is written when a row is longer)"""
+        longest, err = C.c_uint64(), _err()
+        _lib.load().yttm_encode_copy_padded(self._h, None, None, n_sent, 0, 0, C.byref(longest), err, _lib.ERRLEN)
+        return longest.value
+
+    def copy_encode_padded(self, d_matrix, d_lengths, n_sent, width, pad_value):
+        """-> longest row; ValueError when width is smaller"""
+        longest, err = C.c_uint64(), _err()
+        self._check(_lib.load().yttm_encode_copy_padded(self._h, C.c_void_p(d_matrix), C.c_void_p(d_lengths), n_sent, width, int(pad_value),
+                                                        C.byref(longest), err, _lib.ERRLEN), err)
+        return longest.value
+
+    @staticmethod
+    def _ignore(ignore_ids):
+        ign = np.ascontiguousarray(sorted(set(int(i) for i in (ignore_ids or ()))), dtype=np.int32)
+        return ign, ign.ctypes.data_as(_lib.i32p), len(ign)
+
+    def decode_device_raw(self, d_ids, d_offsets, n_sent, n_ids, ignore_ids=None):
+        """-> (n_bytes, kernel_ms); the text stays in the encoder until fetch_decode / copy_decode_device takes it"""
+        ign, ign_p, n_ign = self._ignore(ignore_ids)
+        n, ms, err = C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_decode_device(self._h, C.c_void_p(d_ids), C.c_void_p(d_offsets), n_sent, n_ids, ign_p, n_ign, C.byref(n), C.byref(ms),
+                                                   err, _lib.ERRLEN), err)
+        return n.value, ms.value
+
+    def decode_device_padded_raw(self, d_ids, n_sent, width, row_stride, d_lengths=None, ignore_ids=None):
+        ign, ign_p, n_ign = self._ignore(ignore_ids)
+        n, ms, err = C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_decode_device_padded(self._h, C.c_void_p(d_ids), n_sent, width, row_stride, C.c_void_p(d_lengths), ign_p, n_ign,
+                                                          C.byref(n), C.byref(ms), err, _lib.ERRLEN), err)
+        return n.value, ms.value
+
+    def fetch_decode(self, n_sent, n_bytes):
+        """-> (uint8 bytes[n_bytes], uint64 offsets[n_sent + 1]) on the host"""
+        raw, off, err = np.empty(max(int(n_bytes), 1), np.uint8), np.zeros(n_sent + 1, np.uint64), _err()
+        self._check(_lib.load().yttm_decode_fetch(self._h, C.c_void_p(raw.ctypes.data), off.ctypes.data_as(_lib.u64p), n_sent, err, _lib.ERRLEN), err)
+        return raw[:int(n_bytes)], off
+
+    def copy_decode_device(self, d_bytes, d_out_offsets, n_sent):
+        err = _err()
+        self._check(_lib.load().yttm_decode_copy_device(self._h, C.c_void_p(d_bytes), C.c_void_p(d_out_offsets), n_sent, err, _lib.ERRLEN), err)
 
     def encode(self, sentences, output_type, bos, eos, reverse, dropout_prob):
         if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
@@ -254,6 +316,17 @@ class BPE:
 
     def decode(self, ids: Union[List[int], List[List[int]]], ignore_ids: Optional[Collection] = None) -> List[str]:
         return self.bpe_cython.decode(ids, ignore_ids)
+
+    # ---- device tensors in, device tensors out (youtokentome_amd/tensor.py; the reference has no counterpart)
+    def encode_tensor(self, sentences, bos: bool = False, eos: bool = False, reverse: bool = False, dropout_prob: float = 0, padded: bool = True,
+                      width: Optional[int] = None, pad_id: Optional[int] = None, device=None):
+        from . import tensor
+        return tensor.encode_tensor(self, sentences, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, padded=padded, width=width,
+                                    pad_id=pad_id, device=device)
+
+    def decode_tensor(self, ids, lengths=None, offsets=None, ignore_ids: Optional[Collection] = None, as_str: bool = True):
+        from . import tensor
+        return tensor.decode_tensor(self, ids, lengths=lengths, offsets=offsets, ignore_ids=ignore_ids, as_str=as_str)
 
     def __getstate__(self):
         return {"model": self.model, "n_threads": self.n_threads}

@@ -173,6 +173,37 @@ int yttm_encode_fetch(yttm_encoder *h, int32_t *ids, uint64_t *out_offsets, uint
   return finish(h->enc->fetch_device_result(ids, (unsigned long long *)out_offsets, n_sent), err, errlen);
 }
 
+int yttm_encode_copy_device(yttm_encoder *h, void *d_ids, void *d_out_offsets, uint64_t n_sent, char *err, int errlen) {
+  return finish(h->enc->copy_encode_result(d_ids, d_out_offsets, n_sent), err, errlen);
+}
+int yttm_encode_copy_padded(yttm_encoder *h, void *d_matrix, void *d_lengths, uint64_t n_sent, uint64_t width, int32_t pad_value, uint64_t *longest,
+                            char *err, int errlen) {
+  unsigned long long need = 0;
+  Status s = h->enc->copy_encode_padded(d_matrix, d_lengths, n_sent, width, pad_value, &need);
+  if (longest) *longest = need;
+  return finish(s, err, errlen);
+}
+int yttm_decode_device(yttm_encoder *h, const void *d_ids, const void *d_offsets, uint64_t n_sent, uint64_t n_ids, const int32_t *ignore_ids,
+                       uint64_t n_ignore, uint64_t *n_bytes, double *kernel_ms, char *err, int errlen) {
+  unsigned long long n = 0;
+  Status s = h->enc->decode_device(d_ids, d_offsets, n_sent, n_ids, ignore_ids, n_ignore, &n, kernel_ms);
+  if (n_bytes) *n_bytes = n;
+  return finish(s, err, errlen);
+}
+int yttm_decode_device_padded(yttm_encoder *h, const void *d_ids, uint64_t n_sent, uint64_t width, uint64_t row_stride, const void *d_lengths,
+                              const int32_t *ignore_ids, uint64_t n_ignore, uint64_t *n_bytes, double *kernel_ms, char *err, int errlen) {
+  unsigned long long n = 0;
+  Status s = h->enc->decode_device_padded(d_ids, n_sent, width, row_stride, d_lengths, ignore_ids, n_ignore, &n, kernel_ms);
+  if (n_bytes) *n_bytes = n;
+  return finish(s, err, errlen);
+}
+int yttm_decode_fetch(yttm_encoder *h, char *bytes, uint64_t *out_offsets, uint64_t n_sent, char *err, int errlen) {
+  return finish(h->enc->fetch_decode_result(bytes, (unsigned long long *)out_offsets, n_sent), err, errlen);
+}
+int yttm_decode_copy_device(yttm_encoder *h, void *d_bytes, void *d_out_offsets, uint64_t n_sent, char *err, int errlen) {
+  return finish(h->enc->copy_decode_result(d_bytes, d_out_offsets, n_sent), err, errlen);
+}
+
 int yttm_encoder_set_cache(yttm_encoder *h, int mode, uint64_t min_bytes) {
   h->enc->set_cache(mode, min_bytes);
   return 0;

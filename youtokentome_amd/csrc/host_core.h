@@ -114,6 +114,18 @@ class BaseEncoder {  // bpe.h:22-82
                        unsigned long long max_sentence_bytes, bool bos, bool eos, bool reverse, double dropout_prob,
                        unsigned long long *n_ids_out, double *kernel_ms) const;
   Status fetch_device_result(int32_t *ids, unsigned long long *out_off, unsigned long long n_sent) const;
+  // device decode (host_decode.h, k_decode.h): ids + offsets (or a padded matrix) already in HBM, the text left in HBM in lane 0 next to the
+  // encode result; ignore_ids is a host array.  replaces decode(), bpe.h:52-54, bpe.cpp:1828-1861, for a batch
+  Status decode_device(const void *d_ids, const void *d_offsets, unsigned long long n_sent, unsigned long long n_ids, const int32_t *ignore_ids,
+                       unsigned long long n_ignore, unsigned long long *n_bytes, double *kernel_ms) const;
+  Status decode_device_padded(const void *d_ids, unsigned long long n_sent, unsigned long long width, unsigned long long row_stride, const void *d_lengths,
+                              const int32_t *ignore_ids, unsigned long long n_ignore, unsigned long long *n_bytes, double *kernel_ms) const;
+  Status fetch_decode_result(char *bytes, unsigned long long *out_off, unsigned long long n_sent) const;      // device to host
+  Status copy_decode_result(void *d_bytes, void *d_out_off, unsigned long long n_sent) const;                 // device to device
+  // the result of the last encode_device, device to device: ragged, or as a padded matrix + lengths (k_enc_pad)
+  Status copy_encode_result(void *d_ids, void *d_out_off, unsigned long long n_sent) const;
+  Status copy_encode_padded(void *d_matrix, void *d_lengths, unsigned long long n_sent, unsigned long long width, int32_t pad_value,
+                            unsigned long long *longest) const;
   // the YTTM_* hooks as they stood when THIS encoder was made: every entry point binds them to its thread (yttm_config.h CfgBind), so that a
   // later encoder or training never changes the paths of this one
   std::shared_ptr<const Config> config() const;

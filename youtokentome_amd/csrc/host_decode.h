@@ -1,0 +1,253 @@
+// host_decode.h -- host side of the device decode (k_decode.h) and the device-to-device exits of the encoder's and the decoder's results.
+// Part of host_encoder.cpp (included there: it works on the encoder's lanes).
+//
+// Results live in lane 0 like those of encode_device, in buffers of their own: a decode leaves a pending encode result alone and the other way
+// round.  Every call locks the lane and returns after the lane's stream has synchronised; a pair (decode_device, fetch) is not atomic.
+#pragma once
+
+namespace yttm {
+
+// The text of every id, once per encoder: from the host's id_to_subword(id, replace_space = true), so that the device path cannot drift from
+// the host path.  An id the host function refuses is marked (DEC_INVALID) and reported by the device path the same way.
+static void decode_table(const BaseEncoder &enc, EncoderDevice &D) {
+  std::lock_guard<std::mutex> lk(D.dec_mu);
+  if (D.dec_ready) return;
+  const int V = enc.vocab_size();
+  std::string blob, piece;
+  std::vector<uint32_t> off((size_t)V + 1, 0);
+  for (int id = 0; id < V; id++) {
+    if (blob.size() >= (size_t)DEC_INVALID) throw GpuError{"decode: the vocabulary's text does not fit 2 GB"};
+    off[(size_t)id] = (uint32_t)blob.size();
+    piece.clear();
+    bool ok = false;
+    try {
+      ok = enc.id_to_subword(id, &piece, true).ok();
+    } catch (const std::exception &) {
+    }
+    if (ok) blob += piece;
+    else off[(size_t)id] |= DEC_INVALID;
+  }
+  if (blob.size() >= (size_t)DEC_INVALID) throw GpuError{"decode: the vocabulary's text does not fit 2 GB"};
+  off[(size_t)V] = (uint32_t)blob.size();
+  uint8_t *d_blob = dalloc<uint8_t>(blob.size() + 1);
+  uint32_t *d_off = nullptr;
+  try {
+    d_off = dalloc<uint32_t>(off.size());
+    if (!blob.empty()) HIP_CHECK(hipMemcpy(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+  } catch (...) {
+    (void)hipFree(d_blob);
+    if (d_off) (void)hipFree(d_off);
+    throw;
+  }
+  D.d_piece_blob = d_blob;
+  D.d_piece_off = d_off;
+  D.dec_vocab = (uint32_t)V;
+  D.dec_ready = true;
+}
+
+// measure -> scan -> write on the lane (locked by the caller).  n_flat: the ids the kernels walk (ragged: n_ids; padded: n_sent * stride).
+static Status decode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, DecInput in, unsigned long long n_flat,
+                             const int32_t *ignore_ids, unsigned long long n_ignore, unsigned long long *n_bytes, double *kernel_ms) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  struct Events {
+    hipEvent_t &a, &b;
+    ~Events() {
+      if (a) (void)hipEventDestroy(a);
+      if (b) (void)hipEventDestroy(b);
+    }
+  } events{e0, e1};
+  try {
+    HIP_CHECK(hipSetDevice(device));
+    d.dec_valid = false;
+    if (n_bytes) *n_bytes = 0;
+    if (kernel_ms) *kernel_ms = 0;
+    if (in.n_sent == 0) {
+      d.dec_n_sent = d.dec_n_bytes = 0;
+      d.dec_valid = true;
+      return Status();
+    }
+    decode_table(enc, D);
+    const DecTable tb{D.d_piece_blob, D.d_piece_off, D.dec_vocab};
+    DecIgnore ig{nullptr, nullptr, 0, 0};
+    if (n_ignore) {
+      const size_t words = ((size_t)D.dec_vocab + 31) / 32 + 1;
+      std::vector<uint32_t> host(words, 0);
+      std::vector<int32_t> extra;
+      for (unsigned long long i = 0; i < n_ignore; i++) {
+        const int32_t id = ignore_ids[i];
+        if ((uint32_t)id < D.dec_vocab) host[(uint32_t)id >> 5] |= 1u << ((uint32_t)id & 31u);
+        else extra.push_back(id);
+      }
+      std::sort(extra.begin(), extra.end());
+      extra.erase(std::unique(extra.begin(), extra.end()), extra.end());
+      for (int32_t id : extra) host.push_back((uint32_t)id);
+      d.grow(d.d_dec_ign, d.cap_dec_ign, host.size());
+      HIP_CHECK(hipMemcpy(d.d_dec_ign, host.data(), host.size() * 4, hipMemcpyHostToDevice));  // (the lane's stream is idle; the vector ends with this call)
+      ig = DecIgnore{d.d_dec_ign, (const int32_t *)(d.d_dec_ign + words), (uint32_t)extra.size(), 1u};
+    }
+    if (!d.d_dec_misc) d.d_dec_misc = dalloc<unsigned long long>(2);
+    d.grow(d.d_dec_len, d.cap_dec_len, (size_t)in.n_sent);
+    d.grow(d.d_dec_off, d.cap_dec_off, (size_t)in.n_sent + 1);
+    if (kernel_ms) {
+      HIP_CHECK(hipEventCreate(&e0));
+      HIP_CHECK(hipEventCreate(&e1));
+      HIP_CHECK(hipEventRecord(e0, d.st));
+    }
+    HIP_CHECK(hipMemsetAsync(d.d_dec_misc, 0xff, 8, d.st));
+    launch_decode_measure(in, tb, ig, n_flat, d.d_dec_len, d.d_dec_misc, d.st);
+    unsigned long long bad = ~0ull;
+    HIP_CHECK(hipMemcpyAsync(&bad, d.d_dec_misc, 8, hipMemcpyDeviceToHost, d.st));
+    const unsigned long long total = scan_counts(d, d.d_dec_len, in.n_sent, d.d_dec_off);  // (syncs: `bad` is here)
+    if (bad != ~0ull) {  // the first id, in sentence order then position order, that is neither ignored nor valid: the host path's message
+      int32_t id = 0;
+      HIP_CHECK(hipMemcpyAsync(&id, in.ids + bad, 4, hipMemcpyDeviceToHost, d.st));
+      HIP_CHECK(hipStreamSynchronize(d.st));
+      std::string piece;
+      Status st = enc.id_to_subword(id, &piece, true);
+      return st.ok() ? Status(1, "decode: no text for id " + std::to_string(id)) : st;
+    }
+    d.grow(d.d_dec_bytes, d.cap_dec_bytes, (size_t)total + 16);
+    if (((uintptr_t)d.d_dec_bytes & 15u) != 0) throw GpuError{"decode: the output blob is not 16-byte aligned"};
+    launch_decode_write(in, tb, ig, n_flat, d.d_dec_off, d.d_dec_bytes, d.st);
+    if (kernel_ms) HIP_CHECK(hipEventRecord(e1, d.st));
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    if (kernel_ms) {
+      float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+      *kernel_ms = ms;
+    }
+    d.dec_n_sent = in.n_sent;
+    d.dec_n_bytes = total;
+    d.dec_valid = true;
+    if (n_bytes) *n_bytes = total;
+  } catch (const GpuError &e) {
+    return Status(2, "GPU error: " + e.msg);
+  }
+  return Status();
+}
+
+Status BaseEncoder::decode_device(const void *d_ids, const void *d_offsets, unsigned long long n_sent, unsigned long long n_ids, const int32_t *ignore_ids,
+                                  unsigned long long n_ignore, unsigned long long *n_bytes, double *kernel_ms) const {
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (n_sent && !d_offsets) return Status(2, "decode_device: no offsets");
+  const CfgBind bind(dev_->cfg);
+  std::lock_guard<std::mutex> lk(dev_->lane[0].mu);
+  const DecInput in{(const int32_t *)d_ids, (const unsigned long long *)d_offsets, nullptr, 0, 0, n_sent};
+  return decode_on_lane(*this, *dev_, dev_->lane[0], device_, in, n_ids, ignore_ids, n_ignore, n_bytes, kernel_ms);
+}
+
+Status BaseEncoder::decode_device_padded(const void *d_ids, unsigned long long n_sent, unsigned long long width, unsigned long long row_stride,
+                                         const void *d_lengths, const int32_t *ignore_ids, unsigned long long n_ignore, unsigned long long *n_bytes,
+                                         double *kernel_ms) const {
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (row_stride < width) return Status(2, "decode_device_padded: row_stride is smaller than width");
+  if (row_stride == 0) row_stride = 1;  // (width 0: rows without ids)
+  if (n_sent > (~0ull >> 1) / row_stride) return Status(2, "decode_device_padded: the matrix is too large");
+  const CfgBind bind(dev_->cfg);
+  std::lock_guard<std::mutex> lk(dev_->lane[0].mu);
+  const DecInput in{(const int32_t *)d_ids, nullptr, (const int32_t *)d_lengths, width, row_stride, n_sent};
+  return decode_on_lane(*this, *dev_, dev_->lane[0], device_, in, n_sent * row_stride, ignore_ids, n_ignore, n_bytes, kernel_ms);
+}
+
+Status BaseEncoder::fetch_decode_result(char *bytes, unsigned long long *out_off, unsigned long long n_sent) const {
+  if (!dev_) return Status(2, "fetch_decode_result: no matching result");
+  const CfgBind bind(dev_->cfg);
+  EncodeLane &d = dev_->lane[0];
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (!d.dec_valid || n_sent != d.dec_n_sent) return Status(2, "fetch_decode_result: no matching result");
+  try {
+    HIP_CHECK(hipSetDevice(device_));
+    if (n_sent == 0) { if (out_off) out_off[0] = 0; return Status(); }
+    if (bytes && d.dec_n_bytes) copy_down(device_, bytes, d.d_dec_bytes, (size_t)d.dec_n_bytes, d.st);
+    if (out_off) copy_down(device_, out_off, d.d_dec_off, (size_t)(n_sent + 1) * 8, d.st);
+    HIP_CHECK(hipStreamSynchronize(d.st));
+  } catch (const GpuError &e) {
+    return Status(2, "GPU error: " + e.msg);
+  }
+  return Status();
+}
+
+// device to device, into memory the caller owns (a framework's tensors): src -> dst on the lane's stream, then the stream's sync
+static Status copy_pair_device(int device, EncodeLane &d, void *dst_a, const void *src_a, size_t n_a, void *dst_b, const void *src_b, size_t n_b) {
+  try {
+    HIP_CHECK(hipSetDevice(device));
+    if (dst_a && n_a) HIP_CHECK(hipMemcpyAsync(dst_a, src_a, n_a, hipMemcpyDeviceToDevice, d.st));
+    if (dst_b && n_b) HIP_CHECK(hipMemcpyAsync(dst_b, src_b, n_b, hipMemcpyDeviceToDevice, d.st));
+    HIP_CHECK(hipStreamSynchronize(d.st));
+  } catch (const GpuError &e) {
+    return Status(2, "GPU error: " + e.msg);
+  }
+  return Status();
+}
+
+Status BaseEncoder::copy_decode_result(void *d_bytes, void *d_out_off, unsigned long long n_sent) const {
+  if (!dev_) return Status(2, "copy_decode_result: no matching result");
+  const CfgBind bind(dev_->cfg);
+  EncodeLane &d = dev_->lane[0];
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (!d.dec_valid || n_sent != d.dec_n_sent) return Status(2, "copy_decode_result: no matching result");
+  if (n_sent == 0) {  // (nothing was launched and no buffer exists: the one offset is 0)
+    try {
+      HIP_CHECK(hipSetDevice(device_));
+      if (d_out_off) HIP_CHECK(hipMemsetAsync(d_out_off, 0, 8, d.st));
+      HIP_CHECK(hipStreamSynchronize(d.st));
+    } catch (const GpuError &e) {
+      return Status(2, "GPU error: " + e.msg);
+    }
+    return Status();
+  }
+  return copy_pair_device(device_, d, d_bytes, d.d_dec_bytes, (size_t)d.dec_n_bytes, d_out_off, d.d_dec_off, (size_t)(n_sent + 1) * 8);
+}
+
+Status BaseEncoder::copy_encode_result(void *d_ids, void *d_out_off, unsigned long long n_sent) const {
+  if (!dev_) return Status(2, "copy_encode_result: no matching result");
+  const CfgBind bind(dev_->cfg);
+  EncodeLane &d = dev_->lane[0];
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (n_sent != d.last_n_sent) return Status(2, "copy_encode_result: no matching result");
+  if (n_sent == 0) {
+    try {
+      HIP_CHECK(hipSetDevice(device_));
+      if (d_out_off) HIP_CHECK(hipMemsetAsync(d_out_off, 0, 8, d.st));
+      HIP_CHECK(hipStreamSynchronize(d.st));
+    } catch (const GpuError &e) {
+      return Status(2, "GPU error: " + e.msg);
+    }
+    return Status();
+  }
+  return copy_pair_device(device_, d, d_ids, d.d_ids, (size_t)d.last_n_ids * 4, d_out_off, d.d_out_off, (size_t)(n_sent + 1) * 8);
+}
+
+Status BaseEncoder::copy_encode_padded(void *d_matrix, void *d_lengths, unsigned long long n_sent, unsigned long long width, int32_t pad_value,
+                                       unsigned long long *longest) const {
+  if (longest) *longest = 0;
+  if (!dev_) return Status(2, "copy_encode_padded: no matching result");
+  const CfgBind bind(dev_->cfg);
+  EncodeLane &d = dev_->lane[0];
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (n_sent != d.last_n_sent) return Status(2, "copy_encode_padded: no matching result");
+  if (n_sent == 0) return Status();
+  try {
+    HIP_CHECK(hipSetDevice(device_));
+    if (!d.d_dec_misc) d.d_dec_misc = dalloc<unsigned long long>(2);
+    HIP_CHECK(hipMemsetAsync(d.d_dec_misc + 1, 0, 8, d.st));
+    launch_enc_longest(d.d_out_off, n_sent, (unsigned int *)(d.d_dec_misc + 1), d.st);
+    unsigned long long need = 0;
+    HIP_CHECK(hipMemcpyAsync(&need, d.d_dec_misc + 1, 8, hipMemcpyDeviceToHost, d.st));
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    if (longest) *longest = need;
+    if (need > width)  // nothing is truncated, and nothing was written
+      return Status(1, "width is smaller than the longest row. Current value: width = " + std::to_string(width) + "; longest = " + std::to_string(need) + ";");
+    if (need > 0x7fffffffull) return Status(2, "copy_encode_padded: a row is too long for int32 lengths");
+    if (!d_matrix || !d_lengths) return Status(2, "copy_encode_padded: no output");
+    if (((uintptr_t)d_matrix & 3u) != 0) return Status(2, "copy_encode_padded: the matrix must be 4-byte aligned");
+    launch_enc_pad(d.d_ids, d.d_out_off, n_sent, width, pad_value, (int32_t *)d_matrix, (int32_t *)d_lengths, d.st);
+    HIP_CHECK(hipStreamSynchronize(d.st));
+  } catch (const GpuError &e) {
+    return Status(2, "GPU error: " + e.msg);
+  }
+  return Status();
+}
+
+}  // namespace yttm

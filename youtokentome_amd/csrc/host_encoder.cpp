@@ -57,6 +57,14 @@ struct EncodeLane {
   uint32_t *d_ucounts = nullptr; size_t cap_ucounts = 0;
   unsigned long long last_n_ids = 0, last_n_sent = 0;
   unsigned long long last_distinct_words = 0;  // of the last cached batch (0: the batch went straight through K5)
+  // device decode (host_decode.h): buffers of their own, so that a decode result and an encode result are pending side by side
+  uint32_t *d_dec_len = nullptr; size_t cap_dec_len = 0;
+  unsigned long long *d_dec_off = nullptr; size_t cap_dec_off = 0;
+  uint8_t *d_dec_bytes = nullptr; size_t cap_dec_bytes = 0;
+  uint32_t *d_dec_ign = nullptr; size_t cap_dec_ign = 0;  // ignore bitmap, then the ignored ids outside [0, vocab)
+  unsigned long long *d_dec_misc = nullptr;               // [0] smallest flat index of an invalid id, [1] longest row (k_enc_longest)
+  unsigned long long dec_n_sent = 0, dec_n_bytes = 0;
+  bool dec_valid = false;
 
   template <class T>
   void grow(T *&p, size_t &cap, size_t need) {
@@ -70,7 +78,8 @@ struct EncodeLane {
   ~EncodeLane() {
     for (void *p : {(void *)d_drop, (void *)d_bytes, (void *)d_off, (void *)d_scratch, (void *)d_counts, (void *)d_out_off, (void *)d_scan_tmp,
                     (void *)d_total, (void *)d_ids, (void *)d_work, (void *)d_wc_slot, (void *)d_wc_pos, (void *)d_wc_occ, (void *)d_wc_extra,
-                    (void *)d_wc_misc, (void *)d_wc_blk, (void *)d_wc_blk_off, (void *)d_ustart, (void *)d_uend, (void *)d_uslot, (void *)d_ucounts})
+                    (void *)d_wc_misc, (void *)d_wc_blk, (void *)d_wc_blk_off, (void *)d_ustart, (void *)d_uend, (void *)d_uslot, (void *)d_ucounts,
+                    (void *)d_dec_len, (void *)d_dec_off, (void *)d_dec_bytes, (void *)d_dec_ign, (void *)d_dec_misc})
       if (p) (void)hipFree(p);
     if (st) (void)hipStreamDestroy(st);
   }
@@ -96,6 +105,12 @@ struct EncoderDevice {
   EncodeLane lane[N_LANES];
   std::atomic<unsigned int> next_lane{0};
   std::atomic<unsigned long long> last_distinct_words{0};  // of the most recent batch (cache_words())
+  // piece table of the device decode (host_decode.h), made at the first device decode
+  std::mutex dec_mu;
+  bool dec_ready = false;
+  uint8_t *d_piece_blob = nullptr;
+  uint32_t *d_piece_off = nullptr;
+  uint32_t dec_vocab = 0;
   // a free lane, locked (falls back to waiting for the caller's turn-based choice)
   // (Lane 0 last: the device-resident pair encode_device / fetch_device_result keeps its result there, unlocked, between the two
   // calls -- a host-to-host encode from another thread in between takes another lane while one is free.)
@@ -109,7 +124,7 @@ struct EncoderDevice {
     return l;
   }
   ~EncoderDevice() {
-    for (void *p : {(void *)d_cpmap, (void *)d_rules, (void *)d_rule_z, (void *)d_rule_xy, (void *)d_bloom})
+    for (void *p : {(void *)d_cpmap, (void *)d_rules, (void *)d_rule_z, (void *)d_rule_xy, (void *)d_bloom, (void *)d_piece_blob, (void *)d_piece_off})
       if (p) (void)hipFree(p);
   }
 };
@@ -503,6 +518,10 @@ Status BaseEncoder::fetch_device_result(int32_t *ids, unsigned long long *out_of
   if (n_sent != dev_->lane[0].last_n_sent) return Status(2, "fetch_device_result: no matching result");
   return fetch_lane(dev_->lane[0], device_, ids, out_off, n_sent);
 }
+
+}  // namespace yttm
+#include "host_decode.h"  // device decode and the device-to-device exits of both results (uses the lanes and copy_down above)
+namespace yttm {
 
 // upload -> K5 -> download on one lane; the output arrays come from the caller's allocator once their sizes are known
 template <class AllocIds, class AllocOff>

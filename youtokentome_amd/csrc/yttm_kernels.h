@@ -288,4 +288,34 @@ void launch_wcache_count(const unsigned long long *offsets, unsigned long long n
 void launch_wcache_scatter(const EncModel &m, const unsigned long long *offsets, unsigned long long n_sent, const WordCache &wc, const int32_t *uids, int bos,
                            int eos, int reverse, const unsigned long long *out_off, int32_t *ids_out, hipStream_t st);
 
+// ---- N3: device decode, and the encoder's result as a padded matrix (k_decode.h, compiled with k_encode.hip) ----
+constexpr uint32_t DEC_INVALID = 0x80000000u;  // piece_off[id] with this bit: the host's id_to_subword refuses the id
+struct DecTable {
+  const uint8_t *blob;        // the text of every id back to back: id_to_subword(id, replace_space = true)
+  const uint32_t *piece_off;  // [vocab + 1]
+  uint32_t vocab;
+};
+struct DecIgnore {
+  const uint32_t *bitmap;  // bit per id of [0, vocab)
+  const int32_t *extra;    // ignored ids outside [0, vocab): they cannot sit in the bitmap, yet suppress the range error for themselves
+  uint32_t n_extra;
+  uint32_t any;            // 0: nothing is ignored, neither table is read
+};
+struct DecInput {  // sentence s = ids[offsets[s] .. offsets[s+1]), or (offsets == nullptr) ids[s * stride .. s * stride + min(width, lengths[s]))
+  const int32_t *ids;
+  const unsigned long long *offsets;
+  const int32_t *lengths;  // padded only; nullptr: every row has `width` ids
+  unsigned long long width, stride;  // padded only; 1 <= stride, width <= stride
+  unsigned long long n_sent;
+};
+// n_flat: ids (ragged) or n_sent * stride (padded) -- sizes the groups of sentences.  *bad_min must hold ~0 before the launch.
+void launch_decode_measure(const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, uint32_t *out_len,
+                           unsigned long long *bad_min, hipStream_t st);
+// out: 16-byte aligned
+void launch_decode_write(const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, const unsigned long long *out_off,
+                         uint8_t *out, hipStream_t st);
+void launch_enc_longest(const unsigned long long *out_off, unsigned long long n_sent, unsigned int *longest /* holds 0 before the launch */, hipStream_t st);
+void launch_enc_pad(const int32_t *ids, const unsigned long long *out_off, unsigned long long n_sent, unsigned long long width, int32_t pad_value,
+                    int32_t *matrix /* 4-byte aligned */, int32_t *lengths, hipStream_t st);
+
 }  // namespace yttm

@@ -1,0 +1,143 @@
+"""Device tensors in, device tensors out: `BPE.encode_tensor` / `BPE.decode_tensor` on top of the raw device layer of `bpe._Core`
+(include/yttm_mi355x.h: yttm_encode_device, yttm_encode_copy_*, yttm_decode_device*, yttm_decode_copy_device).  torch is imported at call
+time; the rest of the package does not need it.
+
+The library works on a non-blocking stream of its own and returns after that stream has synchronised.  So the hand-over is: synchronise
+torch's current stream (whatever produced the input tensors is done), call the library, and let it fill output tensors that torch
+allocated -- torch owns all memory it sees."""
+import numpy as np
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _device_of(bpe, device):
+    torch = _torch()
+    own = torch.device("cuda", bpe.bpe_cython.device)
+    if device is not None:
+        want = torch.device(device)
+        if want.type != "cuda" or (want.index is not None and want.index != own.index):
+            raise ValueError("device %s is not the encoder's (%s)" % (want, own))
+    return own
+
+
+def _check_on(t, dev, what):
+    if t.device.type != dev.type or t.device.index != dev.index:
+        raise ValueError("%s is on %s, the encoder on %s" % (what, t.device, dev))
+
+
+def _offsets_u64(torch, offsets, dev, what="offsets"):
+    """int64 / uint64 offsets tensor -> contiguous tensor whose memory the library reads as uint64 (the values are below 2^63)"""
+    if getattr(torch, "uint64", None) is not None and offsets.dtype == torch.uint64:
+        offsets = offsets.view(torch.int64)
+    if offsets.dtype != torch.int64:
+        raise ValueError("%s must be an int64 or uint64 tensor" % what)
+    _check_on(offsets, dev, what)
+    return offsets.contiguous()
+
+
+def encode_tensor(bpe, sentences, bos=False, eos=False, reverse=False, dropout_prob=0, padded=True, width=None, pad_id=None, device=None):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, device)
+    if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
+        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+    if padded and pad_id is None:
+        pad_id = bpe.subword_to_id("<PAD>")
+        if pad_id == -1 or bpe.id_to_subword(pad_id) != "<PAD>":
+            raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
+    if isinstance(sentences, (list, tuple)) and not (len(sentences) == 2 and hasattr(sentences[0], "data_ptr")):
+        from .bpe import _pack
+        blob, offs = _pack(list(sentences))
+        n = len(offs) - 1
+        lens = np.diff(offs.astype(np.int64)) if n else np.zeros(0, np.int64)
+        total, longest_in = int(offs[-1]), int(lens.max()) if n else 0
+        d_bytes = torch.frombuffer(bytearray(blob) if blob else bytearray(1), dtype=torch.uint8).to(dev)
+        d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
+    else:
+        d_bytes, d_off = sentences
+        if d_bytes.dtype != torch.uint8 or d_bytes.dim() != 1 or d_off.dim() != 1 or d_off.numel() < 1:
+            raise ValueError("device input is a pair (uint8 bytes [B], int64 or uint64 offsets [n + 1])")
+        _check_on(d_bytes, dev, "bytes")
+        d_bytes, d_off = d_bytes.contiguous(), _offsets_u64(torch, d_off, dev)
+        n = d_off.numel() - 1
+        if n:
+            total = int(d_off[-1])
+            longest_in = int((d_off[1:] - d_off[:-1]).max())
+            if int(d_off[0]) != 0:
+                raise ValueError("offsets[0] must be 0")
+        else:
+            total = longest_in = 0
+    torch.cuda.current_stream(dev).synchronize()  # the inputs are complete before the library's own stream reads them
+    n_ids, _ = core.encode_device_raw(d_bytes.data_ptr(), d_off.data_ptr(), n, total, longest_in, bos, eos, reverse, dropout_prob)
+    if not padded:
+        ids = torch.empty(n_ids, dtype=torch.int32, device=dev)
+        out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        core.copy_encode_device(ids.data_ptr(), out_off.data_ptr(), n)
+        return ids, out_off
+    longest = core.encode_longest(n) if n else 0
+    if width is None:
+        width = longest
+    elif width < longest:
+        raise ValueError("width = %d is smaller than the longest row (%d ids)" % (width, longest))
+    matrix = torch.empty((n, width), dtype=torch.int32, device=dev)
+    lengths = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        torch.cuda.current_stream(dev).synchronize()
+        core.copy_encode_padded(matrix.data_ptr(), lengths.data_ptr(), n, width, pad_id)
+    return matrix, lengths
+
+
+def decode_tensor(bpe, ids, lengths=None, offsets=None, ignore_ids=None, as_str=True):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    _check_on(ids, dev, "ids")
+    if ids.dtype == torch.int64:
+        ids = ids.to(torch.int32)
+    elif ids.dtype != torch.int32:
+        raise ValueError("ids must be an int32 or int64 tensor")
+    if ids.dim() == 2:
+        if offsets is not None:
+            raise ValueError("offsets go with 1-D ids; a 2-D matrix takes lengths")
+        n, width = ids.shape
+        if n and width and ids.stride(1) != 1:
+            ids = ids.contiguous()
+        stride = ids.stride(0) if n > 1 and width else width  # (rows of a sliced matrix keep their distance: no copy)
+        if stride < width:
+            ids, stride = ids.contiguous(), width
+        d_len = 0
+        if lengths is not None:
+            _check_on(lengths, dev, "lengths")
+            if lengths.dim() != 1 or lengths.numel() != n:
+                raise ValueError("lengths must have one entry per row")
+            lengths = lengths.to(torch.int32).contiguous()
+            d_len = lengths.data_ptr()
+        torch.cuda.current_stream(dev).synchronize()
+        n_bytes, _ = core.decode_device_padded_raw(ids.data_ptr(), n, width, stride, d_len or None, ignore_ids)
+    elif ids.dim() == 1:
+        if offsets is None or lengths is not None:
+            raise ValueError("1-D ids take offsets [n + 1] (and no lengths)")
+        offsets = _offsets_u64(torch, offsets, dev)
+        ids = ids.contiguous()
+        n = offsets.numel() - 1
+        if n < 0:
+            raise ValueError("offsets must have at least one entry")
+        if n and (int(offsets[-1]) > ids.numel() or int(offsets[0]) < 0 or bool((offsets[1:] < offsets[:-1]).any())):
+            raise ValueError("offsets must be non-decreasing and end inside ids")
+        torch.cuda.current_stream(dev).synchronize()
+        n_bytes, _ = core.decode_device_raw(ids.data_ptr(), offsets.data_ptr(), n, ids.numel(), ignore_ids)
+    else:
+        raise ValueError("ids must be 1-D (with offsets) or 2-D (padded)")
+    if as_str:
+        raw, off = core.fetch_decode(n, n_bytes)
+        raw, o = raw.tobytes(), off.tolist()
+        return [raw[o[i]:o[i + 1]].decode() for i in range(n)]
+    text = torch.empty(n_bytes, dtype=torch.uint8, device=dev)
+    out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()
+    core.copy_decode_device(text.data_ptr(), out_off.data_ptr(), n)
+    return text, out_off
