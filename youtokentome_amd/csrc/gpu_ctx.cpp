@@ -19,11 +19,9 @@ GpuCtx::GpuCtx(int device) : device_(device) {
   tl_stream = strm();
   tl_device = device_;
   d_counters_ = dmalloc<unsigned long long>(64);
-  d_stats_ = dmalloc<unsigned long long>(STATS_WORDS);  // [0..3] K4 counters, [8..23] per-phase cycles of a YTTM_K4_PROF build, [32..) per-workgroup rows
+  d_stats_ = dmalloc<unsigned long long>(STATS_WORDS);  // (yttm_kernels.h: StatWord)
   HIP_CHECK(hipMemsetAsync(d_stats_, 0, STATS_WORDS * sizeof(unsigned long long), strm()));  // (stream-ordered like everything that uses them)
-  // one block for everything the host reads back per round, so that it is ONE device-to-host copy:
-  // [0] n_cand, [4] n_keys | [64..) count histogram | [8192..) candidates
-  d_round_ = dmalloc<unsigned char>(8192 + (size_t)CAND_CAP * sizeof(CandRec));
+  d_round_ = dmalloc<RoundBlock>(1);  // one block for everything the host reads back per round, so that it is ONE device-to-host copy
   hot_cap_ = std::min((unsigned int)C.hot_cap.u, HOT_CAP);
   hot_target_ = (unsigned int)C.hot_target.u;  // measured at 1 GB: 4096..16384 equal on the abcd corpus, 8192 best on Zipf text (4279 rounds)
   hot_min_ = (unsigned int)C.hot_min.u;
@@ -48,29 +46,24 @@ GpuCtx::GpuCtx(int device) : device_(device) {
   // in word mode, the 1 GB CJK-shaped corpus (337 M tokens) 21 % faster, random 'abcd ' (94 M tokens at the switch) 10 % faster
   word_min_tokens_ = C.word_min_tokens.u;
   no_batch_args_ = C.no_batch_args.set;
-  launch_env_refresh();
   trace_rounds_ = C.trace_rounds.c_str();  // (points into cfg_, which this context keeps)
   dbg_cand_ = C.dbg_cand.c_str();
   d_hot_slots_ = dmalloc<uint32_t>(HOT_CAP);
-  d_hot_n_ = dmalloc<unsigned int>(4);  // [0] list length, [1] k_hot_scan's finished-workgroup ticket, [2..3] overflow verdict (u64)
-  HIP_CHECK(hipMemsetAsync(d_hot_n_, 0, 16, strm()));
+  d_hot_ctl_ = dmalloc<ListCtl>(1);
+  HIP_CHECK(hipMemsetAsync(d_hot_ctl_, 0, sizeof(ListCtl), strm()));
   top_cap_ = std::max(16u, std::min((unsigned int)C.top_cap.u, TOP_CAP));
   top_target_ = (unsigned int)C.top_target.u;  // about four times what the host looks at per round
   top_min_ = (unsigned int)C.top_min.u;
   d_top_slots_ = dmalloc<uint32_t>(TOP_CAP);
-  d_top_n_ = dmalloc<unsigned int>(4);
-  HIP_CHECK(hipMemsetAsync(d_top_n_, 0, 16, strm()));
-  HIP_CHECK(hipMemsetAsync(d_round_, 0, 8192, strm()));  // k_hot_scan leaves its counters zeroed for the next call
-  d_cand_n_ = (unsigned int *)d_round_;
-  d_cand_hist_ = (unsigned long long *)(d_round_ + 64);
-  d_cand_ = (CandRec *)(d_round_ + 8192);
+  d_top_ctl_ = dmalloc<ListCtl>(1);
+  HIP_CHECK(hipMemsetAsync(d_top_ctl_, 0, sizeof(ListCtl), strm()));
+  HIP_CHECK(hipMemsetAsync(d_round_, 0, offsetof(RoundBlock, cand), strm()));  // k_hot_scan leaves its counters zeroed for the next call
   cand_cap_ = CAND_CAP;
   d_rules_ = dmalloc<RuleSlot>(RULES_CAP);
   rules_cap_ = RULES_CAP;
-  h_pin_ = pool_take_pin();  // pinned staging: one buffer is kept across contexts (hipHostMalloc of 17 MB costs milliseconds)
-  if (!h_pin_) HIP_CHECK(hipHostMalloc(&h_pin_, PIN_BYTES, hipHostMallocDefault));
-  h_pin_bytes_ = PIN_BYTES;
-  memset(h_pin_, 0, 8192);  // mailbox header (k_hot_scan publishes its round id at byte 32)
+  h_pin_ = (PinBlock *)pool_take_pin();  // pinned staging: one buffer is kept across contexts (hipHostMalloc of 17 MB costs milliseconds)
+  if (!h_pin_) HIP_CHECK(hipHostMalloc((void **)&h_pin_, PIN_BYTES, hipHostMallocDefault));
+  memset(&h_pin_->mailbox, 0, offsetof(RoundMailbox, cand));  // (round_id: no round is published)
 }
 
 GpuCtx::~GpuCtx() {
@@ -82,8 +75,8 @@ GpuCtx::~GpuCtx() {
   for (hipEvent_t e : all_events_) (void)hipEventDestroy(e);
   DFREE(d_text_owned_); DFREE(d_hist_); DFREE(d_chunk_segs_); DFREE(d_counters_); DFREE(d_cpmap_); DFREE(d_rules_);
   free_class(cls_[0]); free_class(cls_[1]); free_class(cls_[2]);
-  DFREE(d_stats_); DFREE(d_round_); DFREE(d_recv_); DFREE(d_hot_slots_); DFREE(d_hot_n_); DFREE(d_top_slots_); DFREE(d_top_n_);
-  DFREE(d_xstat_); DFREE(d_bloom_); DFREE(d_maybe_); DFREE(d_maybe_n_);
+  DFREE(d_stats_); DFREE(d_round_); DFREE(d_recv_); DFREE(d_hot_slots_); DFREE(d_hot_ctl_); DFREE(d_top_slots_); DFREE(d_top_ctl_);
+  DFREE(d_xstat_); DFREE(d_bloom_); DFREE(d_maybe_); DFREE(d_maybe_ctl_);
   DFREE(db_.keys); DFREE(db_.touched); DFREE(d_send2_[0]); DFREE(d_send2_[1]);
   free_table(pt_);
   free_index();
@@ -151,12 +144,12 @@ void GpuCtx::resolve_timers() {
     if (pt_cap_) launch_fold_stats(d_stats_, pt_.n_keys, strm());
     sync();
     if (hipMemcpy(st, d_stats_, sizeof st, hipMemcpyDeviceToHost) == hipSuccess) {
-      merge_sites = st[0];
-      kt.bytes[KT_MERGE] = 4 * st[2] + 8 * st[3];
-      touched_tiles = st[1];
-      touched_tile_tokens = st[3];
-      touched_words = st[4];
-      touched_word_tokens = st[5];
+      merge_sites = st[STAT_SITES];
+      kt.bytes[KT_MERGE] = 4 * st[STAT_TOKENS] + 8 * st[STAT_TOUCHED_TOKENS];
+      touched_tiles = st[STAT_TOUCHED];
+      touched_tile_tokens = st[STAT_TOUCHED_TOKENS];
+      touched_words = st[STAT_INSTR_WORDS];
+      touched_word_tokens = st[STAT_INSTR_TOKENS];
     }
   }
   FILE *trace = cfg_->trace.set ? fopen(cfg_->trace.raw.c_str(), "w") : nullptr;  // per-launch times for tuning
@@ -179,6 +172,36 @@ void GpuCtx::resolve_timers() {
 }
 
 // ------------------------------------------------------------------------------------------------- K4
+// One merge round's values, carried between the steps of merge_apply.
+struct GpuCtx::Round {
+  const uint32_t *xyz;
+  uint32_t k;
+  const unsigned long long *rule_counts;
+  uint32_t vmax = 0, z_base = 0;
+  unsigned int cap = 64;                       // slots of the batch's rule hash
+  uint32_t self_x = 0xffffffffu, self_z = 0;   // at most one x == y rule, passed by value
+  bool by_args = false;                        // the batch travels in the kernel arguments (ba.k != 0)
+  BatchArgs ba{};
+  ScanArgs sa{};                               // the candidate scan that rides in the round's last kernel (sa.on == 0: none)
+  ScanArgs xa{};                               // multi-GPU: what the word-mode launches get instead
+  bool dev_timing = false, marked = false;
+  int last_cls = 0;
+  PairTable kpt{};
+  // at most this many distinct pairs can the round touch on a rank: per rule at most five updates per site (sites <= the pair's global count) and
+  // at most four pairs per token type ((a,x), (a,z), (y,b), (z,b)) plus the self pairs.  The same number on every rank (it is computed from the
+  // batch and the global counts).
+  unsigned long long touch_bound() const {
+    unsigned long long b = 0;
+    for (uint32_t j = 0; j < k; j++) b += std::min<unsigned long long>(rule_counts ? 5 * rule_counts[j] : ~0ull >> 8, 4ull * (vmax + 1) + 4);
+    return b;
+  }
+  BatchArgs first_ba() {  // the BatchArgs of the round's next launch: the first one carries the mark
+    BatchArgs b = ba;
+    if (dev_timing && !marked) { b.mark = 1u; marked = true; }
+    return b;
+  }
+};
+
 void GpuCtx::merge_apply(const uint32_t *xyz, uint32_t k, const unsigned long long *rule_counts, const unsigned long long *next_tau_cnt,
                          uint32_t next_tau_mx, uint32_t next_want) {
   HIP_CHECK(hipSetDevice(device_));
@@ -187,29 +210,45 @@ void GpuCtx::merge_apply(const uint32_t *xyz, uint32_t k, const unsigned long lo
   if (!k) return;
   if (!n_tiles && !multi()) return;  // a rank without words still takes part in the exchange
   if (k > RULES_CAP / 2) throw GpuError{"merge_apply: batch too large"};
+  Round r{xyz, k, rule_counts};
+  round_capacity(r);
+  round_word_mode(r);
+  round_batch(r);
+  round_scan(r, next_tau_cnt, next_tau_mx, next_want);
+  if (multi()) round_block_size(r);
+  round_launch(r);
+  merge_rounds++;
+  round_trace(r);
+  round_finish(r);
+  // single GPU: no sync here -- the candidate filter that always follows reads n_keys back together with its results
+  // (its sync also makes the pinned rule staging reusable for the next round)
+  // every occurrence of the batch's pairs has been merged (on every rank): their counts are exactly zero.  The candidate
+  // filter that follows zeroes them while it reads the hot list; any other reader goes through flush_pending_zero().
+}
+
+// the batch's shape, and room for what it can add: the pair table and (multi-GPU) the delta table
+void GpuCtx::round_capacity(Round &r) {
   // new pairs this round: every site adds <= 2 neighbours (+ the z,z run pair); distinct new keys per rule are also
   // bounded by the number of live token types on either side
-  uint32_t vmax = 0, z_base = xyz[2];
-  for (uint32_t j = 0; j < k; j++) {
-    vmax = std::max(vmax, xyz[3 * j + 2]);
-    if (xyz[3 * j + 2] != z_base + j) throw GpuError{"merge_apply: the new ids of a batch must be consecutive"};
+  r.z_base = r.xyz[2];
+  for (uint32_t j = 0; j < r.k; j++) {
+    r.vmax = std::max(r.vmax, r.xyz[3 * j + 2]);
+    if (r.xyz[3 * j + 2] != r.z_base + j) throw GpuError{"merge_apply: the new ids of a batch must be consecutive"};
   }
-  if (vmax >= (1u << 29)) throw GpuError{"merge_apply: token ids must be below 2^29"};
+  if (r.vmax >= (1u << 29)) throw GpuError{"merge_apply: token ids must be below 2^29"};
   unsigned long long bound_new = 0;
-  for (uint32_t j = 0; j < k; j++) {
-    unsigned long long by_tokens = 2ull * (vmax + 1) + 1;
-    unsigned long long by_count = rule_counts ? 3 * rule_counts[j] : by_tokens;
+  for (uint32_t j = 0; j < r.k; j++) {
+    unsigned long long by_tokens = 2ull * (r.vmax + 1) + 1;
+    unsigned long long by_count = r.rule_counts ? 3 * r.rule_counts[j] : by_tokens;
     bound_new += std::min(by_tokens, by_count);
   }
   // (the key count the scans report is one round old -- they fold the statistics after publishing: the previous round's bound covers it)
   ensure_table_capacity(n_keys_host + bound_prev_ + bound_new);
   bound_prev_ = bound_new;
   if (multi() && !delta_cap_forced_) {
-    // distinct pairs this rank's round can touch: per rule at most five updates per site (sites <= the pair's global count) and at most
-    // four pairs per token type ((a,x), (a,z), (y,b), (z,b)) plus the self pairs.  The same number on every rank (it is computed from the
-    // batch and the global counts), so every rank regrows its table in the same round -- an overflow is a bug, not a workload.
-    unsigned long long dt_bound = 0;
-    for (uint32_t j = 0; j < k; j++) dt_bound += std::min<unsigned long long>(rule_counts ? 5 * rule_counts[j] : ~0ull >> 8, 4ull * (vmax + 1) + 4);
+    // distinct pairs this rank's round can touch (Round::touch_bound): every rank regrows its table in the same round -- an overflow is a
+    // bug, not a workload.
+    const unsigned long long dt_bound = r.touch_bound();
     if (dt_bound > send_cap_) {
       unsigned long long cap = db_.mask + 1;
       while (cap / 2 < dt_bound) cap <<= 1;
@@ -218,216 +257,236 @@ void GpuCtx::merge_apply(const uint32_t *xyz, uint32_t k, const unsigned long lo
       delta_regrows++;
     }
   }
+}
 
-  // Word mode: on when the last round's merge sites are few against the tokens a pass over the tiles streams, and a pass is expensive
-  // (and then for good).  Single GPU: this context's numbers.  Multi-GPU: the ranks' numbers summed (block headers -> mailbox), per rank on
-  // average -- the same verdict on every rank in the same round; a rank without class-A tiles follows the decision without switching.
+// Word mode pays when the last round's merge sites are few against the tokens a pass over the tiles streams, and a pass is expensive
+// (numbers of one context, or summed over `ranks` of them).
+bool GpuCtx::word_mode_pays(unsigned long long tiles_a, unsigned long long sites, unsigned long long tokens, unsigned long long ranks) const {
+  return tiles_a >= (unsigned long long)word_min_tiles_ * ranks && tiles_a && sites != ~0ull && tokens && tokens >= word_min_tokens_ * ranks &&
+         (word_div_ == 0 || sites * (unsigned long long)word_div_ < tokens);
+}
+
+void GpuCtx::round_word_mode(const Round &r) {
+  // Word mode: on when word_mode_pays (and then for good).  Single GPU: this context's numbers.  Multi-GPU: the ranks' numbers summed
+  // (block headers -> mailbox), per rank on average -- the same verdict on every rank in the same round; a rank without class-A tiles
+  // follows the decision without switching.
   if (!word_global_ && words_enabled_ && idx_enabled_ && !instrument && hot_state_ == HOT_ACTIVE) {
-    bool go;
-    if (multi()) {
-      const unsigned long long W = (unsigned long long)comm_->world;
-      go = g_tiles_a_ >= (unsigned long long)word_min_tiles_ * W && g_tiles_a_ && g_sites_last_ != ~0ull && g_tokens_last_ && g_tokens_last_ >= word_min_tokens_ * W &&
-           (word_div_ == 0 || g_sites_last_ * (unsigned long long)word_div_ < g_tokens_last_);
-    } else {
-      go = cls_[0].n_tiles >= word_min_tiles_ && cls_[0].n_tiles && sites_last_ != ~0ull && live_tokens_last_ && live_tokens_last_ >= word_min_tokens_ &&
-           (word_div_ == 0 || sites_last_ * (unsigned long long)word_div_ < live_tokens_last_);
-    }
+    const bool go = multi() ? word_mode_pays(g_tiles_a_, g_sites_last_, g_tokens_last_, (unsigned long long)comm_->world)
+                            : word_mode_pays(cls_[0].n_tiles, sites_last_, live_tokens_last_, 1);
     if (go) {
       word_global_ = true;
-      if (cls_[0].n_tiles) enter_word_mode(z_base);
+      if (cls_[0].n_tiles) enter_word_mode(r.z_base);
       else word_switch_round = merge_rounds;
     }
   }
   if (word_mode_) {
     if (*(volatile unsigned int *)tl_.broken) idx_pending_ = true;  // (the last round is over: its mailbox has been read)
-    if (idx_pending_) build_index(z_base);
+    if (idx_pending_) build_index(r.z_base);
   }
+}
 
-  // rule hash (x != y rules) + at most one x == y rule passed by value
-  unsigned int cap = 64;
-  while (cap < 2 * k) cap <<= 1;
-  char *pin = (char *)h_pin_ + (1u << 16) + (size_t)CAND_CAP * sizeof(CandRec);  // after the read-back area of candidates()
-  RuleSlot *h_rules = (RuleSlot *)pin;
-  uint32_t self_x = 0xffffffffu, self_z = 0;
+void build_rule_hash(RuleSlot *tab, unsigned int cap, const uint32_t *rules, unsigned int stride, uint32_t k) {
+  for (unsigned int i = 0; i < cap; i++) { tab[i].key = PT_EMPTY; tab[i].z = 0; tab[i].pad = 0; }
   for (uint32_t j = 0; j < k; j++) {
-    const uint32_t x = xyz[3 * j], y = xyz[3 * j + 1], z = xyz[3 * j + 2];
+    const uint32_t x = rules[stride * j], y = rules[stride * j + 1];
+    if (x == y) continue;
+    const unsigned long long key = pair_key(x, y);
+    unsigned int h = pair_hash32(key) & (cap - 1);
+    while (tab[h].key != PT_EMPTY) h = (h + 1) & (cap - 1);
+    tab[h].key = key;
+    tab[h].z = stride > 2 ? rules[stride * j + 2] : 0;
+  }
+}
+
+// the batch: rule hash (x != y rules) + at most one x == y rule passed by value
+void GpuCtx::round_batch(Round &r) {
+  while (r.cap < 2 * r.k) r.cap <<= 1;
+  for (uint32_t j = 0; j < r.k; j++) {
+    const uint32_t x = r.xyz[3 * j], y = r.xyz[3 * j + 1], z = r.xyz[3 * j + 2];
     if (x >= id_cap_ || y >= id_cap_ || z >= id_cap_) throw GpuError{"merge_apply: token id out of range"};
     if (x == y) {
-      if (self_x != 0xffffffffu) throw GpuError{"merge_apply: more than one x==y rule in a batch"};
-      self_x = x;
-      self_z = z;
+      if (r.self_x != 0xffffffffu) throw GpuError{"merge_apply: more than one x==y rule in a batch"};
+      r.self_x = x;
+      r.self_z = z;
     }
   }
   // A small batch goes to the kernels as an argument and nothing is uploaded (yttm_kernels.h: BatchArgs); a larger one (or any, with
   // class-C tiles: k_giant reads the rule hash from HBM) travels through k_round_begin.
-  const bool by_args = k <= (uint32_t)BATCH_ARGS_MAX && !cls_[2].n_tiles && !no_batch_args_;
-  if (!by_args) {  // (the common small batch needs none of this: the host's share of a round is on the critical path)
-    for (unsigned int i = 0; i < cap; i++) { h_rules[i].key = PT_EMPTY; h_rules[i].z = 0; h_rules[i].pad = 0; }
-    for (uint32_t j = 0; j < k; j++) {
-      const uint32_t x = xyz[3 * j], y = xyz[3 * j + 1], z = xyz[3 * j + 2];
-      if (x == y) continue;
-      const unsigned long long key = pair_key(x, y);
-      unsigned int h = pair_hash32(key) & (cap - 1);
-      while (h_rules[h].key != PT_EMPTY) h = (h + 1) & (cap - 1);
-      h_rules[h].key = key;
-      h_rules[h].z = z;
-    }
-  }
-  BatchArgs ba{};
-  ba.instr = instrument ? 1u : 0u;
+  r.by_args = r.k <= (uint32_t)BATCH_ARGS_MAX && !cls_[2].n_tiles && !no_batch_args_;
+  // (the common small batch needs no rule hash: the host's share of a round is on the critical path)
+  if (!r.by_args) build_rule_hash(h_pin_->rules, r.cap, r.xyz, 3, r.k);
+  r.ba.instr = instrument ? 1u : 0u;
   const uint32_t max_in = max_id_;  // largest id a tile can hold BEFORE this round (the ids the site search looks up)
-  max_id_ = std::max(max_id_, vmax);
-  if (by_args) {
-    ba.k = k;
-    ba.direct_v = direct_enabled_ && max_in + 1 <= DIRECT_MAX_V ? max_in + 1 : 0u;  // (the first rounds of a small alphabet: k_tiles<.., DIRECT>)
-    for (uint32_t j = 0; j < k; j++) { ba.xy[2 * j] = xyz[3 * j]; ba.xy[2 * j + 1] = xyz[3 * j + 1]; }
+  max_id_ = std::max(max_id_, r.vmax);
+  if (r.by_args) {
+    r.ba.k = r.k;
+    r.ba.direct_v = direct_enabled_ && max_in + 1 <= DIRECT_MAX_V ? max_in + 1 : 0u;  // (the first rounds of a small alphabet: k_tiles<.., DIRECT>)
+    for (uint32_t j = 0; j < r.k; j++) { r.ba.xy[2 * j] = r.xyz[3 * j]; r.ba.xy[2 * j + 1] = r.xyz[3 * j + 1]; }
   }
-  // One launch per round: the candidate scan rides in the tail of the round's last kernel -- single GPU: the apply kernel of class A (class
-  // B goes first: the one-wave workgroups of class B took longer over the tail than the launch it saved; class-C tiles -- words of more
-  // than 2048 tokens -- keep the separate scan); multi-GPU: the fold kernel behind the all-gather (exchange_round), whatever the classes.
-  ScanArgs sa{};
+}
+
+// One launch per round: the candidate scan rides in the tail of the round's last kernel -- single GPU: the apply kernel of class A (class
+// B goes first: the one-wave workgroups of class B took longer over the tail than the launch it saved; class-C tiles -- words of more
+// than 2048 tokens -- keep the separate scan); multi-GPU: the fold kernel behind the all-gather (exchange_round), whatever the classes.
+void GpuCtx::round_scan(Round &r, const unsigned long long *next_tau_cnt, uint32_t next_tau_mx, uint32_t next_want) {
+  ScanArgs &sa = r.sa;
   fused_pending_ = false;
-  const int last_cls = cls_[0].n_tiles ? 0 : 1;
+  r.last_cls = cls_[0].n_tiles ? 0 : 1;
   if (next_tau_cnt && fuse_enabled_ && hot_state_ == HOT_ACTIVE && top_state_ == TOP_ACTIVE && !instrument &&
       (multi() || ((cls_[0].n_tiles || cls_[1].n_tiles) && !cls_[2].n_tiles))) {
-    sa.on = 1u;
-    sa.tau_cnt = *next_tau_cnt;
-    sa.tau_mx = next_tau_mx;
+    sa = scan_args(*next_tau_cnt, next_tau_mx, ++mail_round_);
     if (sa.tau_cnt < pt_.top_tau) {  // the list is complete only from top_tau up (as in candidates())
       sa.tau_cnt = pt_.top_tau;
       sa.tau_mx = 0xffffffffu;
     }
-    sa.out = d_cand_;
-    sa.cap = cand_cap_;
-    sa.fast = 4096;
     sa.want = next_want;  // (the scan may raise the threshold to about this many candidates: scan_top)
-    sa.done_ctr = d_hot_n_ + 1;
-    sa.mailbox = (unsigned char *)h_pin_;
-    sa.round_id = ++mail_round_;
+    sa.done_ctr = &d_hot_ctl_->ticket;
     fused_pending_ = true;
     fused_tau_ = *next_tau_cnt;
     fused_mx_ = next_tau_mx;
     fused_round_ = sa.round_id;
   }
-  if (multi()) {
-    // this round's blocks: sized for what the busiest rank will send, predicted from the batch -- its summed pair counts are its merge sites
-    // over all ranks -- and the records per site of the last two rounds, with a margin of three (a block that is too small costs a second
-    // exchange and a scan of its own, ~60 us; one that is too large costs bytes on the links); never more than the round can touch at all
-    // (dt_bound above: the same formula).  Every input is the same on every rank.
-    unsigned long long sites = 0, bound = 0;
-    for (uint32_t j = 0; j < k; j++) {
-      sites += rule_counts ? rule_counts[j] : 0;
-      bound += std::min<unsigned long long>(rule_counts ? 5 * rule_counts[j] : ~0ull >> 8, 4ull * (vmax + 1) + 4);
-    }
-    xch_sites_ = sites;
-    const double margin = xchg_margin_;  // (YTTM_XCHG_MARGIN; tests: a margin below one forces the repeat path)
-    const double pred = rule_counts ? std::max(xrate_[0], xrate_[1]) * (double)sites * margin : (double)bound;
-    unsigned long long need = (unsigned long long)std::min((double)std::min<unsigned long long>(bound, send_cap_), pred) + XHDR;
-    unsigned long long b2 = blk_min_;
-    while (b2 < need) b2 <<= 1;
-    blk_ = b2;
-  }
   // Multi-GPU: what the word-mode launches get instead of the scan (ScanArgs::on == 2): the round's last workgroup only leaves the
   // worklist counters at zero; a one-launch round has not even that to do (launch_words_apply: on = 3).  (Packing the delta table in this
   // tail as well was measured: ONE workgroup walking ten thousand claimed slots across XCDs took 45 us -- k_dt_pack's hundred take 6.)
-  ScanArgs xa{};
   if (multi()) {
-    xa.on = 2u;
-    xa.done_ctr = d_hot_n_ + 1;
+    r.xa.on = 2u;
+    r.xa.done_ctr = &d_hot_ctl_->ticket;
   }
   // A fused round is timed by the device itself (its first launch notes the time, the tail reports the difference in the mailbox):
   // no hipEventRecord on the round's critical path (two per round were 4 us of host time: 8 % of a Zipf step).  YTTM_PROFILE_EVENTS=1
   // keeps the events (cross-check).
-  const bool dev_timing = profile && sa.on && !profile_events_;
-  bool marked = false;
-  auto first_ba = [&]() {  // the BatchArgs of the round's next launch: the first one carries the mark
-    BatchArgs b = ba;
-    if (dev_timing && !marked) { b.mark = 1u; marked = true; }
-    return b;
-  };
-  sa.timed = dev_timing ? 1u : 0u;
-  dev_timing_pending_ = dev_timing;
-  if (!dev_timing) t_begin(KT_MERGE);
-  if (!by_args) {
-    uint32_t *h_bloom = (uint32_t *)(pin + (size_t)RULES_CAP * sizeof(RuleSlot) + 8 * (size_t)RULES_CAP * sizeof(uint32_t));
-    pm_bloom_host(h_bloom, xyz, k);  // the batch's pair filter for the apply kernels (built here: a few hundred hashes)
+  r.dev_timing = profile && sa.on && !profile_events_;
+  sa.timed = r.dev_timing ? 1u : 0u;
+  dev_timing_pending_ = r.dev_timing;
+}
+
+// multi-GPU, this round's blocks: sized for what the busiest rank will send, predicted from the batch -- its summed pair counts are its merge sites
+// over all ranks -- and the records per site of the last two rounds, with a margin of three (a block that is too small costs a second
+// exchange and a scan of its own, ~60 us; one that is too large costs bytes on the links); never more than the round can touch at all
+// (Round::touch_bound).  Every input is the same on every rank.
+void GpuCtx::round_block_size(const Round &r) {
+  unsigned long long sites = 0;
+  for (uint32_t j = 0; j < r.k; j++) sites += r.rule_counts ? r.rule_counts[j] : 0;
+  const unsigned long long bound = r.touch_bound();
+  xch_sites_ = sites;
+  const double margin = xchg_margin_;  // (YTTM_XCHG_MARGIN; tests: a margin below one forces the repeat path)
+  const double pred = r.rule_counts ? std::max(xrate_[0], xrate_[1]) * (double)sites * margin : (double)bound;
+  unsigned long long need = (unsigned long long)std::min((double)std::min<unsigned long long>(bound, send_cap_), pred) + XHDR;
+  unsigned long long b2 = blk_min_;
+  while (b2 < need) b2 <<= 1;
+  blk_ = b2;
+}
+
+// the tail of class ci's launch: the scan (single GPU) or the exchange tail (multi-GPU) in the round's last tile-class launch, nothing elsewhere
+const ScanArgs *GpuCtx::tail_of(const Round &r, int ci) const {
+  if (ci != r.last_cls) return nullptr;
+  if (multi()) return ci == 0 && word_mode_ ? &r.xa : nullptr;  // (the tile kernels have nothing to do in a tail)
+  return r.sa.on ? &r.sa : nullptr;
+}
+
+static int hook_or_auto(const Hook &h) { return h.set && !h.raw.empty() ? (int)h.i : -1; }  // (a test's grid hook; -1: the launcher's own choice)
+
+void GpuCtx::round_launch(Round &r) {
+  if (!r.dev_timing) t_begin(KT_MERGE);
+  if (!r.by_args) {
+    pm_bloom_host(h_pin_->bloom, r.xyz, r.k);  // the batch's pair filter for the apply kernels (built here: a few hundred hashes)
     if (!d_bloom_) d_bloom_ = dmalloc<uint32_t>(PM_BLOOM_WORDS_H);
-    launch_round_begin(h_rules, cap, d_rules_, cls_[0].n_tiles ? cls_[0].d_work_n : nullptr, cls_[1].n_tiles ? cls_[1].d_work_n : nullptr, h_bloom, d_bloom_, strm());
+    launch_round_begin(h_pin_->rules, r.cap, d_rules_, cls_[0].n_tiles ? cls_[0].d_work_n : nullptr, cls_[1].n_tiles ? cls_[1].d_work_n : nullptr, h_pin_->bloom, d_bloom_, strm());
   }
-  const PairTable kpt = multi() ? pt_nolist() : pt_;  // (multi-GPU: the lists are filled behind the exchange, by the final counts -- k_fold_list)
-  // the tail of class ci's launch: the scan (single GPU) or the exchange tail (multi-GPU) in the round's last tile-class launch, nothing elsewhere
-  auto tail_of = [&](int ci) -> const ScanArgs * {
-    if (ci != last_cls) return nullptr;
-    if (multi()) return ci == 0 && word_mode_ ? &xa : nullptr;  // (the tile kernels have nothing to do in a tail)
-    return sa.on ? &sa : nullptr;
-  };
+  r.kpt = multi() ? pt_nolist() : pt_;  // (multi-GPU: the lists are filled behind the exchange, by the final counts -- k_fold_list)
   // Class B, then class A (tiles, or word mode's k_words), on the context's one stream: stream order is the only synchronisation between
   // the round's launches, and the last of them carries the tail (tail_of).
   for (int ci = 1; ci >= 0; ci--) {
     if (!cls_[ci].n_tiles) continue;
     if (ci == 0 && word_mode_) {
-      // the batch's rules -> worklist of words (k_wgather; it also allots the new tokens' instance lists), then the words (k_words)
-      WordClass &c = cls_[0];
-      const uint32_t *d_xyz = nullptr;
-      if (!by_args) {
-        uint32_t *h_xyz = (uint32_t *)(pin + (size_t)RULES_CAP * sizeof(RuleSlot) + 8 * (size_t)RULES_CAP * sizeof(uint32_t) + 16384);
-        memcpy(h_xyz, xyz, (size_t)k * 12);
-        HIP_CHECK(hipMemcpyAsync(d_xyz_, h_xyz, (size_t)k * 12, hipMemcpyHostToDevice, strm()));
-        d_xyz = d_xyz_;
-      }
-      if (k > WGATHER_MAXK) throw GpuError{"merge_apply: batch too large for the word-mode gather"};
-      WGatherArgs ga{};  // (the worklist's length is at zero: enter_word_mode, then every round's k_delta_apply)
-      ga.ix = idx_;
-      ga.ix_valid = idx_valid_ ? 1u : 0u;
-      ga.z_static = idx_valid_ ? idx_zbuild_ : 0xffffffffu;  // (no index: every rule is "not found", the round takes every word)
-      ga.tl = tl_;
-      ga.stamp = d_stamp_;
-      ga.round_id = (uint32_t)(merge_rounds + 1);
-      ga.worklist = d_wworklist_;
-      ga.wl_seg = c.n_unique + 64;
-      ga.work_n = c.d_work_n;
-      ga.gm = d_gm_;
-      ga.done_ctr = d_gm_ + WGATHER_MAXK;
-      ga.xyz = d_xyz;
-      ga.k = k;
-      ga.z_base = z_base;
-      if (by_args)
-        for (uint32_t j = 0; j < k; j++) ga.cnt[j] = rule_counts ? (uint32_t)std::min<unsigned long long>(rule_counts[j], 0xffffffffull) : 0xffffffffu;
-      if (!d_stamp_) {  // (the index could not be built yet: no stamps either -- the gather must not claim words)
-        stamp_cap_ = (unsigned int)(c.n_unique + c.n_unique / 8 + 64);
-        d_stamp_ = dmalloc<uint32_t>(stamp_cap_);
-        HIP_CHECK(hipMemsetAsync(d_stamp_, 0, (size_t)stamp_cap_ * 4, strm()));
-        ga.stamp = d_stamp_;
-      }
-      // live tokens per class-A word, about: what the class held when it left the tiles, less a token per merge site since (a round or two behind)
-      if (sites_last_ != ~0ull && word_sites_seen_ != sites_cum_) {
-        word_live_tokens_ -= std::min(word_live_tokens_, sites_cum_ - std::min(sites_cum_, word_sites_seen_));
-        word_sites_seen_ = sites_cum_;
-      }
-      const unsigned int avg_word_tokens = (unsigned int)std::min<unsigned long long>(std::max<unsigned long long>(1, word_live_tokens_ / std::max<unsigned long long>(1, c.n_unique)), 1u << 16);
-      const unsigned int work_hint = sites_last_ != ~0ull && idx_valid_ ? (unsigned int)std::min<unsigned long long>(2 * sites_last_ + word_hint_floor_, 1ull << 30) : 0u;
-      ga.stats = d_stats_;
-      const BatchArgs gba = first_ba();
-      const WordSet wset{c.d_tok, d_wmeta_, c.d_wcnt, (uint32_t)c.n_unique};
-      if (launch_words_apply(wset, kpt, db_, d_rules_, cap - 1, d_bloom_, self_x, self_z, z_base, k, d_wworklist_, c.n_unique + 64, c.d_work_n, d_stats_, tl_, d_drec_, drec_cap_, d_drec_n_, d_irec_, &gba,
-                             tail_of(0), work_hint, words_inline_max_, &ga, words_fuse_max_, strm(), avg_word_tokens))
-        word_fused_rounds++;
-      word_rounds++;
-      if (!idx_valid_) word_all_rounds++;
+      round_launch_words(r);
       continue;
     }
-    const BatchArgs tba = first_ba();
-    launch_merge_apply(ci, cls_[ci].ts, kpt, db_, d_rules_, cap - 1, self_x, self_z, z_base, d_stats_, &tba, tail_of(ci), d_bloom_, strm());
+    const BatchArgs tba = r.first_ba();
+    launch_merge_apply(ci, cls_[ci].ts, r.kpt, db_, d_rules_, r.cap - 1, r.self_x, r.self_z, r.z_base, d_stats_, &tba, tail_of(r, ci), d_bloom_,
+                       (unsigned int)cfg_->apply_grid.i, strm());
     if (ci == 1 && word_mode_) classb_word_rounds++;
   }
-  launch_giant(true, cls_[2].ts, cls_[2].slot, kpt, db_, d_rules_, cap - 1, self_x, self_z, cls_[2].d_scratch, d_stats_, strm());
-  if (dev_timing) kt.launches[KT_MERGE]++;
-  else t_end(KT_MERGE, 0, /*chain=*/!sa.on);  // (a fused round is followed by the host's turn, not by another kernel: its end event must not start the next interval)
-  merge_rounds++;
+  launch_giant(true, cls_[2].ts, cls_[2].slot, r.kpt, db_, d_rules_, r.cap - 1, r.self_x, r.self_z, cls_[2].d_scratch, d_stats_, strm());
+  if (r.dev_timing) kt.launches[KT_MERGE]++;
+  else t_end(KT_MERGE, 0, /*chain=*/!r.sa.on);  // (a fused round is followed by the host's turn, not by another kernel: its end event must not start the next interval)
+}
+
+// class A in word mode: the batch's rules -> worklist of words (k_wgather; it also allots the new tokens' instance lists), then the words (k_words)
+void GpuCtx::round_launch_words(Round &r) {
+  WordClass &c = cls_[0];
+  const uint32_t *d_xyz = nullptr;
+  if (!r.by_args) {
+    memcpy(h_pin_->xyz, r.xyz, (size_t)r.k * 12);
+    HIP_CHECK(hipMemcpyAsync(d_xyz_, h_pin_->xyz, (size_t)r.k * 12, hipMemcpyHostToDevice, strm()));
+    d_xyz = d_xyz_;
+  }
+  if (r.k > WGATHER_MAXK) throw GpuError{"merge_apply: batch too large for the word-mode gather"};
+  WGatherArgs ga{};  // (the worklist's length is at zero: enter_word_mode, then every round's k_delta_apply)
+  ga.ix = idx_;
+  ga.ix_valid = idx_valid_ ? 1u : 0u;
+  ga.z_static = idx_valid_ ? idx_zbuild_ : 0xffffffffu;  // (no index: every rule is "not found", the round takes every word)
+  ga.tl = tl_;
+  ga.stamp = d_stamp_;
+  ga.round_id = (uint32_t)(merge_rounds + 1);
+  ga.worklist = d_wworklist_;
+  ga.wl_seg = c.n_unique + 64;
+  ga.work_n = c.d_work_n;
+  ga.gm = d_gather_->matched;
+  ga.done_ctr = &d_gather_->ticket;
+  ga.xyz = d_xyz;
+  ga.k = r.k;
+  ga.z_base = r.z_base;
+  if (r.by_args)
+    for (uint32_t j = 0; j < r.k; j++) ga.cnt[j] = r.rule_counts ? (uint32_t)std::min<unsigned long long>(r.rule_counts[j], 0xffffffffull) : 0xffffffffu;
+  if (!d_stamp_) {  // (the index could not be built yet: no stamps either -- the gather must not claim words)
+    stamp_cap_ = (unsigned int)(c.n_unique + c.n_unique / 8 + 64);
+    d_stamp_ = dmalloc<uint32_t>(stamp_cap_);
+    HIP_CHECK(hipMemsetAsync(d_stamp_, 0, (size_t)stamp_cap_ * 4, strm()));
+    ga.stamp = d_stamp_;
+  }
+  // live tokens per class-A word, about: what the class held when it left the tiles, less a token per merge site since (a round or two behind)
+  if (sites_last_ != ~0ull && word_sites_seen_ != sites_cum_) {
+    word_live_tokens_ -= std::min(word_live_tokens_, sites_cum_ - std::min(sites_cum_, word_sites_seen_));
+    word_sites_seen_ = sites_cum_;
+  }
+  ga.stats = d_stats_;
+  const BatchArgs gba = r.first_ba();
+  WordsRound wr{};
+  wr.ws = WordSet{c.d_tok, d_wmeta_, c.d_wcnt, (uint32_t)c.n_unique};
+  wr.pt = r.kpt;
+  wr.db = db_;
+  wr.rules = d_rules_;
+  wr.rule_mask = r.cap - 1;
+  wr.bloom_g = d_bloom_;
+  wr.self_x = r.self_x;
+  wr.self_z = r.self_z;
+  wr.drec = d_drec_;
+  wr.drec_cap = drec_cap_;
+  wr.drec_n = d_drec_n_;
+  wr.irec = d_irec_;
+  wr.ba = &gba;
+  wr.scan = tail_of(r, 0);
+  wr.work_hint = sites_last_ != ~0ull && idx_valid_ ? (unsigned int)std::min<unsigned long long>(2 * sites_last_ + word_hint_floor_, 1ull << 30) : 0u;
+  wr.inline_max = words_inline_max_;
+  wr.ga = &ga;
+  wr.fuse_max = words_fuse_max_;
+  wr.avg_word_tokens = (unsigned int)std::min<unsigned long long>(std::max<unsigned long long>(1, word_live_tokens_ / std::max<unsigned long long>(1, c.n_unique)), 1u << 16);
+  wr.wgather_grid = hook_or_auto(cfg_->wgather_grid);
+  wr.words_grid = hook_or_auto(cfg_->words_grid);
+  wr.words_wpi = hook_or_auto(cfg_->words_wpi);
+  if (launch_words_apply(wr, strm())) word_fused_rounds++;
+  word_rounds++;
+  if (!idx_valid_) word_all_rounds++;
+}
+
+// tuning aids, after the round's launches: cumulative device statistics after every round (YTTM_TRACE_ROUNDS), the measurement pass's snapshot
+void GpuCtx::round_trace(const Round &r) {
   const char *trace_rounds = trace_rounds_;
   if (trace_rounds) {
-    chain_event_ = nullptr;  // tuning aid: cumulative device stats after every round (adds a sync)
-    unsigned long long stt[24];
+    chain_event_ = nullptr;  // (adds a sync)
+    unsigned long long stt[STAT_TAIL];
     launch_fold_stats(d_stats_, pt_.n_keys, strm());
     HIP_CHECK(hipMemcpyAsync(stt, d_stats_, sizeof stt, hipMemcpyDeviceToHost, strm()));
     sync();
@@ -436,14 +495,17 @@ void GpuCtx::merge_apply(const uint32_t *xyz, uint32_t k, const unsigned long lo
       HIP_CHECK(hipMemcpy(rows.data(), d_stats_, STATS_WORDS * 8, hipMemcpyDeviceToHost));
       std::string name = cfg_->trace_blocks.raw + "." + std::to_string(merge_rounds);
       if (FILE *fb = fopen(name.c_str(), "w")) {
-        for (int b = 0; b < 1536; b++) fprintf(fb, "%d %llu %llu %llu\n", b, rows[32 + 8 * b + 5], rows[32 + 8 * b + 6], rows[32 + 8 * b + 7]);
+        for (int b = 0; b < BLK_ROWS; b++) {
+          const unsigned long long *row = rows.data() + blk_at(b);
+          fprintf(fb, "%d %llu %llu %llu\n", b, row[BLK_PROF_T0], row[BLK_PROF_T1], row[BLK_PROF_AUX]);
+        }
         fclose(fb);
       }
     }
     FILE *f = fopen(trace_rounds, merge_rounds == 1 ? "w" : "a");
     if (f) {
-      fprintf(f, "%llu %u %llu %llu %llu %llu %u", merge_rounds, k, stt[0], stt[1], stt[2], stt[3], cls_[0].n_tiles);
-      for (int i = 8; i < 24; i++) fprintf(f, " %llu", stt[i]);
+      fprintf(f, "%llu %u %llu %llu %llu %llu %u", merge_rounds, r.k, stt[STAT_SITES], stt[STAT_TOUCHED], stt[STAT_TOKENS], stt[STAT_TOUCHED_TOKENS], cls_[0].n_tiles);
+      for (int i = STAT_PROF; i < STAT_PROF + STAT_PROF_N; i++) fprintf(f, " %llu", stt[i]);
       fprintf(f, "\n");
       fclose(f);
     }
@@ -453,22 +515,26 @@ void GpuCtx::merge_apply(const uint32_t *xyz, uint32_t k, const unsigned long lo
     launch_fold_stats(d_stats_, pt_.n_keys, strm());
     HIP_CHECK(hipMemcpyAsync(st, d_stats_, sizeof st, hipMemcpyDeviceToHost, strm()));
     sync();
-    split_sites = st[0];
-    split_touched_words = st[4];
-    split_touched_word_tokens = st[5];
+    split_sites = st[STAT_SITES];
+    split_touched_words = st[STAT_INSTR_WORDS];
+    split_touched_word_tokens = st[STAT_INSTR_TOKENS];
   }
+}
+
+// what the round leaves for later: the batch whose pairs are still to be zeroed, the repack schedule, (multi-GPU) the exchange
+void GpuCtx::round_finish(const Round &r) {
   {  // the sites this round may add to what the mailbox has reported so far (maybe_repack)
     unsigned long long s3 = 0;
-    for (uint32_t j = 0; j < k; j++) s3 += rule_counts ? rule_counts[j] : (~0ull >> 8);
+    for (uint32_t j = 0; j < r.k; j++) s3 += r.rule_counts ? r.rule_counts[j] : (~0ull >> 8);
     rp_recent_[2] = rp_recent_[1];
     rp_recent_[1] = rp_recent_[0];
     rp_recent_[0] = std::min<unsigned long long>(s3, ~0ull >> 4);
   }
-  pending_zero_ = !sa.on || multi();  // (a fused round zeroes its batch's pairs itself; multi-GPU: exchange_round hands the batch to the fold's scan)
+  pending_zero_ = !r.sa.on || multi();  // (a fused round zeroes its batch's pairs itself; multi-GPU: exchange_round hands the batch to the fold's scan)
   zero_valid_ = true;
-  zero_ba_ = ba;
-  zero_cap_ = cap;
-  zero_self_key_ = self_x != 0xffffffffu ? pair_key(self_x, self_x) : PT_EMPTY;
+  zero_ba_ = r.ba;
+  zero_cap_ = r.cap;
+  zero_self_key_ = r.self_x != 0xffffffffu ? pair_key(r.self_x, r.self_x) : PT_EMPTY;
   // repack when the tiles are less than half full.  With the hot-list filter the fill is known for free (the previous
   // round's filters report the tokens they streamed); otherwise look every 8 rounds.
   if (hot_state_ == HOT_ACTIVE && live_tokens_last_) {
@@ -483,13 +549,7 @@ void GpuCtx::merge_apply(const uint32_t *xyz, uint32_t k, const unsigned long lo
     rounds_since_check_ = 0;
     for (int ci = 0; ci < 2; ci++) maybe_repack(ci);
   }
-  if (multi()) {  // (stream-ordered; the scan in the fold's tail reports blocks that were too small)
-    exchange_round(0, sa.on ? &sa : nullptr);
-  }
-  // single GPU: no sync here -- the candidate filter that always follows reads n_keys back together with its results
-  // (its sync also makes the pinned rule staging reusable for the next round)
-  // every occurrence of the batch's pairs has been merged (on every rank): their counts are exactly zero.  The candidate
-  // filter that follows zeroes them while it reads the hot list; any other reader goes through flush_pending_zero().
+  if (multi()) exchange_round(0, r.sa.on ? &r.sa : nullptr);  // (stream-ordered; the scan in the fold's tail reports blocks that were too small)
 }
 
 }  // namespace yttm

@@ -49,6 +49,11 @@ struct Comm {
 // returns the device (and pinned) memory cached by finished contexts to the driver
 void release_device_memory();
 
+struct PinBlock;    // gpu_ctx_internal.h: the pinned block, the device's round block, list lengths + tickets, the gather's counters
+struct RoundBlock;
+struct ListCtl;
+struct GatherCtl;
+
 struct KernelTimes {  // accumulated GPU time per kernel family, measured with HIP events on the ctx stream
   double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long launches[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -148,6 +153,19 @@ class GpuCtx {
   void read_stats(int first, int n, unsigned long long *out);  // (tuning aid: words of the device statistics block, synchronising)
 
  private:
+  // merge_apply's steps, in their order (gpu_ctx.cpp); Round: the round's values carried between them
+  struct Round;
+  void round_capacity(Round &r);
+  bool word_mode_pays(unsigned long long tiles_a, unsigned long long sites, unsigned long long tokens, unsigned long long ranks) const;
+  void round_word_mode(const Round &r);
+  void round_batch(Round &r);
+  void round_scan(Round &r, const unsigned long long *next_tau_cnt, uint32_t next_tau_mx, uint32_t next_want);
+  void round_block_size(const Round &r);
+  const ScanArgs *tail_of(const Round &r, int ci) const;
+  void round_launch(Round &r);
+  void round_launch_words(Round &r);
+  void round_trace(const Round &r);
+  void round_finish(const Round &r);
   void upload_staged(unsigned long long n, const std::function<bool(void *dst, unsigned long long off, size_t len)> &fill);
   void ensure_table_capacity(unsigned long long need_keys);
   void rebuild_hot();
@@ -156,10 +174,12 @@ class GpuCtx {
   enum TopState { TOP_INVALID, TOP_ACTIVE, TOP_BYPASS };  // BYPASS: ties too large for the top list, the hot list is scanned instead
   TopState top_state_ = TOP_INVALID;
   uint32_t *d_top_slots_ = nullptr;
-  unsigned int *d_top_n_ = nullptr;
+  ListCtl *d_top_ctl_ = nullptr;
   unsigned int top_cap_ = 0, top_target_ = 0, top_min_ = 0, top_listed_last_ = 0, bypass_rounds_ = 0;
   void poll_mailbox(uint32_t round_id);
+  ScanArgs scan_args(unsigned long long tau_cnt, uint32_t tau_mx, uint32_t round_id) const;
   bool scan_hot(unsigned long long t, uint32_t tm);
+  unsigned int fetch_candidates(CandRec *h, unsigned int n, std::vector<CandRec> &out);
   bool refill_top();
   bool hot_just_rebuilt_ = false;
   const unsigned long long *last_hist_ = nullptr;
@@ -167,7 +187,7 @@ class GpuCtx {
   unsigned int last_top_bin_ = CAND_BINS - 1;
   unsigned long long bound_prev_ = 0;  // new-key bound of the previous round (see merge_apply)
   uint32_t *d_hot_slots_ = nullptr;
-  unsigned int *d_hot_n_ = nullptr;
+  ListCtl *d_hot_ctl_ = nullptr;  // (its ticket: k_hot_scan's and every fused tail's finished workgroups)
   unsigned int fullscan_rounds_ = 0;
   uint32_t mail_round_ = 0;
   bool fused_pending_ = false;  // a fused scan is in flight / in the mailbox ...
@@ -274,7 +294,7 @@ class GpuCtx {
   unsigned int word_min_tiles_ = 16384;
   unsigned long long idx_agg_min_ = 16ull << 20, word_min_tokens_ = 48ull << 20;
   unsigned long long *d_wmeta_ = nullptr;
-  unsigned int *d_gm_ = nullptr;   // [WGATHER_MAXK] + the gather's ticket
+  GatherCtl *d_gather_ = nullptr;
   uint32_t *d_xyz_ = nullptr;      // a batch too large for BatchArgs, as (x, y, z) triples
   uint32_t *d_wworklist_ = nullptr;  // [n_unique + 64] the round's words
   DeltaRec *d_drec_ = nullptr;       // [WORDS_MAX_GRID * drec_cap_] the round's count updates, a region per workgroup of k_words
@@ -291,6 +311,7 @@ class GpuCtx {
   unsigned long long rp_total_[2] = {0, 0}, rp_sites_at_[2] = {0, 0}, rp_recent_[3] = {0, 0, 0};
   bool pending_zero_ = false, zero_valid_ = false;  // valid: the zero_* members still describe the last batch
   void flush_pending_zero();
+  ZeroBatch zero_batch() const;  // what the next scan of a candidate list zeroes (nothing unless pending_zero_)
   unsigned int zero_cap_ = 0;
   BatchArgs zero_ba_{};  // the batch whose pairs are still to be zeroed, when it travelled as a kernel argument
   unsigned long long zero_self_key_ = 0;
@@ -302,14 +323,10 @@ class GpuCtx {
   unsigned int rules_cap_ = 0;
   uint32_t id_cap_ = 0;  // token ids are below this (vocab_size + slack)
   unsigned long long *d_stats_ = nullptr;
-  void *h_pin_ = nullptr;  // pinned staging (rules + flag updates + candidate header)
-  size_t h_pin_bytes_ = 0;
+  PinBlock *h_pin_ = nullptr;  // pinned: the mailbox, the candidates' read-back area, batch staging
   // candidates
-  unsigned char *d_round_ = nullptr;
-  CandRec *d_cand_ = nullptr;
+  RoundBlock *d_round_ = nullptr;
   unsigned int cand_cap_ = 0;
-  unsigned int *d_cand_n_ = nullptr;
-  unsigned long long *d_cand_hist_ = nullptr;
   // multi-GPU delta exchange.  db_ = the round's delta table and send block (yttm_device.h: DeltaBuf); per round the first blk_ 16-byte
   // units of every rank's send block are all-gathered into d_recv_
   DeltaBuf db_{};
@@ -324,7 +341,8 @@ class GpuCtx {
   unsigned long long *d_xstat_ = nullptr;  // [XSTAT_WORDS] the fold's report on a round's exchange (yttm_kernels.h)
   unsigned int xch_parity_ = 0;            // which send block this round's updates go to
   uint32_t *d_maybe_ = nullptr;            // slots whose count an add of this round saw at or above a list threshold (PairTable::maybe)
-  unsigned int *d_maybe_n_ = nullptr, maybe_cap_ = 0;
+  ListCtl *d_maybe_ctl_ = nullptr;         // (its ticket: k_dt_clean's)
+  unsigned int maybe_cap_ = 0;
   unsigned long long xch_sites_ = 0;       // merge sites (summed pair counts of the batch) of the round whose exchange is under way
   double xrate_[2] = {5.0, 5.0};           // delta records of the busiest rank per merge site, last two rounds
   bool multi() const { return comm_ != nullptr; }  // (a communicator of world size 1 still runs the whole exchange path)

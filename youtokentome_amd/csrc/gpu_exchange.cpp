@@ -53,7 +53,7 @@ void GpuCtx::exchange_deltas() {
 // there (k_dt_clean: off the critical path -- it runs while the host picks the next batch)
 void GpuCtx::finish_block(unsigned int n_hint) {
   db_.send = d_send2_[xch_parity_];
-  launch_dt_clean(db_, d_send2_[xch_parity_ ^ 1u], n_hint, d_stats_, cls_[0].n_tiles, d_maybe_n_ + 1, strm());
+  launch_dt_clean(db_, d_send2_[xch_parity_ ^ 1u], n_hint, d_stats_, cls_[0].n_tiles, &d_maybe_ctl_->ticket, strm());
   xch_last_ = d_send2_[xch_parity_];
   xch_parity_ ^= 1u;
   db_.send = d_send2_[xch_parity_];
@@ -61,7 +61,7 @@ void GpuCtx::finish_block(unsigned int n_hint) {
 PairTable GpuCtx::pt_nolist() const {
   PairTable p = pt_;
   p.maybe = d_maybe_;  // (the adds note the slots that may have crossed a threshold: k_fold_list looks at those, by their final counts)
-  p.maybe_n = d_maybe_n_;
+  p.maybe_n = &d_maybe_ctl_->n;
   p.maybe_cap = maybe_cap_;
   p.maybe_hot = pt_.hot_tau;
   p.maybe_top = pt_.top_tau;
@@ -79,10 +79,9 @@ void GpuCtx::exchange_round(unsigned long long only_mask, const ScanArgs *scan) 
   if (!alone) launch_pt_apply_blocks(pt_nolist(), d_recv_, blk_, comm_->world, comm_->rank, only_mask, d_xstat_, d_stats_, strm());
   PairTable fpt = pt_;  // (the real thresholds, and the notes to go through)
   fpt.maybe = d_maybe_;
-  fpt.maybe_n = d_maybe_n_;
+  fpt.maybe_n = &d_maybe_ctl_->n;
   fpt.maybe_cap = maybe_cap_;
-  launch_fold_list(fpt, d_recv_, blk_, comm_->world, only_mask, scan, d_stats_, pending_zero_ && !zero_ba_.k ? d_rules_ : nullptr, zero_cap_ - 1, zero_self_key_,
-                   pending_zero_ && zero_ba_.k ? &zero_ba_ : nullptr, d_xstat_, alone, strm());
+  launch_fold_list(fpt, d_recv_, blk_, comm_->world, only_mask, scan, d_stats_, zero_batch(), d_xstat_, alone, strm());
   if (scan) pending_zero_ = false;  // (the scan zeroes the finished batch's pairs)
   if (!only_mask) finish_block((unsigned int)std::min<unsigned long long>(blk_ / 2, 1u << 18));  // (about as many records as the block was sized for)
 }

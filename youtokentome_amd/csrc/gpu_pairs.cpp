@@ -11,11 +11,11 @@ void GpuCtx::alloc_table(PairTable &pt, unsigned long long cap) {
   pt.mask = cap - 1;
   pt.hot_tau = ~0ull;  // no hot list until rebuild_hot()
   pt.hot_slots = d_hot_slots_;
-  pt.hot_n = d_hot_n_;
+  pt.hot_n = &d_hot_ctl_->n;
   pt.hot_cap = hot_cap_;
   pt.top_tau = ~0ull;
   pt.top_slots = d_top_slots_;
-  pt.top_n = d_top_n_;
+  pt.top_n = &d_top_ctl_->n;
   pt.top_cap = top_cap_;
   hot_state_ = HOT_INVALID;
   top_state_ = TOP_INVALID;
@@ -85,8 +85,8 @@ void GpuCtx::pair_count() {
       HIP_CHECK(hipMemsetAsync(d_xstat_, 0, XSTAT_WORDS * 8, strm()));
       maybe_cap_ = std::max(1u, (unsigned int)cfg_->xchg_notes.u);  // (tests shrink it: the fold then walks every record)
       d_maybe_ = dmalloc<uint32_t>(maybe_cap_);
-      d_maybe_n_ = dmalloc<unsigned int>(4);
-      HIP_CHECK(hipMemsetAsync(d_maybe_n_, 0, 16, strm()));
+      d_maybe_ctl_ = dmalloc<ListCtl>(1);
+      HIP_CHECK(hipMemsetAsync(d_maybe_ctl_, 0, sizeof(ListCtl), strm()));
       blk_min_ = std::max(2u * XHDR, (unsigned int)cfg_->xchg_blk_min.u);  // (tests shrink it to force the repeat path)
       blk_ = blk_min_;
       grow_recv(std::max<unsigned long long>(send_cap_, blk_ * (unsigned long long)comm_->world));
@@ -136,6 +136,18 @@ void GpuCtx::download_pairs(std::vector<unsigned long long> &keys, std::vector<u
   for (uint32_t i = 0; i < n; i++) { keys[i] = out[i].key; cnts[i] = out[i].cnt; }
 }
 
+// The host's view of a scan's n candidates: the first CAND_FAST are in `h` already (the mailbox, or scan_full's copy); more only by a second
+// copy behind them (the host rarely looks past a few thousand).  Returns how many `out` got.
+unsigned int GpuCtx::fetch_candidates(CandRec *h, unsigned int n, std::vector<CandRec> &out) {
+  const unsigned int take = std::min(n, cand_cap_);
+  if (take > CAND_FAST) {
+    HIP_CHECK(hipMemcpyAsync(h + CAND_FAST, d_round_->cand + CAND_FAST, (size_t)(take - CAND_FAST) * sizeof(CandRec), hipMemcpyDeviceToHost, strm()));
+    sync();
+  }
+  out.assign(h, h + take);
+  return take;
+}
+
 uint32_t GpuCtx::scan_full(unsigned long long tau_cnt, uint32_t tau_mx, std::vector<CandRec> &out, unsigned long long *hist) {
   HIP_CHECK(hipSetDevice(device_));
   tl_stream = strm();
@@ -150,34 +162,27 @@ uint32_t GpuCtx::scan_full(unsigned long long tau_cnt, uint32_t tau_mx, std::vec
   }
   flush_pending_zero();
   launch_fold_stats(d_stats_, pt_.n_keys, strm());
-  HIP_CHECK(hipMemsetAsync(d_cand_n_, 0, 16, strm()));
-  HIP_CHECK(hipMemsetAsync(d_cand_hist_, 0, CAND_BINS * 8, strm()));
+  HIP_CHECK(hipMemsetAsync(d_round_->n_out, 0, sizeof d_round_->n_out, strm()));
+  HIP_CHECK(hipMemsetAsync(d_round_->hist, 0, CAND_BINS * 8, strm()));
   t_begin(KT_CAND);
-  launch_cand_scan(pt_, tau_cnt, tau_mx, d_cand_, cand_cap_, d_cand_n_, d_cand_hist_, strm());  // (always with the histogram: last_hist())
+  launch_cand_scan(pt_, tau_cnt, tau_mx, d_round_->cand, cand_cap_, d_round_->n_out, d_round_->hist, strm());  // (always with the histogram: last_hist())
   t_end(KT_CAND, 16 * pt_cap_);
   // ONE device-to-host copy per round: header + histogram + the first CAND_FAST candidates; a second copy only when
   // more candidates passed (the host rarely looks past a few thousand)
-  constexpr unsigned int CAND_FAST = 4096;
-  unsigned char *h = (unsigned char *)h_pin_;
-  HIP_CHECK(hipMemcpyAsync(h, d_round_, 8192 + (size_t)CAND_FAST * sizeof(CandRec), hipMemcpyDeviceToHost, strm()));
+  const RoundBlock &h = h_pin_->round;  // (the device's round block, copied over the mailbox)
+  HIP_CHECK(hipMemcpyAsync(&h_pin_->round, d_round_, offsetof(RoundBlock, cand) + (size_t)CAND_FAST * sizeof(CandRec), hipMemcpyDeviceToHost, strm()));
   sync();
-  const unsigned int n = *(unsigned int *)h;
-  n_keys_host = *(unsigned int *)(h + 4);
-  if (hist) memcpy(hist, h + 64, CAND_BINS * 8);
-  memcpy(hist_buf_, h + 64, CAND_BINS * 8);
+  const unsigned int n = h.n_out[0];
+  n_keys_host = h.n_out[1];
+  if (hist) memcpy(hist, h.hist, CAND_BINS * 8);
+  memcpy(hist_buf_, h.hist, CAND_BINS * 8);
   last_hist_ = hist_buf_;
   last_live_ = 0;
   last_top_bin_ = CAND_BINS - 1;
   for (int b = 1; b < CAND_BINS; b++) last_live_ += hist_buf_[b];
-  const unsigned int take = std::min(n, cand_cap_);
-  CandRec *h_c = (CandRec *)(h + 8192);
-  if (take > CAND_FAST) {
-    HIP_CHECK(hipMemcpyAsync(h_c + CAND_FAST, d_cand_ + CAND_FAST, (size_t)(take - CAND_FAST) * sizeof(CandRec), hipMemcpyDeviceToHost, strm()));
-    sync();
-  }
-  out.assign(h_c, h_c + take);
-  HIP_CHECK(hipMemsetAsync(d_cand_n_, 0, 16, strm()));  // the hot-list filter expects its counters cleared
-  HIP_CHECK(hipMemsetAsync(d_cand_hist_, 0, CAND_BINS * 8, strm()));
+  fetch_candidates(h_pin_->round.cand, n, out);
+  HIP_CHECK(hipMemsetAsync(d_round_->n_out, 0, sizeof d_round_->n_out, strm()));  // the hot-list filter expects its counters cleared
+  HIP_CHECK(hipMemsetAsync(d_round_->hist, 0, CAND_BINS * 8, strm()));
   return n;
 }
 
@@ -209,7 +214,7 @@ void GpuCtx::rebuild_hot() {
     return;
   }
   pt_.hot_tau = std::max<unsigned long long>(1, cand_bin_lower(chosen));
-  HIP_CHECK(hipMemsetAsync(d_hot_n_, 0, 4, strm()));
+  HIP_CHECK(hipMemsetAsync(&d_hot_ctl_->n, 0, 4, strm()));
   t_begin(KT_CAND);
   launch_hot_rebuild(pt_, strm());
   t_end(KT_CAND, 8 * pt_cap_);
@@ -217,11 +222,25 @@ void GpuCtx::rebuild_hot() {
   hot_just_rebuilt_ = true;
 }
 
+// What every scan that publishes in the mailbox is told: threshold, where the candidates go, the id to publish (done_ctr: a single-workgroup launch).
+ScanArgs GpuCtx::scan_args(unsigned long long tau_cnt, uint32_t tau_mx, uint32_t round_id) const {
+  ScanArgs sa{};
+  sa.on = 1u;
+  sa.tau_cnt = tau_cnt;
+  sa.tau_mx = tau_mx;
+  sa.out = d_round_->cand;
+  sa.cap = cand_cap_;
+  sa.fast = CAND_FAST;
+  sa.mailbox = &h_pin_->mailbox;
+  sa.round_id = round_id;
+  return sa;
+}
+
 // Waits for `round_id` in the pinned mailbox: the kernel that publishes it writes header + histogram + first candidates there
 // first (a copy + stream synchronisation would cost tens of microseconds per round).
 void GpuCtx::poll_mailbox(uint32_t round_id) {
-  unsigned char *h = (unsigned char *)h_pin_;
-  volatile uint32_t *flag = (volatile uint32_t *)(h + 32);
+  const RoundMailbox &mb = h_pin_->mailbox;
+  volatile const uint32_t *flag = &mb.round_id;
   for (unsigned long long spins = 0; *flag != round_id; spins++) {
     if ((spins & 0x3fff) == 0x3fff) {
       const hipError_t q = hipStreamQuery(st_raw_);
@@ -233,21 +252,21 @@ void GpuCtx::poll_mailbox(uint32_t round_id) {
     }
   }
   std::atomic_thread_fence(std::memory_order_acquire);
-  const unsigned long long cum = *(const unsigned long long *)(h + 40);
+  const unsigned long long cum = mb.tokens_cum;
   if (cum != scanned_cum_) {  // a merge round ran since the last call: that is how many tokens its filters streamed
     live_tokens_last_ = cum - scanned_cum_;
     scanned_cum_ = cum;
-    const unsigned long long touched = *(const unsigned long long *)(h + 48);
+    const unsigned long long touched = mb.touched_cum;
     touched_last_ = touched - touched_cum_;
     touched_cum_ = touched;
   }
-  const unsigned long long sites = *(const unsigned long long *)(h + 88);  // (published by scan_top only; one round old, like the token counts)
+  const unsigned long long sites = mb.sites_cum;  // (published by scan_top only; one round old, like the token counts)
   if (sites > sites_cum_) {
     sites_last_ = sites - sites_cum_;
     sites_cum_ = sites;
   }
   if (multi()) {  // the same numbers summed over the ranks' block headers: what the switch to word mode is decided from
-    const unsigned long long *xs = (const unsigned long long *)(h + MB_XSUM);
+    const unsigned long long *xs = mb.xsum;
     if (xs[3] == (unsigned long long)comm_->world) {  // (a scan that ran before any exchange leaves zeros)
       if (xs[0] > g_sites_cum_) { g_sites_last_ = xs[0] - g_sites_cum_; g_sites_cum_ = xs[0]; }
       if (xs[1] > g_tokens_cum_) { g_tokens_last_ = xs[1] - g_tokens_cum_; g_tokens_cum_ = xs[1]; }
@@ -260,38 +279,41 @@ void GpuCtx::poll_mailbox(uint32_t round_id) {
 // live counts, the pending zeroing of the finished batch's pairs.  Leaves the result in the mailbox.  False: the exchange of
 // this round had to be completed first (multi-GPU), scan again.
 bool GpuCtx::scan_hot(unsigned long long t, uint32_t tm) {
-  constexpr unsigned int CAND_FAST = 4096;
-  unsigned char *h = (unsigned char *)h_pin_;
-  const uint32_t round_id = ++mail_round_;
+  HotScan hs{};
+  hs.pt = pt_;
+  hs.sa = scan_args(t, tm, ++mail_round_);
+  hs.sa.done_ctr = &d_hot_ctl_->ticket;
+  hs.n_out = d_round_->n_out;
+  hs.hist = d_round_->hist;
+  hs.stats = d_stats_;
+  hs.zero = zero_batch();
+  hs.listed_hint = listed_last_ ? listed_last_ + 4096 : hot_cap_;
+  hs.xstat = multi() ? d_xstat_ : nullptr;
   t_begin(KT_CAND);
-  launch_hot_scan(pt_, t, tm, d_cand_, cand_cap_, d_cand_n_, d_cand_hist_, d_hot_n_ + 1, h, CAND_FAST, round_id, d_stats_,
-                  pending_zero_ && !zero_ba_.k ? d_rules_ : nullptr, zero_cap_ - 1, zero_self_key_, listed_last_ ? listed_last_ + 4096 : hot_cap_,
-                  pending_zero_ && zero_ba_.k ? &zero_ba_ : nullptr, multi() ? d_xstat_ : nullptr, strm());
+  launch_hot_scan(hs, strm());
   pending_zero_ = false;
   t_end(KT_CAND, 20ull * listed_last_);  // (not chained: the host round trip that follows belongs to no kernel family)
-  poll_mailbox(round_id);
-  const unsigned int *hdr = (const unsigned int *)h;
-  n_keys_host = hdr[1];
-  listed_last_ = std::min(hdr[2], hot_cap_);
-  if (multi() && settle_exchange(*(const unsigned long long *)(h + 56), *(const unsigned long long *)(h + 64), *(const unsigned long long *)(h + 80))) return false;
-  return true;
+  poll_mailbox(hs.sa.round_id);
+  const RoundMailbox &mb = h_pin_->mailbox;
+  n_keys_host = mb.n_keys;
+  listed_last_ = std::min(mb.listed, hot_cap_);
+  return !(multi() && settle_exchange(mb.xverdict[0], mb.xverdict[1], mb.xverdict[3]));
 }
 
 // Refill of the top list (L2) from the hot list (L1): one scan of L1 for the histogram of its live counts, the threshold that
 // puts about top_target_ of them on the top list, one pass that lists them.  False: L1 itself has to be rebuilt first (it
 // overflowed or ran dry; hot_state_ says so) or the scan has to be repeated.
 bool GpuCtx::refill_top() {
-  unsigned char *h = (unsigned char *)h_pin_;
   if (!scan_hot(~0ull >> 2, 0)) return false;
-  const unsigned int *hdr = (const unsigned int *)h;
-  const unsigned int listed = hdr[2], live = hdr[3];
+  const RoundMailbox &mb = h_pin_->mailbox;
+  const unsigned int listed = mb.listed, live = mb.live;
   const bool over = listed > hot_cap_;  // (multi-GPU: the lists hold the same pairs on every rank -- k_fold_list -- so this verdict is every rank's)
   if (over || (live < hot_min_ && pt_.hot_tau > 1 && !hot_just_rebuilt_)) {
     hot_state_ = HOT_INVALID;  // overflowed, or running dry: relist with a new threshold (a list that is short right after its
     return false;              // rebuild stays: ties kept the threshold up)
   }
   hot_just_rebuilt_ = false;
-  const unsigned long long *hist = (const unsigned long long *)(h + MB_HIST);
+  const unsigned long long *hist = mb.hist;
   unsigned long long acc = 0;
   int chosen = -1;
   for (int b = CAND_BINS - 1; b >= 1; b--) {
@@ -308,7 +330,7 @@ bool GpuCtx::refill_top() {
     return true;
   }
   pt_.top_tau = std::max<unsigned long long>(pt_.hot_tau, cand_bin_lower(chosen));
-  HIP_CHECK(hipMemsetAsync(d_top_n_, 0, 4, strm()));
+  HIP_CHECK(hipMemsetAsync(&d_top_ctl_->n, 0, 4, strm()));
   t_begin(KT_CAND);
   launch_top_rebuild(pt_, listed_last_, strm());
   t_end(KT_CAND, 20ull * listed_last_);
@@ -331,8 +353,7 @@ uint32_t GpuCtx::candidates(unsigned long long tau_cnt, uint32_t tau_mx, std::ve
     last_live_ = 0;
     return 0;
   }
-  constexpr unsigned int CAND_FAST = 4096;
-  unsigned char *h = (unsigned char *)h_pin_;
+  const RoundMailbox &mb = h_pin_->mailbox;
   const bool fused_ok = fused_pending_ && fused_tau_ == tau_cnt && fused_mx_ == tau_mx;
   fused_pending_ = false;  // (a scan that was fused but is not wanted any more is simply ignored)
   int dry_refills = 0, dry_rebuilds = 0;
@@ -368,10 +389,9 @@ uint32_t GpuCtx::candidates(unsigned long long tau_cnt, uint32_t tau_mx, std::ve
     bool hot_over = false, top_over = false;
     if (top_state_ == TOP_BYPASS) {
       if (!scan_hot(t, tm)) continue;
-      const unsigned int *hdr = (const unsigned int *)h;
-      n = hdr[0];
-      live = hdr[3];
-      hot_over = hdr[2] > hot_cap_;
+      n = mb.n_cand;
+      live = mb.live;
+      hot_over = mb.listed > hot_cap_;
       if (hot_over || (live < hot_min_ && pt_.hot_tau > 1 && dry_rebuilds < 1)) {
         if (!hot_over) dry_rebuilds++;
         hot_state_ = HOT_INVALID;
@@ -380,37 +400,25 @@ uint32_t GpuCtx::candidates(unsigned long long tau_cnt, uint32_t tau_mx, std::ve
     } else {
       const uint32_t round_id = use_fused ? fused_round_ : ++mail_round_;
       if (!use_fused) {
-        ScanArgs sa{};
-        sa.on = 1;
-        sa.tau_cnt = t;
-        sa.tau_mx = tm;
-        sa.out = d_cand_;
-        sa.cap = cand_cap_;
-        sa.fast = CAND_FAST;
-        sa.done_ctr = nullptr;
-        sa.mailbox = h;
-        sa.round_id = round_id;
         t_begin(KT_CAND);
-        launch_top_scan(pt_, sa, d_stats_, pending_zero_ && !zero_ba_.k ? d_rules_ : nullptr, zero_cap_ - 1, zero_self_key_,
-                        pending_zero_ && zero_ba_.k ? &zero_ba_ : nullptr, multi() ? d_xstat_ : nullptr, strm());
+        launch_top_scan(pt_, scan_args(t, tm, round_id), d_stats_, zero_batch(), multi() ? d_xstat_ : nullptr, strm());
         pending_zero_ = false;
         t_end(KT_CAND, 20ull * top_listed_last_);
       }
       poll_mailbox(round_id);
-      const unsigned int *hdr = (const unsigned int *)h;
-      n = hdr[0];
-      n_keys_host = hdr[1];
-      const unsigned int top_listed = hdr[2], hot_listed = hdr[4];
-      live = hdr[3];
+      n = mb.n_cand;
+      n_keys_host = mb.n_keys;
+      const unsigned int top_listed = mb.listed, hot_listed = mb.hot_listed;
+      live = mb.live;
       top_listed_last_ = std::min(live, top_cap_);
       hot_over = hot_listed > hot_cap_;
       top_over = top_listed > top_cap_;
       if (use_fused) {
         fused_rounds++;
         if (dev_timing_pending_) {  // the round's duration by the device's 100 MHz clock (merge_apply: dev_timing)
-          double ms = (double)*(const unsigned long long *)(h + 24) * 1e-5;
+          double ms = (double)mb.round_ticks * 1e-5;
           if (multi()) {  // the apply kernels, and what follows them (pack, all-gather, fold, scan), apart
-            const double k4 = std::min(ms, (double)*(const unsigned long long *)(h + MB_XSUM + 32) * 1e-5);
+            const double k4 = std::min(ms, (double)mb.xsum[4] * 1e-5);
             kt.ms[KT_XCHG] += ms - k4;
             kt.launches[KT_XCHG]++;
             ms = k4;
@@ -420,7 +428,7 @@ uint32_t GpuCtx::candidates(unsigned long long tau_cnt, uint32_t tau_mx, std::ve
           dev_round_ms_.push_back((float)ms);
           last_round_dev_ms = ms;
         }
-        const unsigned long long *tmk = (const unsigned long long *)(h + 96);  // scan_top's marks (100 MHz wall clock)
+        const unsigned long long *tmk = mb.tail_marks;  // scan_top's marks (100 MHz wall clock)
         tail_ticks[0] += tmk[1] - tmk[0];
         tail_ticks[1] += tmk[2] - tmk[1];
         tail_ticks[2] += tmk[3] - tmk[2];
@@ -430,7 +438,7 @@ uint32_t GpuCtx::candidates(unsigned long long tau_cnt, uint32_t tau_mx, std::ve
       // a scan that found its list overflowed read nothing -- and so did not zero the finished batch's pairs: k_pt_zero /
       // the next scan does it (the batch is still described by the zero_* members)
       if (top_over) pending_zero_ = zero_valid_;
-      if (multi() && settle_exchange(*(const unsigned long long *)(h + 56), *(const unsigned long long *)(h + 64), *(const unsigned long long *)(h + 80))) continue;
+      if (multi() && settle_exchange(mb.xverdict[0], mb.xverdict[1], mb.xverdict[3])) continue;
       if (hot_over) {
         hot_state_ = HOT_INVALID;
         continue;
@@ -452,17 +460,11 @@ uint32_t GpuCtx::candidates(unsigned long long tau_cnt, uint32_t tau_mx, std::ve
         }
       }
     }
-    if (hist) memcpy(hist, h + MB_HIST, CAND_BINS * 8);
-    last_hist_ = (const unsigned long long *)(h + MB_HIST);
+    if (hist) memcpy(hist, mb.hist, CAND_BINS * 8);
+    last_hist_ = mb.hist;
     last_live_ = live;
-    last_top_bin_ = top_state_ == TOP_ACTIVE ? std::min<unsigned int>(((const unsigned int *)h)[5], CAND_BINS - 1) : CAND_BINS - 1;
-    const unsigned int take = std::min(n, cand_cap_);
-    CandRec *h_c = (CandRec *)(h + 8192);
-    if (take > CAND_FAST) {
-      HIP_CHECK(hipMemcpyAsync(h_c + CAND_FAST, d_cand_ + CAND_FAST, (size_t)(take - CAND_FAST) * sizeof(CandRec), hipMemcpyDeviceToHost, strm()));
-      sync();
-    }
-    out.assign(h_c, h_c + take);
+    last_top_bin_ = top_state_ == TOP_ACTIVE ? std::min<unsigned int>(mb.top_bin, CAND_BINS - 1) : CAND_BINS - 1;
+    const unsigned int take = fetch_candidates(h_pin_->mailbox.cand, n, out);
     if (const char *dbg = dbg_cand_) {  // debugging aid: one line per scan, comparable across scan implementations
       static FILE *f = nullptr;
       if (!f) f = fopen(dbg, "w");
@@ -488,20 +490,17 @@ void GpuCtx::pair_query(const unsigned long long *keys, uint32_t n, unsigned lon
   DFREE(d_o);
 }
 
+ZeroBatch GpuCtx::zero_batch() const {
+  const bool by_args = zero_ba_.k != 0;  // (the batch travelled as a kernel argument: its rule hash never went to HBM)
+  return ZeroBatch{pending_zero_ && !by_args ? d_rules_ : nullptr, zero_cap_ - 1, zero_self_key_, pending_zero_ && by_args ? &zero_ba_ : nullptr};
+}
+
 void GpuCtx::flush_pending_zero() {
   if (!pending_zero_) return;
   chain_event_ = nullptr;
   if (zero_ba_.k) {  // the batch never went to HBM: upload its rule hash for k_pt_zero (rare: only readers other than the hot scan)
     std::vector<RuleSlot> tab(zero_cap_);
-    for (auto &r : tab) { r.key = PT_EMPTY; r.z = 0; r.pad = 0; }
-    for (uint32_t j = 0; j < zero_ba_.k; j++) {
-      const uint32_t x = zero_ba_.xy[2 * j], y = zero_ba_.xy[2 * j + 1];
-      if (x == y) continue;
-      const unsigned long long key = pair_key(x, y);
-      unsigned int h = pair_hash32(key) & (zero_cap_ - 1);
-      while (tab[h].key != PT_EMPTY) h = (h + 1) & (zero_cap_ - 1);
-      tab[h].key = key;
-    }
+    build_rule_hash(tab.data(), zero_cap_, zero_ba_.xy, 2, zero_ba_.k);
     HIP_CHECK(hipMemcpyAsync(d_rules_, tab.data(), tab.size() * sizeof(RuleSlot), hipMemcpyHostToDevice, strm()));
     sync();
   }

@@ -5,7 +5,7 @@
 namespace yttm {
 
 void GpuCtx::free_words() {
-  DFREE(d_wmeta_); DFREE(d_gm_); DFREE(d_xyz_); DFREE(d_wworklist_); DFREE(d_drec_); DFREE(d_drec_n_); DFREE(d_irec_);
+  DFREE(d_wmeta_); DFREE(d_gather_); DFREE(d_xyz_); DFREE(d_wworklist_); DFREE(d_drec_); DFREE(d_drec_n_); DFREE(d_irec_);
   DFREE(tl_.base); DFREE(tl_.cap); DFREE(tl_.fill); DFREE(tl_.rec_word); DFREE(tl_.rec_l); DFREE(tl_.rec_r); DFREE(tl_.cursor);
   tl_ = TokLists{};
   word_mode_ = false;
@@ -24,8 +24,8 @@ void GpuCtx::enter_word_mode(uint32_t z_next) {
   launch_words_init(c.ts, d_wmeta_, strm());
   d_wworklist_ = dmalloc<uint32_t>(c.n_unique + 64);
   HIP_CHECK(hipMemsetAsync(c.d_work_n, 0, 64, strm()));
-  d_gm_ = dmalloc<unsigned int>(WGATHER_MAXK + 4);
-  HIP_CHECK(hipMemsetAsync(d_gm_, 0, (WGATHER_MAXK + 4) * 4, strm()));
+  d_gather_ = dmalloc<GatherCtl>(1);
+  HIP_CHECK(hipMemsetAsync(d_gather_, 0, sizeof(GatherCtl), strm()));
   d_xyz_ = dmalloc<uint32_t>(3 * (size_t)RULES_CAP);
   drec_cap_ = (unsigned int)cfg_->word_drec.u;  // (tests: a region that overflows)
   d_drec_ = dmalloc<DeltaRec>((size_t)WORDS_MAX_GRID * drec_cap_);
@@ -47,8 +47,7 @@ void GpuCtx::enter_word_mode(uint32_t z_next) {
   tl_.rec_word = dmalloc<uint32_t>(tl_.log_cap);
   tl_.rec_l = dmalloc<uint32_t>(tl_.log_cap);
   tl_.rec_r = dmalloc<uint32_t>(tl_.log_cap);
-  tl_.broken = (unsigned int *)((unsigned char *)h_pin_ + PIN_BYTES - 64);  // (the last line of the pinned block -- behind the mailbox, the candidates' read-back
-                                                                            // area and the batch staging; the kernels write it with system-scope stores)
+  tl_.broken = &h_pin_->broken;  // (the kernels write it with system-scope stores)
   *(volatile unsigned int *)tl_.broken = 0;
   word_mode_ = true;
   word_global_ = true;
@@ -78,7 +77,7 @@ void GpuCtx::build_index(uint32_t z_next) {
   if (!c.n_tiles || hot_state_ != HOT_ACTIVE || !word_mode_) return;
   chain_event_ = nullptr;
   unsigned int listed = 0;  // (the list has grown since the scan that last reported its length)
-  HIP_CHECK(hipMemcpyAsync(&listed, d_hot_n_, 4, hipMemcpyDeviceToHost, strm()));
+  HIP_CHECK(hipMemcpyAsync(&listed, &d_hot_ctl_->n, 4, hipMemcpyDeviceToHost, strm()));
   sync();
   if (listed > hot_cap_) return;  // overflowed: the next scan rebuilds the list, and the index after it
   unsigned long long want = 1024;

@@ -171,12 +171,12 @@ __global__ __launch_bounds__(BLOCK) void k_giant(TileSet ts, unsigned int slot, 
         count_pairs(tok, wgt2, n2, +1, pt, db, &new_keys);
         if (threadIdx.x == 0) {
           ts.tile_len[t] = (uint32_t)n2;
-          atomicAdd(&stats[0], (unsigned long long)n_sites);
-          atomicAdd(&stats[1], 1ull);
-          atomicAdd(&stats[3], (unsigned long long)n);
+          atomicAdd(&stats[STAT_SITES], (unsigned long long)n_sites);
+          atomicAdd(&stats[STAT_TOUCHED], 1ull);
+          atomicAdd(&stats[STAT_TOUCHED_TOKENS], (unsigned long long)n);
         }
       }
-      if (threadIdx.x == 0) atomicAdd(&stats[2], (unsigned long long)n);
+      if (threadIdx.x == 0) atomicAdd(&stats[STAT_TOKENS], (unsigned long long)n);
     }
     __syncthreads();
     if (threadIdx.x == 0 && new_keys) atomicAdd(pt.n_keys, new_keys);

@@ -38,25 +38,24 @@ __device__ inline void global_emit(const PairTable &pt, const DeltaBuf &db, unsi
 
 // Per-workgroup statistics.  A launch of >= 1024 workgroups that each bump the same global counters serialises at
 // ~11 ns per atomic (measured: +10 us per launch at 1024 workgroups, +47 us at 4096), a floor under every short kernel of
-// a late round.  So workgroup b adds to its own row stats[BLK_BASE + 8 b + j] with plain stores (launches on the stream
-// are serial), and one workgroup folds the rows into the totals when somebody needs them (fold_blk_stats).
-constexpr int BLK_BASE = 32, BLK_ROWS = 1536;  // >= the largest grid of k_filter / k_tiles<.., true>  // j: 0..3 = the K4 counters, 4 = pair-table slots claimed
+// a late round.  So workgroup b adds to its own row stats[blk_at(b, j)] (yttm_kernels.h: the K4 counters under their own numbers, BLK_NEW_KEYS)
+// with plain stores (launches on the stream are serial), and one workgroup folds the rows into the totals when somebody needs them (fold_blk_stats).
 __device__ inline void blk_add(unsigned long long *stats, int j, unsigned long long v) {
   // (the row is this workgroup's alone, and the round's tail may read it from another XCD before any cache write-back -- see round_tail --
   // so the update must leave the XCD: an atomic add, which on a line nobody else touches costs what a write-through store does)
-  unsigned long long *p = &stats[BLK_BASE + 8 * (blockIdx.x % BLK_ROWS) + j];
+  unsigned long long *p = &stats[blk_at(blockIdx.x % BLK_ROWS, j)];
   if (v) atomicAdd(p, v);
 }
-// called by ONE workgroup of 256 threads, all threads; ends with the totals in stats[0..3] and *n_keys
+// called by ONE workgroup of 256 threads, all threads; ends with the totals in stats[STAT_SITES .. STAT_TOUCHED_TOKENS] and *n_keys
 __device__ inline void fold_blk_stats(unsigned long long *stats, unsigned int *n_keys) {
   __shared__ unsigned long long fold_acc[5];
   if (threadIdx.x < 5) fold_acc[threadIdx.x] = 0;
   __syncthreads();
   unsigned long long a[5] = {0, 0, 0, 0, 0};
   for (int b = (int)threadIdx.x; b < BLK_ROWS; b += (int)blockDim.x) {
-    unsigned long long *row = stats + BLK_BASE + 8 * b;  // written by earlier kernels: plain 16-byte loads
+    unsigned long long *row = stats + blk_at(b);  // written by earlier kernels: plain 16-byte loads
     const uint4 v01 = *reinterpret_cast<const uint4 *>(row), v23 = *reinterpret_cast<const uint4 *>(row + 2);
-    const unsigned long long v4 = row[4];
+    const unsigned long long v4 = row[BLK_NEW_KEYS];
     const unsigned long long v[5] = {((unsigned long long)v01.y << 32) | v01.x, ((unsigned long long)v01.w << 32) | v01.z,
                                      ((unsigned long long)v23.y << 32) | v23.x, ((unsigned long long)v23.w << 32) | v23.z, v4};
     bool any = false;
@@ -69,7 +68,7 @@ __device__ inline void fold_blk_stats(unsigned long long *stats, unsigned int *n
       const uint4 z{0u, 0u, 0u, 0u};
       *reinterpret_cast<uint4 *>(row) = z;
       *reinterpret_cast<uint4 *>(row + 2) = z;
-      row[4] = 0;
+      row[BLK_NEW_KEYS] = 0;
     }
   }
 #pragma unroll
@@ -102,15 +101,18 @@ struct RuleProbe {
 // ------------------------------------------------------------------------------------------------- multi-GPU pieces of a round
 // What the fold of this round's exchange left in xstat (yttm_kernels.h: XSTAT_WORDS) goes to the host with the scan's result: the verdict
 // words [0..3] are consumed (zeroed), the sums [4..7] stay.  Called with k = 0 .. 7 by eight threads; xstat == nullptr: zeros (single GPU).
-__device__ inline void xstat_forward(unsigned char *mailbox, unsigned long long *__restrict__ xstat, int k) {
+__device__ inline void xstat_forward(RoundMailbox *mailbox, unsigned long long *__restrict__ xstat, int k) {
   if (k < 0 || k >= XSTAT_WORDS || (!xstat && k >= 4)) return;
   unsigned long long v = 0;
   if (xstat) {
     v = ld_agent(&xstat[k]);
     if (k < 4) xstat[k] = 0;
   }
-  if (k < 4) *reinterpret_cast<unsigned long long *>(mailbox + 56 + 8 * k) = v;
-  else *reinterpret_cast<unsigned long long *>(mailbox + MB_XSUM + 8 * (k - 4)) = v;
+  // xverdict[k] / xsum[k - 4], addressed by a 32-bit byte offset from the mailbox: as array accesses with a lane's own index they take a 64-bit
+  // address computation per lane, and the device code is held to what it was (profiles/round_protocol_isa_diff.txt)
+  unsigned char *const mb = reinterpret_cast<unsigned char *>(mailbox);
+  if (k < 4) *reinterpret_cast<unsigned long long *>(mb + offsetof(RoundMailbox, xverdict) + 8 * k) = v;
+  else *reinterpret_cast<unsigned long long *>(mb + offsetof(RoundMailbox, xsum) + 8 * (k - 4)) = v;
 }
 
 // ------------------------------------------------------------------------------------------------- fused candidate scan
@@ -163,9 +165,7 @@ __device__ inline int cand_bin(unsigned long long c) {
 //      hold the same pairs on every rank (k_fold_list), so no verdict on them has to be exchanged first; `xstat` (the fold's report on
 //      the exchange itself) rides along.
 //   3. last, off the critical path: the per-workgroup statistics rows are folded into the totals and the key count
-// Box layout: [0] candidates, [4] keys in the table, [8] top-list entries before the scan, [12] of those still >= top_tau,
-// [16] hot-list entries (overflow check), [24] the round's duration on the device (ScanArgs::timed), [88] merge sites so far, [32] round id, [40] tokens streamed so far, [48] tiles with a site so far, [56..87]
-// xstat verdicts (multi-GPU; the sums at MB_XSUM), [96..127] timing marks (100 MHz), [MB_HIST..) histogram, [8192..) candidates.
+// The box is a RoundMailbox (yttm_kernels.h).
 // lds = at least (CAND_BINS + 160) words of scratch (the apply kernel's tile buffers are free by now).
 template <int NT>
 __device__ inline void scan_top(const PairTable &pt, const ScanArgs &sa, unsigned long long *__restrict__ stats, const RuleProbe &zprobe,
@@ -189,7 +189,7 @@ __device__ inline void scan_top(const PairTable &pt, const ScanArgs &sa, unsigne
   const unsigned int hot_raw = __hip_atomic_load(pt.hot_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const bool overflow = tn_raw > pt.top_cap;  // entries were dropped: the host refills the list, nothing to scan
   const unsigned int tn = overflow ? 0u : tn_raw;
-  uint4 *box_out = reinterpret_cast<uint4 *>(sa.mailbox + 8192);
+  uint4 *box_out = reinterpret_cast<uint4 *>(sa.mailbox->cand);
   constexpr int TAIL_E = 8;
   unsigned int my_live = 0;
   unsigned int pass = 0;  // (ctl[4 + ((pass - 1) & 1)] = entries kept by the passes before this one; 0 for the first)
@@ -200,7 +200,7 @@ __device__ inline void scan_top(const PairTable &pt, const ScanArgs &sa, unsigne
   // refined count (a complete prefix of the order, as the host needs; it reads the threshold back as the smallest count it got).
   const bool refine = sa.want != 0 && tn != 0 && tn <= (unsigned int)(NT * TAIL_E);
 #if defined(YTTM_K4_PROF) && defined(__HIP_DEVICE_COMPILE__)
-  // tuning build: where the scan's time goes (100 MHz ticks, summed over the rounds into stats[24..30]; YTTM_TRACE prints them)
+  // tuning build: where the scan's time goes (100 MHz ticks, summed over the rounds into stats[STAT_TAIL ..]; YTTM_TRACE prints them)
   unsigned long long tq_[7];
 #define TAIL_MARK(i) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); tq_[i] = (unsigned long long)wall_clock64(); } while (0)
   TAIL_MARK(0);
@@ -371,38 +371,36 @@ __device__ inline void scan_top(const PairTable &pt, const ScanArgs &sa, unsigne
 #if defined(YTTM_K4_PROF) && defined(__HIP_DEVICE_COMPILE__)
   TAIL_MARK(6);
   if (tid == 0 && tn != 0) {
-    stats[24] += tq_[0] - tm1;  // list lengths
-    for (int i = 1; i < 7; i++) stats[24 + i] += tq_[i] - tq_[i - 1];  // slots | keys + counts | keep / zero / histogram | refine | emit | compaction + the later passes
-    stats[31] += 1;
+    stats[STAT_TAIL] += tq_[0] - tm1;  // list lengths
+    for (int i = 1; i < 7; i++) stats[STAT_TAIL + i] += tq_[i] - tq_[i - 1];  // slots | keys + counts | keep / zero / histogram | refine | emit | compaction + the later passes
+    stats[STAT_TAIL_SCANS] += 1;
   }
 #endif
   // ---- 3. publish
   const unsigned long long tm2 = (unsigned long long)wall_clock64();
-  unsigned int *hdr = reinterpret_cast<unsigned int *>(sa.mailbox);
-  unsigned long long *box_hist = reinterpret_cast<unsigned long long *>(sa.mailbox + MB_HIST);
+  RoundMailbox *const box = sa.mailbox;
   if (tid == 0) {
-    hdr[0] = ctl[1];
-    hdr[1] = __hip_atomic_load(pt.n_keys, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    hdr[2] = tn_raw;
-    hdr[3] = ctl[2];
-    hdr[4] = hot_raw;
-    hdr[5] = ctl[3];  // the host reads the histogram from here down (every line of the pinned mailbox it touches is a cache miss)
-    *reinterpret_cast<unsigned long long *>(sa.mailbox + 88) = stats[0];  // merge sites so far (word-mode switch)
-    *reinterpret_cast<unsigned long long *>(sa.mailbox + 24) = sa.timed ? (unsigned long long)wall_clock64() - ld_agent(&stats[STAT_T0]) : 0ull;  // the round on the device
-    *reinterpret_cast<unsigned long long *>(sa.mailbox + 40) = stats[2];  // tokens streamed so far (repack trigger)
-    *reinterpret_cast<unsigned long long *>(sa.mailbox + 48) = stats[1];  // tiles that held a merge site so far
+    box->n_cand = ctl[1];
+    box->n_keys = __hip_atomic_load(pt.n_keys, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    box->listed = tn_raw;
+    box->live = ctl[2];
+    box->hot_listed = hot_raw;
+    box->top_bin = ctl[3];  // the host reads the histogram from here down (every line of the pinned mailbox it touches is a cache miss)
+    box->sites_cum = stats[STAT_SITES];  // merge sites so far (word-mode switch)
+    box->round_ticks = sa.timed ? (unsigned long long)wall_clock64() - ld_agent(&stats[STAT_T0]) : 0ull;  // the round on the device
+    box->tokens_cum = stats[STAT_TOKENS];  // tokens streamed so far (repack trigger)
+    box->touched_cum = stats[STAT_TOUCHED];  // tiles that held a merge site so far
     if (!overflow) *pt.top_n = ctl[kept_total_at];
     if (sa.done_ctr) *sa.done_ctr = 0;
-    unsigned long long *tmark = reinterpret_cast<unsigned long long *>(sa.mailbox + 96);
-    tmark[0] = tm0; tmark[1] = tm1; tmark[2] = tm2; tmark[3] = (unsigned long long)wall_clock64();
+    box->tail_marks[0] = tm0; box->tail_marks[1] = tm1; box->tail_marks[2] = tm2; box->tail_marks[3] = (unsigned long long)wall_clock64();
   }
-  xstat_forward(sa.mailbox, xstat, tid - 6);  // (multi-GPU: the exchange's report)
-  if (xstat && tid == 14) *reinterpret_cast<unsigned long long *>(sa.mailbox + MB_XSUM + 32) = sa.timed ? ld_agent(&stats[STAT_T1]) - ld_agent(&stats[STAT_T0]) : 0ull;
-  for (int b = tid; b < CAND_BINS; b += NT) box_hist[b] = (unsigned long long)lh[b];
+  xstat_forward(box, xstat, tid - 6);  // (multi-GPU: the exchange's report)
+  if (xstat && tid == 14) box->xsum[4] = sa.timed ? ld_agent(&stats[STAT_T1]) - ld_agent(&stats[STAT_T0]) : 0ull;
+  for (int b = tid; b < CAND_BINS; b += NT) box->hist[b] = (unsigned long long)lh[b];
   if (sa.round_id) {
     __threadfence_system();
     __syncthreads();
-    if (tid == 0) __hip_atomic_store(&hdr[8], sa.round_id, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (tid == 0) __hip_atomic_store(&box->round_id, sa.round_id, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   // ---- 4. the statistics rows, AFTER the host has its candidates: the fold is off the round's critical path (the key count
   // and the token totals in the header are therefore one round old; the host allows for that)
@@ -416,7 +414,7 @@ __device__ inline void scan_top(const PairTable &pt, const ScanArgs &sa, unsigne
         const int b = b0 + tid + r * NT;
 #pragma unroll
         for (int jj = 0; jj < 5; jj++)
-          v[r][jj] = b < BLK_ROWS ? __hip_atomic_load(&stats[BLK_BASE + 8 * b + jj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+          v[r][jj] = b < BLK_ROWS ? __hip_atomic_load(&stats[blk_at(b, jj)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
       }
 #pragma unroll
       for (int r = 0; r < RPT; r++) {
@@ -424,7 +422,7 @@ __device__ inline void scan_top(const PairTable &pt, const ScanArgs &sa, unsigne
 #pragma unroll
         for (int jj = 0; jj < 5; jj++) {
           // (taken by an exchange: an atomic on a line nobody else touches costs what a write-through store does)
-          if (v[r][jj]) a[jj] += atomicExch(&stats[BLK_BASE + 8 * b + jj], 0ull);
+          if (v[r][jj]) a[jj] += atomicExch(&stats[blk_at(b, jj)], 0ull);
         }
       }
     }

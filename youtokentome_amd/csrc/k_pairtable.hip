@@ -57,28 +57,25 @@ __global__ __launch_bounds__(BLOCK) void k_cand_scan(PairTable pt, unsigned long
 
 // One workgroup copies header, histogram and the first `fast` candidates of a finished candidate scan into the host's pinned
 // mailbox, publishes `round_id` there (system-scope release) and clears the device-side counters for the next call: the host
-// polls the mailbox instead of paying a copy + stream synchronisation every round.  Mailbox: [0..15] n_out[0..3], [32] round
-// id, [40] tokens streamed so far, [48] tiles touched so far, [56..79] xstat (multi-GPU: ranks whose delta block overflowed,
-// largest record count of a rank this round, number of ranks whose hot list overflowed, "a rank's send buffer overflowed"),
-// histogram at byte MB_HIST = 128, candidates at byte 8192.
+// polls the mailbox instead of paying a copy + stream synchronisation every round.  n_out[0..3] become the mailbox's n_cand, n_keys,
+// listed, live (yttm_kernels.h: RoundMailbox).
 __device__ inline void publish_round(const PairTable &pt, CandRec *__restrict__ out, unsigned int cap, unsigned int *__restrict__ n_out,
-                                     unsigned long long *__restrict__ hist, unsigned int *__restrict__ done_ctr, unsigned char *__restrict__ mailbox,
+                                     unsigned long long *__restrict__ hist, unsigned int *__restrict__ done_ctr, RoundMailbox *__restrict__ mailbox,
                                      unsigned int fast, uint32_t round_id, unsigned long long *__restrict__ stats,
                                      unsigned long long *__restrict__ xstat) {
   if (threadIdx.x == 0) n_out[1] = __hip_atomic_load(pt.n_keys, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();
   const unsigned int n = __hip_atomic_load(&n_out[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  unsigned int *mb_hdr = reinterpret_cast<unsigned int *>(mailbox);
-  unsigned long long *mb_hist = reinterpret_cast<unsigned long long *>(mailbox + MB_HIST);
-  uint4 *mb_out = reinterpret_cast<uint4 *>(mailbox + 8192);
-  if (threadIdx.x < 4) mb_hdr[threadIdx.x] = __hip_atomic_load(&n_out[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  static_assert(offsetof(RoundMailbox, live) == offsetof(RoundMailbox, n_cand) + 12, "n_cand, n_keys, listed, live: the four words of n_out");
+  uint4 *mb_out = reinterpret_cast<uint4 *>(mailbox->cand);
+  if (threadIdx.x < 4) (&mailbox->n_cand)[threadIdx.x] = __hip_atomic_load(&n_out[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (threadIdx.x == 4)  // tokens streamed by the K4 filters so far: the host derives the tiles' fill from it (repack trigger)
-    *reinterpret_cast<unsigned long long *>(mailbox + 40) = __hip_atomic_load(&stats[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    mailbox->tokens_cum = __hip_atomic_load(&stats[STAT_TOKENS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (threadIdx.x == 5)  // tiles that held a merge site so far: a dense round skips the filter's exact rule test
-    *reinterpret_cast<unsigned long long *>(mailbox + 48) = __hip_atomic_load(&stats[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    mailbox->touched_cum = __hip_atomic_load(&stats[STAT_TOUCHED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   xstat_forward(mailbox, xstat, (int)threadIdx.x - 6);
   for (int b = (int)threadIdx.x; b < CAND_BINS; b += BLOCK) {
-    mb_hist[b] = __hip_atomic_load(&hist[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    mailbox->hist[b] = __hip_atomic_load(&hist[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     hist[b] = 0;
   }
   unsigned int take = n < cap ? n : cap;
@@ -96,7 +93,7 @@ __device__ inline void publish_round(const PairTable &pt, CandRec *__restrict__ 
   if (threadIdx.x == 0) {
     n_out[0] = n_out[1] = n_out[2] = n_out[3] = 0;
     *done_ctr = 0;
-    __hip_atomic_store(&mb_hdr[8], round_id, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&mailbox->round_id, round_id, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -108,7 +105,7 @@ __device__ inline void publish_round(const PairTable &pt, CandRec *__restrict__ 
 // polls the mailbox instead of paying a copy + stream synchronisation every round.
 __global__ __launch_bounds__(BLOCK) void k_hot_scan(PairTable pt, unsigned long long tau_cnt, uint32_t tau_mx, CandRec *__restrict__ out,
                                                     unsigned int cap, unsigned int *__restrict__ n_out, unsigned long long *__restrict__ hist,
-                                                    unsigned int *__restrict__ done_ctr, unsigned char *__restrict__ mailbox, unsigned int fast,
+                                                    unsigned int *__restrict__ done_ctr, RoundMailbox *__restrict__ mailbox, unsigned int fast,
                                                     uint32_t round_id, unsigned long long *__restrict__ stats, const RuleSlot *__restrict__ zrules,
                                                     unsigned int zmask, unsigned long long zself, BatchArgs zba,
                                                     unsigned long long *__restrict__ xstat /* multi-GPU: the exchange's report, forwarded */) {
@@ -146,8 +143,8 @@ __global__ __launch_bounds__(BLOCK) void k_hot_scan(PairTable pt, unsigned long 
       unsigned long long v[5] = {0, 0, 0, 0, 0};
       const int b = (int)blockIdx.x * per + (int)threadIdx.x;
       if ((int)threadIdx.x < per && b < BLK_ROWS) {
-        unsigned long long *row = stats + BLK_BASE + 8 * b;
-        for (int j = 0; j < 5; j++) {
+        unsigned long long *row = stats + blk_at(b);
+        for (int j = 0; j < 5; j++) {  // (columns STAT_SITES .. STAT_TOUCHED_TOKENS, BLK_NEW_KEYS)
           v[j] = row[j];
           if (v[j]) row[j] = 0;
         }
@@ -371,8 +368,8 @@ __global__ __launch_bounds__(BLOCK) void k_dt_clean(DeltaBuf db, DeltaRec *__res
   if (!is_last || threadIdx.x != 0) return;
   other[0].key = 0;
   other[0].delta = (long long)db.send_cap;
-  other[1].key = stats ? ld_agent(&stats[0]) : 0ull;                 // merge sites so far (folded by the scans: a round or two old)
-  other[1].delta = (long long)(stats ? ld_agent(&stats[2]) : 0ull);  // tokens streamed so far
+  other[1].key = stats ? ld_agent(&stats[STAT_SITES]) : 0ull;                 // merge sites so far (folded by the scans: a round or two old)
+  other[1].delta = (long long)(stats ? ld_agent(&stats[STAT_TOKENS]) : 0ull);  // tokens streamed so far
   other[2].key = tiles_a;
   other[2].delta = 0;
   other[3].key = 0;
@@ -559,17 +556,14 @@ void launch_cand_scan(const PairTable &pt, unsigned long long tau_cnt, uint32_t 
   if (b > 256 * 16) b = 256 * 16;
   hipLaunchKernelGGL(k_cand_scan, dim3((unsigned int)b), dim3(BLOCK), 0, st, pt, tau_cnt, tau_mx, out, cap, n_out, hist);
 }
-void launch_hot_scan(const PairTable &pt, unsigned long long tau_cnt, uint32_t tau_mx, CandRec *out, unsigned int cap, unsigned int *n_out,
-                     unsigned long long *hist, unsigned int *done_ctr, unsigned char *mailbox, unsigned int fast, uint32_t round_id,
-                     unsigned long long *stats, const RuleSlot *zrules, unsigned int zmask, unsigned long long zself, unsigned int listed_hint,
-                     const BatchArgs *zba, unsigned long long *xstat, hipStream_t st) {
+void launch_hot_scan(const HotScan &h, hipStream_t st) {
   // one entry per thread; every workgroup costs ~11 ns of serialised ticket/total atomics at the end, so no more of them
   // than the list needs (the statistics rows need >= BLK_ROWS / 64 = 24)
-  unsigned int g = (listed_hint + BLOCK - 1) / BLOCK;
+  unsigned int g = (h.listed_hint + BLOCK - 1) / BLOCK;
   if (g < 32) g = 32;
   if (g > 256) g = 256;
-  hipLaunchKernelGGL(k_hot_scan, dim3(g), dim3(BLOCK), 0, st, pt, tau_cnt, tau_mx, out, cap, n_out, hist, done_ctr, mailbox, fast, round_id,
-                     stats, zrules, zmask, zself, zba ? *zba : BatchArgs{}, xstat);
+  hipLaunchKernelGGL(k_hot_scan, dim3(g), dim3(BLOCK), 0, st, h.pt, h.sa.tau_cnt, h.sa.tau_mx, h.sa.out, h.sa.cap, h.n_out, h.hist, h.sa.done_ctr, h.sa.mailbox, h.sa.fast,
+                     h.sa.round_id, h.stats, h.zero.rules, h.zero.mask, h.zero.self_key, h.zero.ba ? *h.zero.ba : BatchArgs{}, h.xstat);
 }
 void launch_dt_clean(const DeltaBuf &db, DeltaRec *other, unsigned int n_hint, unsigned long long *stats, uint32_t tiles_a, unsigned int *done_ctr, hipStream_t st) {
   unsigned int g = (n_hint + BLOCK - 1) / BLOCK;
@@ -589,14 +583,12 @@ void launch_pt_apply_blocks(const PairTable &pt, const DeltaRec *blocks, unsigne
   hipLaunchKernelGGL(k_pt_apply_blocks, dim3((unsigned int)b), dim3(BLOCK), 0, st, pt, blocks, blk, world, rank, only_mask, xstat, stats);
 }
 void launch_fold_list(const PairTable &pt, const DeltaRec *blocks, unsigned long long blk, int world, unsigned long long only_mask, const ScanArgs *scan,
-                      unsigned long long *stats, const RuleSlot *zrules, unsigned int zmask, unsigned long long zself, const BatchArgs *zba,
-                      unsigned long long *xstat, bool read_headers, hipStream_t st) {
-  hipLaunchKernelGGL(k_fold_list, dim3(1), dim3(FOLD_NT), 0, st, pt, blocks, blk, world, only_mask, scan ? *scan : ScanArgs{}, stats, zrules, zmask, zself,
-                     zba ? *zba : BatchArgs{}, xstat, read_headers ? 1 : 0);
+                      unsigned long long *stats, const ZeroBatch &zero, unsigned long long *xstat, bool read_headers, hipStream_t st) {
+  hipLaunchKernelGGL(k_fold_list, dim3(1), dim3(FOLD_NT), 0, st, pt, blocks, blk, world, only_mask, scan ? *scan : ScanArgs{}, stats, zero.rules, zero.mask, zero.self_key,
+                     zero.ba ? *zero.ba : BatchArgs{}, xstat, read_headers ? 1 : 0);
 }
-void launch_top_scan(const PairTable &pt, const ScanArgs &sa, unsigned long long *stats, const RuleSlot *zrules, unsigned int zmask, unsigned long long zself,
-                     const BatchArgs *zba, unsigned long long *xstat, hipStream_t st) {
-  hipLaunchKernelGGL(k_top_scan, dim3(1), dim3(TOP_SCAN_NT), 0, st, pt, sa, stats, zrules, zmask, zself, zba ? *zba : BatchArgs{}, xstat);
+void launch_top_scan(const PairTable &pt, const ScanArgs &sa, unsigned long long *stats, const ZeroBatch &zero, unsigned long long *xstat, hipStream_t st) {
+  hipLaunchKernelGGL(k_top_scan, dim3(1), dim3(TOP_SCAN_NT), 0, st, pt, sa, stats, zero.rules, zero.mask, zero.self_key, zero.ba ? *zero.ba : BatchArgs{}, xstat);
 }
 void launch_top_rebuild(const PairTable &pt, unsigned int listed_hint, hipStream_t st) {
   unsigned int g = (listed_hint + BLOCK - 1) / BLOCK;

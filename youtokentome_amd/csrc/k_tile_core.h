@@ -138,7 +138,7 @@ __device__ inline void agg_init(AggLds &A, const uint32_t *__restrict__ flagbits
     for (int s = (int)threadIdx.x; s < (int)(FLAG_LDS_IDS / 16); s += NT) A.flagbits[s] = flagbits_g[s];
   if (threadIdx.x == 0) {
     A.new_keys = 0;
-    A.st[0] = A.st[1] = A.st[2] = A.st[3] = A.st[4] = A.st[5] = 0;
+    A.st[STAT_SITES] = A.st[STAT_TOUCHED] = A.st[STAT_TOKENS] = A.st[STAT_TOUCHED_TOKENS] = A.st[STAT_INSTR_WORDS] = A.st[STAT_INSTR_TOKENS] = 0;
 #ifdef YTTM_K4_PROF
     A.miss_n = A.miss_cyc = 0;
 #endif

@@ -212,12 +212,12 @@ __global__ __launch_bounds__(WPB * 64, SLOT == TILE_SLOT_B ? 1 : MERGE ? (WPB ==
   if (MERGE) {
     S.sites = wave_sum_u64(S.sites);
     if (lane == 0) {
-      if (S.sites) atomicAdd(&A.st[0], S.sites);
-      if (S.touched) atomicAdd(&A.st[1], S.touched);
-      if (S.scanned && !worklist) atomicAdd(&A.st[2], S.scanned);
-      if (S.touched_tok) atomicAdd(&A.st[3], S.touched_tok);
-      if (S.words_hit) atomicAdd(&A.st[4], S.words_hit);
-      if (S.words_hit_tok) atomicAdd(&A.st[5], S.words_hit_tok);
+      if (S.sites) atomicAdd(&A.st[STAT_SITES], S.sites);
+      if (S.touched) atomicAdd(&A.st[STAT_TOUCHED], S.touched);
+      if (S.scanned && !worklist) atomicAdd(&A.st[STAT_TOKENS], S.scanned);
+      if (S.touched_tok) atomicAdd(&A.st[STAT_TOUCHED_TOKENS], S.touched_tok);
+      if (S.words_hit) atomicAdd(&A.st[STAT_INSTR_WORDS], S.words_hit);
+      if (S.words_hit_tok) atomicAdd(&A.st[STAT_INSTR_TOKENS], S.words_hit_tok);
     }
   }
 #ifdef YTTM_K4_PROF
@@ -240,28 +240,28 @@ __global__ __launch_bounds__(WPB * 64, SLOT == TILE_SLOT_B ? 1 : MERGE ? (WPB ==
     K4_MARK(12);  // flush
     if (lane == 0)
       for (int i = 0; i < 16; i++)
-        if (S.pt[i]) atomicAdd(&stats[8 + i], S.pt[i]);
+        if (S.pt[i]) atomicAdd(&stats[STAT_PROF + i], S.pt[i]);
     if (threadIdx.x == 0 && A.miss_n) {  // emits that found no room in the workgroup's LDS hash (they went to the HBM table one by one)
-      atomicAdd(&stats[8 + 14], A.miss_n);
-      atomicAdd(&stats[8 + 15], A.miss_cyc);
+      atomicAdd(&stats[STAT_PROF_MISS_N], A.miss_n);
+      atomicAdd(&stats[STAT_PROF_MISS_CYC], A.miss_cyc);
     }
   }
 #endif
 #ifdef YTTM_K4_PROF
   if (MERGE && threadIdx.x == 0) {  // per-workgroup timeline (100 MHz wall clock) for YTTM_TRACE_ROUNDS
-    unsigned long long *row = stats + BLK_BASE + 8 * (blockIdx.x % BLK_ROWS);
-    row[5] = wall0_;
-    row[6] = wall_clock64();
-    row[7] = A.st[1];
+    unsigned long long *row = stats + blk_at(blockIdx.x % BLK_ROWS);
+    row[BLK_PROF_T0] = wall0_;
+    row[BLK_PROF_T1] = wall_clock64();
+    row[BLK_PROF_AUX] = A.st[STAT_TOUCHED];
   }
 #endif
   if (threadIdx.x == 0) {
     if (MERGE) {
-      blk_add(stats, 4, A.new_keys);
+      blk_add(stats, BLK_NEW_KEYS, A.new_keys);
       for (int i = 0; i < 4; i++) blk_add(stats, i, A.st[i]);
       if (ba.instr) {  // (measurement pass: plain global atomics)
-        if (A.st[4]) atomicAdd(&stats[4], A.st[4]);
-        if (A.st[5]) atomicAdd(&stats[5], A.st[5]);
+        if (A.st[STAT_INSTR_WORDS]) atomicAdd(&stats[STAT_INSTR_WORDS], A.st[STAT_INSTR_WORDS]);
+        if (A.st[STAT_INSTR_TOKENS]) atomicAdd(&stats[STAT_INSTR_TOKENS], A.st[STAT_INSTR_TOKENS]);
       }
     } else if (A.new_keys) {
       atomicAdd(pt.n_keys, A.new_keys);  // K3: one launch
@@ -540,7 +540,7 @@ void launch_pair_count(int cls, const TileSet &ts, const PairTable &pt, const De
 }
 void launch_merge_apply(int cls, const TileSet &ts, const PairTable &pt, const DeltaBuf &db, const RuleSlot *rules, unsigned int rule_mask,
                         uint32_t self_x, uint32_t self_z, uint32_t z_base, unsigned long long *stats, const BatchArgs *ba, const ScanArgs *scan,
-                        const uint32_t *bloom_g, hipStream_t st) {
+                        const uint32_t *bloom_g, unsigned int apply_grid, hipStream_t st) {
   if (!ts.n_tiles) return;
   const BatchArgs bargs = ba ? *ba : BatchArgs{};
   const ScanArgs sargs = scan ? *scan : ScanArgs{};  // (the caller hands the scan to the round's LAST launch)
@@ -549,12 +549,9 @@ void launch_merge_apply(int cls, const TileSet &ts, const PairTable &pt, const D
   // index: class A leaves the tiles for word mode before either could pay).
   // class-A grid: APPLY_BPC workgroups per CU when there are tiles for all of them; a small tile set (natural-language corpora:
   // a few thousand tiles) gets fewer workgroups with several tiles per wave -- every workgroup costs a prologue (44 KB of LDS set-up)
-  // and a serialised ticket at the end (~11 ns each), which a round of ~15 us notices.  YTTM_APPLY_GRID overrides (tuning hook).
+  // and a serialised ticket at the end (~11 ns each), which a round of ~15 us notices.  apply_grid is that cap (YTTM_APPLY_GRID, tuning hook).
   unsigned int grid_a = tile_grid(ts.n_tiles, APPLY_WPB, APPLY_BPC);
-  {
-    const unsigned int small = (unsigned int)g_apply_grid;  // (YTTM_APPLY_GRID, read by launch_env_refresh when the context was made)
-    if (ts.n_tiles <= 16384 && small && grid_a > small) grid_a = small;
-  }
+  if (ts.n_tiles <= 16384 && apply_grid && grid_a > apply_grid) grid_a = apply_grid;
   const uint8_t *no_flags = nullptr;
   const uint32_t *no_list = nullptr;
   const unsigned int *no_n = nullptr;

@@ -730,9 +730,9 @@ __global__ __launch_bounds__(WPB * 64) void k_words(WordSet ws, PairTable pt, De
   {
     S.sites = wave_sum_u64(S.sites);
     if (lane == 0) {
-      if (S.sites) atomicAdd(&A.st[0], S.sites);
-      if (S.touched) atomicAdd(&A.st[1], S.touched);
-      if (S.touched_tok) atomicAdd(&A.st[3], S.touched_tok);
+      if (S.sites) atomicAdd(&A.st[STAT_SITES], S.sites);
+      if (S.touched) atomicAdd(&A.st[STAT_TOUCHED], S.touched);
+      if (S.touched_tok) atomicAdd(&A.st[STAT_TOUCHED_TOKENS], S.touched_tok);
     }
   }
 #ifdef YTTM_K4_PROF
@@ -801,15 +801,15 @@ __global__ __launch_bounds__(WPB * 64) void k_words(WordSet ws, PairTable pt, De
   K4_MARK(10);  // (record flush)
   if (lane == 0)
     for (int i = 0; i < 16; i++)
-      if (S.pt[i]) atomicAdd(&stats[8 + i], S.pt[i]);
+      if (S.pt[i]) atomicAdd(&stats[STAT_PROF + i], S.pt[i]);
   if (threadIdx.x == 0 && A.miss_n) {
-    atomicAdd(&stats[8 + 14], A.miss_n);
-    atomicAdd(&stats[8 + 15], A.miss_cyc);
+    atomicAdd(&stats[STAT_PROF_MISS_N], A.miss_n);
+    atomicAdd(&stats[STAT_PROF_MISS_CYC], A.miss_cyc);
   }
 #endif
   if (!inline_apply) {  // the usual way: k_delta_apply takes the records from here (and runs the round's candidate scan)
     if (threadIdx.x == 0) {
-      blk_add(stats, 4, A.new_keys);
+      blk_add(stats, BLK_NEW_KEYS, A.new_keys);
       for (int i = 0; i < 4; i++) blk_add(stats, i, A.st[i]);
       drec_n[blockIdx.x] = dn < drec_cap ? dn : drec_cap;
     }
@@ -825,18 +825,18 @@ __global__ __launch_bounds__(WPB * 64) void k_words(WordSet ws, PairTable pt, De
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-      blk_add(stats, 4, A.new_keys);
+      blk_add(stats, BLK_NEW_KEYS, A.new_keys);
       for (int i = 0; i < 4; i++) blk_add(stats, i, A.st[i]);
     }
   }
 #ifdef YTTM_K4_PROF
   if (threadIdx.x == 0) {
-    unsigned long long *row = stats + BLK_BASE + 8 * (blockIdx.x % BLK_ROWS);
-    row[5] = wall0_;
-    // (set-up marks: word 5 of row 512 + b -- k_words runs at most 512 workgroups, the rows behind are nobody's in a word-mode round)
-    stats[BLK_BASE + 8 * (512 + blockIdx.x % 512) + 5] = ((wall_m1_ - wall0_) & 0xffffull) | (((wall_m2_ - wall0_) & 0xffffull) << 16) | (((wall_m3_ - wall0_) & 0xffffull) << 32);
-    row[6] = ((wall_setup_ - wall0_) & 0xffffffffull) | ((wall_words_ - wall0_) << 32);
-    row[7] = ((wall_clock64() - wall0_) & 0xffffffffull) | ((unsigned long long)A.st[1] << 32);
+    unsigned long long *row = stats + blk_at(blockIdx.x % BLK_ROWS);
+    row[BLK_PROF_T0] = wall0_;
+    // (set-up marks: the same word of row 512 + b -- k_words runs at most 512 workgroups, the rows behind are nobody's in a word-mode round)
+    stats[blk_at(512 + blockIdx.x % 512, BLK_PROF_T0)] = ((wall_m1_ - wall0_) & 0xffffull) | (((wall_m2_ - wall0_) & 0xffffull) << 16) | (((wall_m3_ - wall0_) & 0xffffull) << 32);
+    row[BLK_PROF_T1] = ((wall_setup_ - wall0_) & 0xffffffffull) | ((wall_words_ - wall0_) << 32);
+    row[BLK_PROF_AUX] = ((wall_clock64() - wall0_) & 0xffffffffull) | ((unsigned long long)A.st[STAT_TOUCHED] << 32);
   }
 #endif
   // (ordering: k_merge_shared.h "ORDERING OF A FUSED TAIL" -- P1: the inline apply above is atomics only, blk_add atomics; P2 here; C1 - C3 in the branch)
@@ -884,7 +884,7 @@ __global__ __launch_bounds__(DAPPLY_NT) void k_delta_apply(PairTable pt, DeltaBu
     global_emit(pt, db, rec.key, rec.delta, &new_keys);
   }
   __syncthreads();
-  if (threadIdx.x == 0) blk_add(stats, 4, new_keys);
+  if (threadIdx.x == 0) blk_add(stats, BLK_NEW_KEYS, new_keys);
   if (!sa.on) return;
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -924,75 +924,60 @@ void launch_words_init(const TileSet &ts, unsigned long long *wmeta, hipStream_t
   if (g > 256 * 8) g = 256 * 8;
   hipLaunchKernelGGL((k_words_init<TILE_SLOT_A>), dim3(g), dim3(BLOCK), 0, st, ts, wmeta);
 }
-// The grid hooks of the word-mode launchers (tests, tuning) are read when a context is made, not every round: getenv walks the whole
-// environment, and a round's launch is on its critical path (yttm_kernels.h: launch_env_refresh).
-static int g_wgather_grid = -1, g_words_grid = -1, g_words_wpi = -1;
-int g_apply_grid = 256;  // (k_tiles.hip: launch_merge_apply)
-void launch_env_refresh() {
-  const std::shared_ptr<const Config> C = cfg();
-  auto rd = [](const Hook &h) { return h.set && !h.raw.empty() ? (int)h.i : -1; };
-  g_wgather_grid = rd(C->wgather_grid);
-  g_words_grid = rd(C->words_grid);
-  g_words_wpi = rd(C->words_wpi);
-  g_apply_grid = (int)C->apply_grid.i;
-}
-void launch_wgather(const WGatherArgs &a, const BatchArgs *ba, unsigned int work_hint, hipStream_t st) {
+void launch_wgather(const WGatherArgs &a, const BatchArgs *ba, unsigned int work_hint, int grid, hipStream_t st) {
   // every workgroup looks all the rules up and takes a ticket at the end: a small round (work_hint = about how many words it will visit;
   // 0: unknown) gets a small grid
   unsigned int g = 256u;
   if (work_hint) g = std::max(16u, std::min(256u, work_hint / 1024u));
-  if (g_wgather_grid >= 0) g = (unsigned int)g_wgather_grid;
+  if (grid >= 0) g = (unsigned int)grid;
   hipLaunchKernelGGL(k_wgather, dim3(g ? g : 1u), dim3(WG_NT), 0, st, a, ba ? *ba : BatchArgs{});
 }
-bool launch_words_apply(const WordSet &ws, const PairTable &pt, const DeltaBuf &db, const RuleSlot *rules, unsigned int rule_mask, const uint32_t *bloom_g,
-                        uint32_t self_x, uint32_t self_z, uint32_t z_base, uint32_t k_rules, const uint32_t *worklist, unsigned long long wl_seg,
-                        const unsigned int *work_n, unsigned long long *stats, const TokLists &tl, DeltaRec *drec, unsigned int drec_cap, unsigned int *drec_n,
-                        uint4 *irec, const BatchArgs *ba, const ScanArgs *scan, unsigned int work_hint, unsigned int inline_max, const WGatherArgs *ga,
-                        unsigned int fuse_max, hipStream_t st, unsigned int avg_word_tokens) {
-  if (!ws.n_words) return false;
-  BatchArgs bargs = ba ? *ba : BatchArgs{};
-  ScanArgs sargs = scan ? *scan : ScanArgs{};
+bool launch_words_apply(const WordsRound &r, hipStream_t st) {
+  if (!r.ws.n_words) return false;
+  BatchArgs bargs = r.ba ? *r.ba : BatchArgs{};
+  ScanArgs sargs = r.scan ? *r.scan : ScanArgs{};
+  const WGatherArgs &ga = *r.ga;
+  const bool listed = ga.worklist && r.work_hint;  // the round visits the worklist's words, and about work_hint of them
   // the worklist first (k_wgather) -- unless the round is small enough for k_words to find its words itself (one launch a round)
-  const bool fused = ga && worklist && work_hint && work_hint <= fuse_max && sargs.on && bargs.k != 0 && !ga->xyz && rule_mask < APPLY_LDS_RULES;
+  const bool fused = listed && r.work_hint <= r.fuse_max && sargs.on && bargs.k != 0 && !ga.xyz && r.rule_mask < APPLY_LDS_RULES;
   if (fused && sargs.on == 2u) sargs.on = 3u;  // (multi-GPU: a fused round leaves no worklist behind -- there is no tail)
-  if (ga && !fused) launch_wgather(*ga, &bargs, work_hint, st);
+  if (!fused) launch_wgather(ga, &bargs, r.work_hint, r.wgather_grid, st);
   if (!fused) bargs.mark = 0u;  // (the round's first launch carries the mark)
   // one run of 64 words per wave and iteration; work_hint = about how many words the round will visit (0: unknown / every word)
-  const unsigned int gmax = std::min(g_words_grid >= 0 ? (unsigned int)g_words_grid : 512u, (unsigned int)WORDS_MAX_GRID);
+  const unsigned int gmax = std::min(r.words_grid >= 0 ? (unsigned int)r.words_grid : 512u, (unsigned int)WORDS_MAX_GRID);
   // words per wave: 64, or fewer when that would leave most of the chip idle (work_hint words over at most gmax workgroups)
   unsigned int wpi = 64;
-  if (worklist && work_hint) {
-    while (wpi > 8 && (unsigned long long)work_hint < (unsigned long long)wpi * APPLY_WPB * gmax / 2) wpi >>= 1;
+  if (listed) {
+    while (wpi > 8 && (unsigned long long)r.work_hint < (unsigned long long)wpi * APPLY_WPB * gmax / 2) wpi >>= 1;
     // Long words (round 6): a wave's LDS tile holds 512 tokens, and a work item whose words do not fit it takes a second (third ...) gather-and-merge
     // pass, one behind the other -- CJK-shaped text, clauses of ~41 tokens: 16 words per item were 656 tokens, two passes; 8 words per item, one
     // pass and twice the waves at work: merge loop 0.432 -> 0.385 s (profiles/r6_words_per_item.txt).
-    while (wpi > 4 && avg_word_tokens && (unsigned long long)wpi * avg_word_tokens > 600ull) wpi >>= 1;
-    if (g_words_wpi >= 0) wpi = (unsigned int)g_words_wpi;
+    while (wpi > 4 && r.avg_word_tokens && (unsigned long long)wpi * r.avg_word_tokens > 600ull) wpi >>= 1;
+    if (r.words_wpi >= 0) wpi = (unsigned int)r.words_wpi;
   }
-  unsigned long long items = worklist && work_hint ? ((unsigned long long)work_hint + wpi - 1) / wpi + 1 : ((unsigned long long)ws.n_words + 63) / 64;
+  unsigned long long items = listed ? ((unsigned long long)r.work_hint + wpi - 1) / wpi + 1 : ((unsigned long long)r.ws.n_words + 63) / 64;
   unsigned long long g = (items + APPLY_WPB - 1) / APPLY_WPB;
   if (g > gmax) g = gmax;
   if (g < 1) g = 1;
   // a small round applies its records itself and carries the candidate scan (it needs that scan: its last workgroup resets the worklist)
-  const bool inl = fused || (worklist && work_hint && work_hint <= inline_max && sargs.on);
+  const bool inl = fused || (listed && r.work_hint <= r.inline_max && sargs.on);
   const ScanArgs none{};
   const WGatherArgs gnone{};
-  if (fused)
-    hipLaunchKernelGGL((k_words<APPLY_WPB, true, true>), dim3((unsigned int)g), dim3(64 * APPLY_WPB), 0, st, ws, pt, db, rules, rule_mask, bloom_g, self_x, self_z, z_base,
-                       k_rules, worklist, wl_seg, work_n, stats, tl, drec, drec_cap, drec_n, irec, wpi, 1u, bargs, sargs, *ga);
-  else if (rule_mask < APPLY_LDS_RULES)
-    hipLaunchKernelGGL((k_words<APPLY_WPB, true, false>), dim3((unsigned int)g), dim3(64 * APPLY_WPB), 0, st, ws, pt, db, rules, rule_mask, bloom_g, self_x, self_z, z_base,
-                       k_rules, worklist, wl_seg, work_n, stats, tl, drec, drec_cap, drec_n, irec, wpi, inl ? 1u : 0u, bargs, inl ? sargs : none, gnone);
-  else
-    hipLaunchKernelGGL((k_words<APPLY_WPB, false, false>), dim3((unsigned int)g), dim3(64 * APPLY_WPB), 0, st, ws, pt, db, rules, rule_mask, bloom_g, self_x, self_z, z_base,
-                       k_rules, worklist, wl_seg, work_n, stats, tl, drec, drec_cap, drec_n, irec, wpi, inl ? 1u : 0u, bargs, inl ? sargs : none, gnone);
+#define YTTM_K_WORDS(LDSR, FUSED, inl_flag, scan_args, gather_args)                                                                                              \
+  hipLaunchKernelGGL((k_words<APPLY_WPB, LDSR, FUSED>), dim3((unsigned int)g), dim3(64 * APPLY_WPB), 0, st, r.ws, r.pt, r.db, r.rules, r.rule_mask, r.bloom_g, r.self_x, \
+                     r.self_z, ga.z_base, ga.k, ga.worklist, ga.wl_seg, ga.work_n, ga.stats, ga.tl, r.drec, r.drec_cap, r.drec_n, r.irec, wpi, inl_flag, bargs, scan_args, gather_args)
+  if (fused) YTTM_K_WORDS(true, true, 1u, sargs, ga);
+  else if (r.rule_mask < APPLY_LDS_RULES) YTTM_K_WORDS(true, false, inl ? 1u : 0u, inl ? sargs : none, gnone);
+  else YTTM_K_WORDS(false, false, inl ? 1u : 0u, inl ? sargs : none, gnone);
+#undef YTTM_K_WORDS
   if (inl) return fused;
   // the records -> the pair table, then the round's candidate scan (every workgroup owns a statistics row: at most BLK_ROWS of them)
   // (every workgroup takes a ticket at the end, ~12 ns each on one address: a small round gets a small grid)
-  const bool big = !worklist || !work_hint || work_hint > (1u << 17);
+  const bool big = !listed || r.work_hint > (1u << 17);
   const unsigned int parts = std::max(1u, std::min(8u, (big ? (unsigned int)BLK_ROWS : 256u) / (unsigned int)g));
-  hipLaunchKernelGGL(k_delta_apply, dim3((unsigned int)g * parts), dim3(DAPPLY_NT), 0, st, pt, db, (const DeltaRec *)drec, drec_cap, (const unsigned int *)drec_n, parts,
-                     const_cast<unsigned int *>(work_n), stats, bargs.k ? (const RuleSlot *)nullptr : rules, rule_mask, self_x != 0xffffffffu ? pair_key(self_x, self_x) : PT_EMPTY, bargs, sargs);
+  hipLaunchKernelGGL(k_delta_apply, dim3((unsigned int)g * parts), dim3(DAPPLY_NT), 0, st, r.pt, r.db, (const DeltaRec *)r.drec, r.drec_cap, (const unsigned int *)r.drec_n, parts,
+                     ga.work_n, ga.stats, bargs.k ? (const RuleSlot *)nullptr : r.rules, r.rule_mask,
+                     r.self_x != 0xffffffffu ? pair_key(r.self_x, r.self_x) : PT_EMPTY, bargs, sargs);
   return false;
 }
 }  // namespace yttm

@@ -1,6 +1,7 @@
 // yttm_kernels.h -- host-callable launchers of the gfx950 kernels (k_frontend.hip; k_tiles.hip, k_words.hip, k_index.hip, k_pairtable.hip, k_giant.hip; k_encode.hip, k_wcache.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "yttm_config.h"
@@ -14,6 +15,64 @@ struct CandRec {
   unsigned long long key;  // x<<32|y
   unsigned long long cnt;
 };
+constexpr unsigned int CAND_CAP = 1u << 20;  // candidates a scan can hand over (the read-back area behind the mailbox holds as many)
+constexpr unsigned int CAND_FAST = 4096;     // of those, the first ones travel through the mailbox itself; the rest by a copy of their own
+
+// The round's mailbox: what a candidate scan (scan_top in the tail of the round's last kernel, k_hot_scan's publish_round) writes into the
+// host's pinned block, and what the host reads when it has seen `round_id` (GpuCtx::poll_mailbox).  The device writes everything else first,
+// then __threadfence_system(), a barrier, and ONE system-scope release store of round_id; the host spins on that word (volatile) and issues
+// an acquire fence before it reads the rest (k_merge_shared.h, "ORDERING OF A FUSED TAIL").
+// `listed`: the length of the list the scan read, before it read it -- the TOP list after scan_top (k_top_scan, a fused tail, k_fold_list),
+// the HOT list after k_hot_scan; `live`: those of its entries still at or above the list's threshold.  `hot_listed` and `top_bin` are
+// written by scan_top only.
+struct RoundMailbox {
+  uint32_t n_cand;                     // candidates that passed (may exceed what was stored: CAND_CAP, and CAND_FAST of them here)
+  uint32_t n_keys;                     // keys in the pair table (scan_top: one round old, it folds the statistics after publishing)
+  uint32_t listed, live;
+  uint32_t hot_listed;                 // scan_top: hot-list entries (overflow check)
+  uint32_t top_bin;                    // scan_top: no histogram bin above this one is in use (every line of the pinned block the host touches is a cache miss)
+  unsigned long long round_ticks;      // scan_top: the round's duration on the device (ScanArgs::timed; 100 MHz ticks)
+  uint32_t round_id, pad0_;            // published last
+  unsigned long long tokens_cum;       // tokens the K4 kernels streamed so far (repack trigger)
+  unsigned long long touched_cum;      // tiles (word mode: words) that held a merge site so far
+  unsigned long long xverdict[4];      // multi-GPU, the fold's report on the round's exchange (XSTAT_WORDS: d_xstat[0..3]); zeros on a single GPU
+  unsigned long long sites_cum;        // scan_top: merge sites so far (word-mode switch)
+  unsigned long long tail_marks[4];    // scan_top's timing marks (100 MHz wall clock)
+  unsigned long long hist[CAND_BINS];  // histogram of the live counts
+  unsigned char pad1_[6144 - 128 - 8 * CAND_BINS];
+  unsigned long long xsum[5];          // multi-GPU, sums over the ranks' block headers (d_xstat[4..7]): [0] merge sites so far, [1] tokens streamed so far,
+                                       // [2] class-A tiles, [3] ranks; [4] the round's apply kernels on the device clock (ticks; ScanArgs::timed)
+  unsigned char pad2_[8192 - 6144 - 8 * 5];
+  CandRec cand[CAND_CAP];              // the first CAND_FAST by the device; the host copies the rest behind them when it wants more
+};
+#define YTTM_MB_AT(field, at) static_assert(offsetof(RoundMailbox, field) == at, "RoundMailbox::" #field " moved")
+YTTM_MB_AT(n_cand, 0); YTTM_MB_AT(n_keys, 4); YTTM_MB_AT(listed, 8); YTTM_MB_AT(live, 12); YTTM_MB_AT(hot_listed, 16); YTTM_MB_AT(top_bin, 20);
+YTTM_MB_AT(round_ticks, 24); YTTM_MB_AT(round_id, 32); YTTM_MB_AT(tokens_cum, 40); YTTM_MB_AT(touched_cum, 48); YTTM_MB_AT(xverdict, 56);
+YTTM_MB_AT(sites_cum, 88); YTTM_MB_AT(tail_marks, 96); YTTM_MB_AT(hist, 128); YTTM_MB_AT(xsum, 6144); YTTM_MB_AT(cand, 8192);
+#undef YTTM_MB_AT
+
+// The statistics block of the merge loop (d_stats, unsigned long long words): totals, then one row per workgroup.
+enum StatWord : int {
+  STAT_SITES = 0,          // merge sites
+  STAT_TOUCHED = 1,        // tiles (word mode: words) that held one
+  STAT_TOKENS = 2,         // tokens the K4 kernels streamed
+  STAT_TOUCHED_TOKENS = 3, // tokens of the tiles that held a site
+  STAT_INSTR_WORDS = 4,    // measurement pass (BatchArgs::instr): words that held a site ...
+  STAT_INSTR_TOKENS = 5,   // ... and their tokens
+  STAT_T0 = 6,             // wall_clock64() at the start of the round's first launch
+  STAT_T1 = 7,             // (multi-GPU) ... when the round's apply kernels and the all-gather behind them were done (noted by the fold's first kernel)
+  STAT_PROF = 8,           // [STAT_PROF_N] YTTM_K4_PROF build: per-phase cycles of the apply kernels; the last two: emits that found no room in LDS, their cycles
+  STAT_TAIL = 24,          // [STAT_TAIL_N] YTTM_K4_PROF build: scan_top's phases (100 MHz ticks, summed over the rounds); the last one: the scans counted
+  BLK_BASE = 32,           // workgroup b's row: the BLK_COLS words from stats[blk_at(b)] on
+};
+constexpr int STAT_PROF_N = 16, STAT_PROF_MISS_N = STAT_PROF + 14, STAT_PROF_MISS_CYC = STAT_PROF + 15, STAT_TAIL_N = 8, STAT_TAIL_SCANS = STAT_TAIL + 7;
+static_assert(STAT_PROF + STAT_PROF_N == STAT_TAIL && STAT_TAIL + STAT_TAIL_N == BLK_BASE, "the totals fill the words below the rows");
+constexpr int BLK_ROWS = 1536;  // >= the largest grid of k_tiles<.., true>
+// a row's columns: the K4 counters STAT_SITES .. STAT_TOUCHED_TOKENS under their own numbers, then
+enum BlkCol : int { BLK_NEW_KEYS = 4 /* pair-table slots claimed */, BLK_PROF_T0 = 5, BLK_PROF_T1 = 6, BLK_PROF_AUX = 7 /* YTTM_K4_PROF build: the workgroup's timeline */, BLK_COLS = 8 };
+template <class I>
+__host__ __device__ constexpr auto blk_at(I b, int col = 0) { return BLK_BASE + BLK_COLS * b + col; }  // index of a column of workgroup b's row
+constexpr int STATS_WORDS = BLK_BASE + BLK_COLS * BLK_ROWS;
 
 // lower bound of a candidate-histogram bin (inverse of cand_bin in k_merge_shared.h)
 inline unsigned long long cand_bin_lower(int bin) {
@@ -82,7 +141,7 @@ struct BatchArgs {
   uint32_t mark;                     // this is the round's first launch: workgroup 0 notes the time in stats[STAT_T0] (the round's duration then
                                      // comes from the device's own clock, ScanArgs::timed -- two hipEventRecord calls per round cost 4 us of host time)
   uint32_t instr;                    // measurement pass (never timed): also count the WORDS that hold a merge site and their tokens
-                                     // (T_touched, W_touched) into stats[4], stats[5]; single-site tiles take the general path
+                                     // (T_touched, W_touched) into stats[STAT_INSTR_WORDS], stats[STAT_INSTR_TOKENS]; single-site tiles take the general path
 };
 // The candidate scan that follows a merge round, done by the round's own apply kernel: the last workgroup to finish folds the
 // statistics rows, zeroes the batch's pairs, scans (and compacts) the hot list and publishes header + histogram + candidates
@@ -96,15 +155,22 @@ struct ScanArgs {
   CandRec *out;                // [cap] all candidates (the first `fast` also go to the mailbox)
   unsigned int cap, fast;
   unsigned int *done_ctr;      // ticket of finished workgroups (left at 0); nullptr: a single-workgroup launch
-  unsigned char *mailbox;      // the host's pinned mailbox, or (round_id == 0) a staging block in HBM with the same layout
+  RoundMailbox *mailbox;       // the host's pinned mailbox, or (round_id == 0) a staging block in HBM with the same layout
   uint32_t round_id;           // published in the mailbox when everything else is there; 0: nothing is published
   uint32_t want;               // != 0: about this many candidates are wanted -- the scan may raise the threshold by itself (scan_top: refine)
   uint32_t timed;              // the round's first launch left its start time in stats[STAT_T0]: the mailbox gets the duration (100 MHz ticks)
 };
-constexpr int STAT_T0 = 6;  // stats[6]: wall_clock64() at the start of the round's first launch
-constexpr int STAT_T1 = 7;  // stats[7] (multi-GPU): ... when the round's apply kernels and the all-gather behind them were done (noted by the fold's first kernel)
-void launch_top_scan(const PairTable &pt, const ScanArgs &sa, unsigned long long *stats, const RuleSlot *zrules, unsigned int zmask, unsigned long long zself,
-                     const BatchArgs *zba, unsigned long long *xstat /* multi-GPU: the exchange's report, forwarded to the mailbox */, hipStream_t st);
+// The batch whose pairs are still to be zeroed by the next scan of a candidate list (every occurrence was merged, so their counts are exactly
+// zero): its rule hash in HBM (rules, mask; self_key: its x == x rule, or PT_EMPTY), or -- a batch that travelled as a kernel argument -- ba.
+// Neither: nothing is pending.
+struct ZeroBatch {
+  const RuleSlot *rules;
+  unsigned int mask;
+  unsigned long long self_key;
+  const BatchArgs *ba;
+};
+void launch_top_scan(const PairTable &pt, const ScanArgs &sa, unsigned long long *stats, const ZeroBatch &zero,
+                     unsigned long long *xstat /* multi-GPU: the exchange's report, forwarded to the mailbox */, hipStream_t st);
 void launch_top_rebuild(const PairTable &pt, unsigned int listed_hint, hipStream_t st);
 // id_min / n_ids: the token ids in the tiles are id_min .. id_min + n_ids - 1 (K3 runs before any merge: the alphabet); n_ids <= 32
 // counts pairs in a dense LDS table, 0 (unknown / larger) in the LDS hash
@@ -120,7 +186,8 @@ bool launch_pair_count_radix(const TileSet &ts, const PairTable &pt, const Delta
 void launch_merge_apply(int cls, const TileSet &ts, const PairTable &pt, const DeltaBuf &db, const RuleSlot *rules, unsigned int rule_mask,
                         uint32_t self_x, uint32_t self_z, uint32_t z_base, unsigned long long *stats, const BatchArgs *ba,
                         const ScanArgs *scan /* the round's last launch only */,
-                        const uint32_t *bloom_g /* the batch not in ba: the batch's pair filter (pm_bloom_host) */, hipStream_t st);
+                        const uint32_t *bloom_g /* the batch not in ba: the batch's pair filter (pm_bloom_host) */,
+                        unsigned int apply_grid /* YTTM_APPLY_GRID: class-A grid cap for small tile sets (0: none) */, hipStream_t st);
 constexpr int PM_BLOOM_WORDS_H = 2048;
 void pm_bloom_host(uint32_t *bloom, const uint32_t *xyz, uint32_t k);
 // pair index for K4's worklists (k_index_core.h: PairIndex; k_index.hip)
@@ -141,7 +208,7 @@ void launch_idx_stream(bool fill, const TileSet &ts, const PairIndexArgs &a, hip
 size_t idx_save_bytes();
 // ---- word mode (k_words.hip)
 void launch_words_init(const TileSet &ts, unsigned long long *wmeta, hipStream_t st);
-struct WGatherArgs {
+struct WGatherArgs {  // (a kernel argument of k_wgather and k_words<FUSED>)
   PairIndexArgs ix;
   uint32_t ix_valid, z_static;   // tokens below z_static existed when the index was built
   TokLists tl;
@@ -158,26 +225,50 @@ struct WGatherArgs {
   uint32_t cnt[BATCH_ARGS_MAX];  // k_words<FUSED>: the count the host picked rule j by (saturated): no rule has more sites than that
 };
 constexpr unsigned int WGATHER_MAXK = 4096;
-extern int g_apply_grid;    // YTTM_APPLY_GRID as launch_env_refresh() found it (k_tiles.hip: launch_merge_apply)
-void launch_env_refresh();  // re-reads the launchers' environment hooks (YTTM_WORDS_GRID, YTTM_WORDS_WPI, YTTM_WGATHER_GRID): once per context
-void launch_wgather(const WGatherArgs &a, const BatchArgs *ba, unsigned int work_hint, hipStream_t st);
-bool launch_words_apply(const WordSet &ws, const PairTable &pt, const DeltaBuf &db, const RuleSlot *rules, unsigned int rule_mask, const uint32_t *bloom_g,
-                        uint32_t self_x, uint32_t self_z, uint32_t z_base, uint32_t k_rules, const uint32_t *worklist /* nullptr: every word */, unsigned long long wl_seg,
-                        const unsigned int *work_n, unsigned long long *stats, const TokLists &tl, DeltaRec *drec /* [WORDS_MAX_GRID * drec_cap] */,
-                        unsigned int drec_cap, unsigned int *drec_n /* [WORDS_MAX_GRID] */, uint4 *irec /* [WORDS_MAX_GRID * drec_cap] */, const BatchArgs *ba, const ScanArgs *scan, unsigned int work_hint,
-                        unsigned int inline_max /* rounds of at most this many words (by the hint) apply their records themselves */,
-                        const WGatherArgs *ga /* the round's gather: launched here (k_wgather) ... */,
-                        unsigned int fuse_max /* ... unless the hint is at most this and the batch is in the arguments: k_words gathers itself */, hipStream_t st,
-                        unsigned int avg_word_tokens = 0 /* live tokens per word, about (0: unknown): a wave takes no more words at a time than fit its 512-token tile */);
+void launch_wgather(const WGatherArgs &a, const BatchArgs *ba, unsigned int work_hint, int grid /* YTTM_WGATHER_GRID; < 0: by the hint */, hipStream_t st);
+// A word-mode round of class A: the gather (k_wgather), the words (k_words), their records (k_delta_apply) -- or fewer launches, see the fields.
+struct WordsRound {
+  WordSet ws;
+  PairTable pt;
+  DeltaBuf db;
+  const RuleSlot *rules;          // the batch's rule hash in HBM (the batch not in *ba)
+  unsigned int rule_mask;
+  const uint32_t *bloom_g;        // ... and its pair filter
+  uint32_t self_x, self_z;        // the batch's x == y rule; self_x == 0xffffffff: none
+  DeltaRec *drec;                 // [WORDS_MAX_GRID * drec_cap]
+  unsigned int drec_cap;
+  unsigned int *drec_n;           // [WORDS_MAX_GRID]
+  uint4 *irec;                    // [WORDS_MAX_GRID * drec_cap]
+  const BatchArgs *ba;
+  const ScanArgs *scan;           // the round's tail (nullptr: none)
+  unsigned int work_hint;         // about how many words the round will visit (0: unknown / every word)
+  unsigned int inline_max;        // rounds of at most this many words (by the hint) apply their records themselves
+  const WGatherArgs *ga;          // the round's gather -- its worklist, instance lists, statistics block, k and z_base are k_words' too --: launched
+                                  // here (k_wgather) ...
+  unsigned int fuse_max;          // ... unless the hint is at most this and the batch is in the arguments: k_words gathers itself
+  unsigned int avg_word_tokens;   // live tokens per word, about (0: unknown): a wave takes no more words at a time than fit its 512-token tile
+  int wgather_grid, words_grid, words_wpi;  // YTTM_WGATHER_GRID, YTTM_WORDS_GRID, YTTM_WORDS_WPI (tests); < 0: the launcher's own choice
+};
+bool launch_words_apply(const WordsRound &r, hipStream_t st);  // true: the round was ONE launch (k_words<FUSED>)
 constexpr unsigned int WORDS_MAX_GRID = 512;  // workgroups of k_words: each owns a region of the round's count-update records
 void launch_repack(int cls, const TileSet &ts, const unsigned long long *off, unsigned int nom, unsigned long long total,
                    unsigned long long *gstart, unsigned int n_new, uint32_t *new_tok, uint32_t *new_len, uint32_t *new_word0, hipStream_t st);
 void launch_cand_scan(const PairTable &pt, unsigned long long tau_cnt, uint32_t tau_mx, CandRec *out, unsigned int cap,
                       unsigned int *n_out, unsigned long long *hist, hipStream_t st);
-void launch_hot_scan(const PairTable &pt, unsigned long long tau_cnt, uint32_t tau_mx, CandRec *out, unsigned int cap, unsigned int *n_out,
-                     unsigned long long *hist, unsigned int *done_ctr, unsigned char *mailbox, unsigned int fast, uint32_t round_id,
-                     unsigned long long *stats, const RuleSlot *zrules, unsigned int zmask, unsigned long long zself, unsigned int listed_hint,
-                     const BatchArgs *zba, unsigned long long *xstat /* multi-GPU: the exchange's report, forwarded to the mailbox */, hipStream_t st);
+// One scan of the hot list (k_hot_scan): the candidates as sa says (threshold, out, cap; on, want, timed are not looked at), their number,
+// the key count, the list's length and its live entries in n_out[0..3], the histogram of the live counts in hist; then the last workgroup
+// (sa.done_ctr) publishes all of it in sa.mailbox under sa.round_id.
+struct HotScan {
+  PairTable pt;
+  ScanArgs sa;
+  unsigned int *n_out;
+  unsigned long long *hist;
+  unsigned long long *stats;
+  ZeroBatch zero;
+  unsigned int listed_hint;    // about the list's length: sizes the grid
+  unsigned long long *xstat;   // multi-GPU: the exchange's report, forwarded to the mailbox
+};
+void launch_hot_scan(const HotScan &h, hipStream_t st);
 // ---- multi-GPU, per round: K4 -> ncclAllGather -> k_pt_apply_blocks -> k_fold_list (+ the round's candidate scan) [-> k_dt_clean, during the host's turn]
 void launch_dt_clean(const DeltaBuf &db /* .send = the block just exchanged */, DeltaRec *other /* the block of the round to come */, unsigned int n_hint,
                      unsigned long long *stats, uint32_t tiles_a, unsigned int *done_ctr, hipStream_t st);
@@ -190,14 +281,10 @@ void launch_pt_apply_blocks(const PairTable &pt, const DeltaRec *blocks, unsigne
 // the same on every rank, so the lists hold the same pairs everywhere and no verdict on them has to be exchanged.  Then the round's
 // candidate scan (scan != nullptr) straight into the mailbox.
 void launch_fold_list(const PairTable &pt, const DeltaRec *blocks, unsigned long long blk, int world, unsigned long long only_mask, const ScanArgs *scan,
-                      unsigned long long *stats, const RuleSlot *zrules, unsigned int zmask, unsigned long long zself, const BatchArgs *zba,
-                      unsigned long long *xstat, bool read_headers /* phase 1 was not launched */, hipStream_t st);
-constexpr int MB_HIST = 128;  // byte offset of the count histogram in the mailbox (header + xstat before it)
-constexpr int MB_XSUM = 6144; // multi-GPU, behind the histogram: sums over the ranks' block headers -- [0] merge sites so far, [8] tokens streamed so far,
-                              // [16] class-A tiles, [24] ranks; [32] the round's apply kernels on the device clock (ticks; ScanArgs::timed)
-constexpr int XSTAT_WORDS = 8;  // d_xstat: [0] ranks whose block did not fit (bit r), [1] largest record count, [2] -, [3] a rank lost records, [4..7] the sums above
+                      unsigned long long *stats, const ZeroBatch &zero, unsigned long long *xstat, bool read_headers /* phase 1 was not launched */, hipStream_t st);
+constexpr int XSTAT_WORDS = 8;  // d_xstat: [0] ranks whose block did not fit (bit r), [1] largest record count, [2] -, [3] a rank lost records (-> RoundMailbox::xverdict),
+                                // [4..7] sums over the ranks' block headers (-> RoundMailbox::xsum[0..3])
 void launch_fold_stats(unsigned long long *stats, unsigned int *n_keys, hipStream_t st);
-constexpr int STATS_WORDS = 32 + 8 * 1536;  // totals + one row per workgroup (k_merge_shared.h: BLK_BASE, BLK_ROWS)
 void launch_round_begin(const RuleSlot *src_rules, unsigned int n_slots, RuleSlot *dst_rules, unsigned int *work_n_a, unsigned int *work_n_b,
                         const uint32_t *src_bloom, uint32_t *dst_bloom, hipStream_t st);
 void launch_hot_rebuild(const PairTable &pt, hipStream_t st);
