@@ -80,6 +80,37 @@ int yttm_encode_copy_device(yttm_encoder *enc, void *d_ids, void *d_out_offsets,
 int yttm_encode_copy_padded(yttm_encoder *enc, void *d_matrix, void *d_lengths, uint64_t n_sent, uint64_t width, int32_t pad_value,
                             uint64_t *longest, char *err, int errlen);
 
+/* Text that is not cut into sentences yet: its lines are found on the device, by the rules of std::getline as the command line applies them
+ * (bpe.cpp:1942-2014 reads std::cin with std::getline, utils.cpp:103-111): a line ends at the byte 0x0A; a last line without one counts; nothing
+ * follows a final newline; empty text has 0 lines; "\r" is no separator; an empty line is a sentence.  The lines come as the packed convention
+ * of this header: uint64 offsets[n_lines + 1], offsets[0] = 0, line i = text[offsets[i] .. offsets[i+1]) INCLUDING its newline (white space
+ * to the encoder: the ids of a line equal those of the line without it), offsets[n_lines] = n_bytes.
+ * yttm_lines_device: d_text = any device address.  The offsets stay in HBM inside the encoder, beside a pending encode or decode result, until
+ * yttm_lines_copy_device (to device memory the caller owns) / yttm_lines_fetch (to a host array) takes them.  *longest = the longest line in
+ * bytes, its newline included; kernel_ms (optional) = HIP-event time of count + scan + write + longest.  One thread at a time, as the other
+ * device pairs. */
+int yttm_lines_device(yttm_encoder *enc, const void *d_text, uint64_t n_bytes, uint64_t *n_lines, uint64_t *longest, double *kernel_ms, char *err,
+                      int errlen);
+int yttm_lines_copy_device(yttm_encoder *enc, void *d_offsets, uint64_t n_lines, char *err, int errlen);
+int yttm_lines_fetch(yttm_encoder *enc, uint64_t *offsets, uint64_t n_lines, char *err, int errlen);
+/* yttm_lines_device, then yttm_encode_device on those lines: the result is pending exactly as after yttm_encode_device with n_sent = *n_lines
+ * (yttm_encode_fetch, yttm_encode_copy_device, yttm_encode_copy_padded, yttm_encode_cache_words), and the lines' offsets as after
+ * yttm_lines_device.  kernel_ms (optional) = split + encode.  bpe.cpp:1942-2014 (the batch loop of encode_cli) without the text formatting */
+int yttm_encode_text_device(yttm_encoder *enc, const void *d_text, uint64_t n_bytes, int bos, int eos, int reverse, double dropout_prob,
+                            uint64_t *n_lines, uint64_t *n_ids, double *kernel_ms, char *err, int errlen);
+/* A text file of any size -> ids.  The file is read with pread into pinned chunks and crosses in pieces of about chunk_bytes (0: the default),
+ * each cut behind the last newline inside it -- a longer line extends its piece, it is never split --, through both encoder lanes: the upload of
+ * one piece runs beside the split and encode of the one before and the download of the one before that.  With dropout_prob == 0 the result
+ * does not depend on chunk_bytes.  out_prefix == NULL: *ids (int32[*n_ids]) and *offsets (uint64[*n_lines + 1], into ids) are malloc'ed, to be
+ * released with yttm_free, as yttm_encode_as_ids returns them.  Otherwise two raw little-endian files are written, PREFIX.ids (int32) and
+ * PREFIX.off (uint64, *n_lines + 1), and ids / offsets may be NULL.  report_json (optional): {"pieces", "piece_bytes", "bytes", "lines", "ids",
+ * "seconds_total", "seconds_read_upload", "seconds_split", "seconds_encode", "seconds_download_write"} (the four legs overlap).  A file that
+ * cannot be read or written is code 1 with a plain message.  Uses both lanes: a pending device result does not survive the call.
+ * replaces: encode_cli (bpe.h:66-68, bpe.cpp:1942-2014) with output_type "id", without the decimal formatting */
+int yttm_encode_file(yttm_encoder *enc, const char *path, const char *out_prefix, int bos, int eos, int reverse, double dropout_prob,
+                     uint64_t chunk_bytes, int32_t **ids, uint64_t **offsets, uint64_t *n_lines, uint64_t *n_ids, char *report_json, int report_len,
+                     char *err, int errlen);
+
 /* Word-level encode cache (SURVEY.md 8f "N4"; the reference has no counterpart: bpe.cpp:1497-1632 encodes every word occurrence).
  * mode 0: every batch goes straight through the encode kernel; 1: distinct words are encoded once whenever that is possible
  * (dropout_prob == 0); 2 (default): the same for batches of at least min_bytes.  The ids are identical either way.

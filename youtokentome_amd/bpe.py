@@ -2,6 +2,7 @@
 of the Cython class it wraps (`_youtokentome_cython.BPE`, youtokentome/cpp/yttm.pyx:51-182), on top of the MI355X C ABI
 (include/yttm_mi355x.h).  Same names, argument meaning, return shapes and error behaviour (ValueError / TypeError)."""
 import ctypes as C
+import os
 from collections.abc import Collection
 from enum import Enum
 from typing import List, Optional, Union
@@ -46,6 +47,25 @@ def _take(ptr, n, ctype, dtype):
     arr = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(max(n, 1),))[:n].astype(dtype, copy=True)
     L.yttm_free(C.cast(ptr, C.c_void_p))
     return arr
+
+
+class _Malloced:
+    """a malloc'ed result of the library as the base of a numpy array: released with yttm_free when the last view of it goes"""
+
+    def __init__(self, ptr, n, dtype):
+        self._addr = C.cast(ptr, C.c_void_p).value
+        self.__array_interface__ = {"shape": (int(n),), "typestr": np.dtype(dtype).str, "data": (self._addr, False), "version": 3}
+
+    def __del__(self):
+        if self._addr:
+            _lib.load().yttm_free(C.c_void_p(self._addr))
+            self._addr = None
+
+
+def _adopt(ptr, n, dtype):
+    """the same without the copy of _take (a file's ids are gigabytes)"""
+    owner = _Malloced(ptr, n, dtype)
+    return np.asarray(owner) if n else np.empty(0, dtype)
 
 
 class _Core:
@@ -157,6 +177,58 @@ class _Core:
     def copy_decode_device(self, d_bytes, d_out_offsets, n_sent):
         err = _err()
         self._check(_lib.load().yttm_decode_copy_device(self._h, C.c_void_p(d_bytes), C.c_void_p(d_out_offsets), n_sent, err, _lib.ERRLEN), err)
+
+    # ---- text that is not cut into sentences yet (include/yttm_mi355x.h): the lines are found on the device
+    def lines_device_raw(self, d_text, n_bytes):
+        """-> (n_lines, longest, kernel_ms); the offsets stay in the encoder until copy_lines_device / fetch_lines takes them"""
+        n, longest, ms, err = C.c_uint64(), C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_lines_device(self._h, C.c_void_p(d_text), n_bytes, C.byref(n), C.byref(longest), C.byref(ms), err, _lib.ERRLEN), err)
+        return n.value, longest.value, ms.value
+
+    def copy_lines_device(self, d_offsets, n_lines):
+        err = _err()
+        self._check(_lib.load().yttm_lines_copy_device(self._h, C.c_void_p(d_offsets), n_lines, err, _lib.ERRLEN), err)
+
+    def fetch_lines(self, n_lines):
+        """-> uint64 offsets[n_lines + 1] on the host"""
+        off, err = np.zeros(n_lines + 1, np.uint64), _err()
+        self._check(_lib.load().yttm_lines_fetch(self._h, off.ctypes.data_as(_lib.u64p), n_lines, err, _lib.ERRLEN), err)
+        return off
+
+    def encode_text_device_raw(self, d_text, n_bytes, bos=False, eos=False, reverse=False, dropout_prob=0.0):
+        """-> (n_lines, n_ids, kernel_ms); the ids are pending as after encode_device_raw with n_sent = n_lines"""
+        nl, ni, ms, err = C.c_uint64(), C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_encode_text_device(self._h, C.c_void_p(d_text), n_bytes, int(bos), int(eos), int(reverse), float(dropout_prob),
+                                                        C.byref(nl), C.byref(ni), C.byref(ms), err, _lib.ERRLEN), err)
+        return nl.value, ni.value, ms.value
+
+    def fetch_encode(self, n_sent, n_ids):
+        """the pending encode result -> (int32 ids[n_ids], uint64 offsets[n_sent + 1]) on the host"""
+        ids, off, err = np.empty(max(int(n_ids), 1), np.int32), np.zeros(n_sent + 1, np.uint64), _err()
+        self._check(_lib.load().yttm_encode_fetch(self._h, ids.ctypes.data_as(_lib.i32p), off.ctypes.data_as(_lib.u64p), n_sent, err, _lib.ERRLEN), err)
+        return ids[:int(n_ids)], off
+
+    def encode_file(self, path, out=None, bos=False, eos=False, reverse=False, dropout_prob=0.0, chunk_bytes=None, report=False):
+        """a text file -> (int32 ids, uint64 offsets[n_lines + 1]), or with out=PREFIX the files PREFIX.ids / PREFIX.off and (n_lines, n_ids);
+        report=True appends the call's report (a dict) to the result"""
+        if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
+            raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+        L = _lib.load()
+        ids, off, nl, ni, err = _lib.i32p(), _lib.u64p(), C.c_uint64(), C.c_uint64(), _err()
+        rep = C.create_string_buffer(1024)
+        rc = L.yttm_encode_file(self._h, os.fsencode(path), None if out is None else os.fsencode(out), int(bos), int(eos), int(reverse), float(dropout_prob),
+                                int(chunk_bytes or 0), None if out is not None else C.byref(ids), None if out is not None else C.byref(off),
+                                C.byref(nl), C.byref(ni), rep, len(rep), err, _lib.ERRLEN)
+        if rc != 0:
+            raise ValueError(err.value.decode(errors="replace"))
+        if out is not None:
+            res = (nl.value, ni.value)
+        else:
+            res = (_adopt(ids, ni.value, np.int32), _adopt(off, nl.value + 1, np.uint64))
+        if report:
+            import json
+            res += (json.loads(rep.value.decode()),)
+        return res
 
     def encode(self, sentences, output_type, bos, eos, reverse, dropout_prob):
         if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
@@ -323,6 +395,24 @@ class BPE:
         from . import tensor
         return tensor.encode_tensor(self, sentences, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, padded=padded, width=width,
                                     pad_id=pad_id, device=device)
+
+    def encode_text_tensor(self, text, bos: bool = False, eos: bool = False, reverse: bool = False, dropout_prob: float = 0, padded: bool = True,
+                           width: Optional[int] = None, pad_id: Optional[int] = None):
+        """`text`: a 1-D uint8 tensor on the encoder's device, or bytes / bytearray / memoryview (uploaded); one sentence per line.  Returns what
+        encode_tensor returns."""
+        from . import tensor
+        return tensor.encode_text_tensor(self, text, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, padded=padded, width=width, pad_id=pad_id)
+
+    def text_lines_tensor(self, text):
+        """the lines of `text` as an int64 offsets tensor [n_lines + 1] on the device (line i = text[off[i]:off[i + 1]], its newline included)"""
+        from . import tensor
+        return tensor.text_lines_tensor(self, text)
+
+    def encode_file(self, path, out: Optional[str] = None, bos: bool = False, eos: bool = False, reverse: bool = False, dropout_prob: float = 0,
+                    chunk_bytes: Optional[int] = None):
+        """A text file, one sentence per line -> (ids np.int32, offsets np.uint64 [n_lines + 1]); with out=PREFIX the raw little-endian files
+        PREFIX.ids (int32) and PREFIX.off (uint64) are written instead and (n_lines, n_ids) is returned.  Needs no torch."""
+        return self.bpe_cython.encode_file(path, out=out, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, chunk_bytes=chunk_bytes)
 
     def decode_tensor(self, ids, lengths=None, offsets=None, ignore_ids: Optional[Collection] = None, as_str: bool = True):
         from . import tensor

@@ -204,6 +204,44 @@ int yttm_decode_copy_device(yttm_encoder *h, void *d_bytes, void *d_out_offsets,
   return finish(h->enc->copy_decode_result(d_bytes, d_out_offsets, n_sent), err, errlen);
 }
 
+int yttm_lines_device(yttm_encoder *h, const void *d_text, uint64_t n_bytes, uint64_t *n_lines, uint64_t *longest, double *kernel_ms, char *err, int errlen) {
+  unsigned long long n = 0, m = 0;
+  Status s = h->enc->lines_device(d_text, n_bytes, &n, &m, kernel_ms);
+  if (n_lines) *n_lines = n;
+  if (longest) *longest = m;
+  return finish(s, err, errlen);
+}
+int yttm_lines_copy_device(yttm_encoder *h, void *d_offsets, uint64_t n_lines, char *err, int errlen) {
+  return finish(h->enc->take_lines(d_offsets, n_lines, true), err, errlen);
+}
+int yttm_lines_fetch(yttm_encoder *h, uint64_t *offsets, uint64_t n_lines, char *err, int errlen) {
+  return finish(h->enc->take_lines(offsets, n_lines, false), err, errlen);
+}
+int yttm_encode_text_device(yttm_encoder *h, const void *d_text, uint64_t n_bytes, int bos, int eos, int reverse, double dropout_prob, uint64_t *n_lines,
+                            uint64_t *n_ids, double *kernel_ms, char *err, int errlen) {
+  unsigned long long nl = 0, ni = 0;
+  Status s = h->enc->encode_text_device(d_text, n_bytes, bos, eos, reverse, dropout_prob, &nl, &ni, kernel_ms);
+  if (n_lines) *n_lines = nl;
+  if (n_ids) *n_ids = ni;
+  return finish(s, err, errlen);
+}
+int yttm_encode_file(yttm_encoder *h, const char *path, const char *out_prefix, int bos, int eos, int reverse, double dropout_prob, uint64_t chunk_bytes,
+                     int32_t **ids, uint64_t **offsets, uint64_t *n_lines, uint64_t *n_ids, char *report_json, int report_len, char *err, int errlen) {
+  unsigned long long nl = 0, ni = 0, *off = nullptr;
+  int32_t *idp = nullptr;
+  std::string report;
+  Status s = h->enc->encode_file(path ? path : "", out_prefix, bos, eos, reverse, dropout_prob, chunk_bytes, out_prefix ? nullptr : &idp, out_prefix ? nullptr : &off,
+                                 &nl, &ni, &report);
+  if (ids) *ids = idp;
+  else free(idp);
+  if (offsets) *offsets = (uint64_t *)off;
+  else free(off);
+  if (n_lines) *n_lines = nl;
+  if (n_ids) *n_ids = ni;
+  if (s.ok() && report_json && report_len > 0) snprintf(report_json, (size_t)report_len, "%s", report.c_str());
+  return finish(s, err, errlen);
+}
+
 int yttm_encoder_set_cache(yttm_encoder *h, int mode, uint64_t min_bytes) {
   h->enc->set_cache(mode, min_bytes);
   return 0;

@@ -126,6 +126,16 @@ class BaseEncoder {  // bpe.h:22-82
   Status copy_encode_result(void *d_ids, void *d_out_off, unsigned long long n_sent) const;
   Status copy_encode_padded(void *d_matrix, void *d_lengths, unsigned long long n_sent, unsigned long long width, int32_t pad_value,
                             unsigned long long *longest) const;
+  // text that is not cut into sentences yet (host_lines.h, k_lines.h): its lines by std::getline's rules, found on the device.  lines_device leaves
+  // uint64 offsets[n_lines + 1] (line i WITH its newline) in lane 0, beside a pending encode / decode result; take_lines copies them out.
+  Status lines_device(const void *d_text, unsigned long long n_bytes, unsigned long long *n_lines, unsigned long long *longest, double *kernel_ms) const;
+  Status take_lines(void *offsets, unsigned long long n_lines, bool to_device) const;
+  // split + encode_device: the result is pending as after encode_device (n_sent = *n_lines)
+  Status encode_text_device(const void *d_text, unsigned long long n_bytes, bool bos, bool eos, bool reverse, double dropout_prob,
+                            unsigned long long *n_lines, unsigned long long *n_ids, double *kernel_ms) const;
+  // a file of any size in pieces through both lanes; out_prefix: PREFIX.ids / PREFIX.off instead of malloc'ed arrays
+  Status encode_file(const std::string &path, const char *out_prefix, bool bos, bool eos, bool reverse, double dropout_prob, unsigned long long piece_bytes,
+                     int32_t **ids, unsigned long long **out_off, unsigned long long *n_lines, unsigned long long *n_ids, std::string *report) const;
   // the YTTM_* hooks as they stood when THIS encoder was made: every entry point binds them to its thread (yttm_config.h CfgBind), so that a
   // later encoder or training never changes the paths of this one
   std::shared_ptr<const Config> config() const;

@@ -65,6 +65,13 @@ struct EncodeLane {
   unsigned long long *d_dec_misc = nullptr;               // [0] smallest flat index of an invalid id, [1] longest row (k_enc_longest)
   unsigned long long dec_n_sent = 0, dec_n_bytes = 0;
   bool dec_valid = false;
+  // line split (host_lines.h): newlines per tile, their scan, the lines' offsets -- again buffers of their own
+  uint32_t *d_ln_cnt = nullptr; size_t cap_ln_cnt = 0;
+  unsigned long long *d_ln_rank = nullptr; size_t cap_ln_rank = 0;
+  unsigned long long *d_ln_off = nullptr; size_t cap_ln_off = 0;
+  unsigned long long *d_ln_misc = nullptr;  // [0] longest line (k_lines_longest)
+  unsigned long long ln_n_lines = 0, ln_n_bytes = 0, ln_longest = 0;
+  bool ln_valid = false;
 
   template <class T>
   void grow(T *&p, size_t &cap, size_t need) {
@@ -79,7 +86,8 @@ struct EncodeLane {
     for (void *p : {(void *)d_drop, (void *)d_bytes, (void *)d_off, (void *)d_scratch, (void *)d_counts, (void *)d_out_off, (void *)d_scan_tmp,
                     (void *)d_total, (void *)d_ids, (void *)d_work, (void *)d_wc_slot, (void *)d_wc_pos, (void *)d_wc_occ, (void *)d_wc_extra,
                     (void *)d_wc_misc, (void *)d_wc_blk, (void *)d_wc_blk_off, (void *)d_ustart, (void *)d_uend, (void *)d_uslot, (void *)d_ucounts,
-                    (void *)d_dec_len, (void *)d_dec_off, (void *)d_dec_bytes, (void *)d_dec_ign, (void *)d_dec_misc})
+                    (void *)d_dec_len, (void *)d_dec_off, (void *)d_dec_bytes, (void *)d_dec_ign, (void *)d_dec_misc, (void *)d_ln_cnt, (void *)d_ln_rank,
+                    (void *)d_ln_off, (void *)d_ln_misc})
       if (p) (void)hipFree(p);
     if (st) (void)hipStreamDestroy(st);
   }
@@ -904,3 +912,4 @@ std::vector<std::string> BaseEncoder::vocabulary() const {  // bpe.cpp:1884-1894
 }
 
 }  // namespace yttm
+#include "host_lines.h"  // the line split and the entries for unsplit text: a buffer in HBM, a file (uses the lanes, encode_on_lane, result_alloc)

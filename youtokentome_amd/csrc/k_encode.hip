@@ -1145,3 +1145,4 @@ void launch_encode_gather(const int32_t *scratch_ids, const unsigned long long *
 }  // namespace yttm
 
 #include "k_decode.h"  // device decode and the padded encode result: kernels and launchers of this translation unit
+#include "k_lines.h"   // the lines of a text in HBM: kernels and launchers of this translation unit

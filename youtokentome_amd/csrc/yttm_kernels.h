@@ -405,4 +405,13 @@ void launch_enc_longest(const unsigned long long *out_off, unsigned long long n_
 void launch_enc_pad(const int32_t *ids, const unsigned long long *out_off, unsigned long long n_sent, unsigned long long width, int32_t pad_value,
                     int32_t *matrix /* 4-byte aligned */, int32_t *lengths, hipStream_t st);
 
+// ---- the lines of a text in HBM (k_lines.h, compiled with k_encode.hip): count -> launch_exclusive_scan -> write, then the longest line ----
+// d_text: any address.  lines_tiles: entries of cnt (the scan's input; 0: a text of fewer than two bytes holds no newline that starts a line).
+unsigned long long lines_tiles(const void *d_text, unsigned long long n_bytes);
+void launch_lines_count(const uint8_t *d_text, unsigned long long n_bytes, uint32_t *cnt, hipStream_t st);
+// rank: the exclusive scan of cnt; off[n_lines + 1], n_lines = (sum of cnt) + 1: line i = text[off[i] .. off[i + 1]) with its newline
+void launch_lines_write(const uint8_t *d_text, unsigned long long n_bytes, const unsigned long long *rank, unsigned long long *off, unsigned long long n_lines,
+                        hipStream_t st);
+void launch_lines_longest(const unsigned long long *off, unsigned long long n_lines, unsigned long long *longest /* holds 0 before the launch */, hipStream_t st);
+
 }  // namespace yttm

@@ -1,5 +1,6 @@
-"""Device tensors in, device tensors out: `BPE.encode_tensor` / `BPE.decode_tensor` on top of the raw device layer of `bpe._Core`
-(include/yttm_mi355x.h: yttm_encode_device, yttm_encode_copy_*, yttm_decode_device*, yttm_decode_copy_device).  torch is imported at call
+"""Device tensors in, device tensors out: `BPE.encode_tensor` / `BPE.encode_text_tensor` / `BPE.text_lines_tensor` / `BPE.decode_tensor` on top
+of the raw device layer of `bpe._Core` (include/yttm_mi355x.h: yttm_encode_device, yttm_encode_text_device, yttm_lines_*, yttm_encode_copy_*,
+yttm_decode_device*, yttm_decode_copy_device).  torch is imported at call
 time; the rest of the package does not need it.
 
 The library works on a non-blocking stream of its own and returns after that stream has synchronised.  So the hand-over is: synchronise
@@ -72,6 +73,11 @@ def encode_tensor(bpe, sentences, bos=False, eos=False, reverse=False, dropout_p
             total = longest_in = 0
     torch.cuda.current_stream(dev).synchronize()  # the inputs are complete before the library's own stream reads them
     n_ids, _ = core.encode_device_raw(d_bytes.data_ptr(), d_off.data_ptr(), n, total, longest_in, bos, eos, reverse, dropout_prob)
+    return _take_encoded(torch, core, dev, n, n_ids, padded, width, pad_id)
+
+
+def _take_encoded(torch, core, dev, n, n_ids, padded, width, pad_id):
+    """the pending encode result of n sentences as tensors that torch owns"""
     if not padded:
         ids = torch.empty(n_ids, dtype=torch.int32, device=dev)
         out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
@@ -89,6 +95,47 @@ def encode_tensor(bpe, sentences, bos=False, eos=False, reverse=False, dropout_p
         torch.cuda.current_stream(dev).synchronize()
         core.copy_encode_padded(matrix.data_ptr(), lengths.data_ptr(), n, width, pad_id)
     return matrix, lengths
+
+
+def _text_on(torch, text, dev):
+    """1-D uint8 tensor on the encoder's device, or bytes-like (uploaded) -> (contiguous tensor, n_bytes)"""
+    if isinstance(text, (bytes, bytearray, memoryview)):
+        raw = bytearray(text)
+        n = len(raw)
+        return torch.frombuffer(raw if n else bytearray(1), dtype=torch.uint8).to(dev), n
+    if not hasattr(text, "data_ptr") or text.dtype != torch.uint8 or text.dim() != 1:
+        raise ValueError("text is a 1-D uint8 tensor on the encoder's device, or bytes / bytearray / memoryview")
+    _check_on(text, dev, "text")
+    return text.contiguous(), text.numel()
+
+
+def encode_text_tensor(bpe, text, bos=False, eos=False, reverse=False, dropout_prob=0, padded=True, width=None, pad_id=None):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
+        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+    if padded and pad_id is None:
+        pad_id = bpe.subword_to_id("<PAD>")
+        if pad_id == -1 or bpe.id_to_subword(pad_id) != "<PAD>":
+            raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
+    d_text, n_bytes = _text_on(torch, text, dev)
+    torch.cuda.current_stream(dev).synchronize()  # the text is complete before the library's own stream reads it
+    n, n_ids, _ = core.encode_text_device_raw(d_text.data_ptr(), n_bytes, bos, eos, reverse, dropout_prob)
+    return _take_encoded(torch, core, dev, n, n_ids, padded, width, pad_id)
+
+
+def text_lines_tensor(bpe, text):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    d_text, n_bytes = _text_on(torch, text, dev)
+    torch.cuda.current_stream(dev).synchronize()
+    n, _, _ = core.lines_device_raw(d_text.data_ptr(), n_bytes)
+    off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()
+    core.copy_lines_device(off.data_ptr(), n)
+    return off
 
 
 def decode_tensor(bpe, ids, lengths=None, offsets=None, ignore_ids=None, as_str=True):
