@@ -669,6 +669,42 @@ static double rng_uniform01(void) {
   return r;
 }
 
+/* ---- the second draw source: the product's keyed draws (DESIGN.md, K5 "The draw function"), restated from that text.  A word's stream is
+ * keyed by (the pass's seed, the sentence's index in the pass, word index in the sentence); one draw per event examined inside DropoutQueue::pop.
+ * Off by default: the mt19937 path above is what the reference does. ---- */
+static int keyed_on = 0;
+static uint64_t keyed_seed = 0, keyed_sidx = 0;
+void oracle_rng_keyed(int on, uint64_t seed) { keyed_on = on; keyed_seed = seed; keyed_sidx = 0; }
+static uint64_t keyed_word_key(uint64_t seed, uint64_t sidx, uint64_t word) {
+  return mix64(seed + sidx * 0x9e3779b97f4a7c15ull + (word << 34));
+}
+typedef struct { uint32_t draw, hi; } keyed_stream;
+static keyed_stream keyed_begin(uint64_t wkey) { keyed_stream k = {(uint32_t)wkey, (uint32_t)(wkey >> 32)}; return k; }
+static uint32_t keyed_next(keyed_stream *k) {
+  k->draw += 0x9e3779b9u;
+  uint32_t h = k->draw ^ k->hi;
+  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+  return h;
+}
+/* the k-th (0-based) 32-bit value of the stream of word `word` of sentence `sidx` */
+uint32_t oracle_keyed_draw(uint64_t seed, uint64_t sidx, uint64_t word, uint64_t k) {
+  keyed_stream st = keyed_begin(keyed_word_key(seed, sidx, word));
+  uint32_t h = 0;
+  for (uint64_t i = 0; i <= k; i++) h = keyed_next(&st);
+  return h;
+}
+/* n consecutive values of that stream */
+void oracle_keyed_draws(uint64_t seed, uint64_t sidx, uint64_t word, uint64_t n, uint32_t *out) {
+  keyed_stream st = keyed_begin(keyed_word_key(seed, sidx, word));
+  for (uint64_t i = 0; i < n; i++) out[i] = keyed_next(&st);
+}
+/* skipped iff h < the top 32 bits of floor(p * 2^64); p >= 1 skips without drawing */
+static int keyed_skip(keyed_stream *k, double p) {
+  if (p >= 1.0) return 1;
+  uint32_t thr = (uint32_t)((uint64_t)(p * 18446744073709551616.0) >> 32);
+  return keyed_next(k) < thr;
+}
+
 typedef struct { int prio, pos; } ev_t;
 /* MergeEvent2::operator< (bpe.cpp:1475-1478): smallest (priority,pos) pops first */
 static int ev_before(ev_t a, ev_t b) { return a.prio < b.prio || (a.prio == b.prio && a.pos < b.pos); }
@@ -707,7 +743,9 @@ int64_t oracle_encode(const oracle_model *m, const uint8_t *s, uint64_t n, int b
   const uint32_t new_tokens_start = 1000000000u; /* :1503 */
   node_t *list = NULL; uint64_t lcap = 0;
   evheap q = {0, 0, 0}; ev_t *skipped = NULL; uint64_t scap = 0;
-  uint64_t it = 0;
+  uint64_t it = 0, word_no = 0;
+  keyed_stream ks = {0, 0};
+  const char *trace = keyed_on ? getenv("ORACLE_TRACE_DRAWS") : NULL; /* examined events to stderr, for a mismatch hunt */
   while (it < tl) { /* :1505 */
     uint64_t b = it; while (b < tl && is_space_cp(text[b])) b++;
     uint64_t e = b; while (e < tl && !is_space_cp(text[e])) e++;
@@ -728,6 +766,8 @@ int64_t oracle_encode(const oracle_model *m, const uint8_t *s, uint64_t n, int b
 #undef LPUSH
     list[ln - 1].next = -1;
     q.n = 0;
+    if (keyed_on) ks = keyed_begin(keyed_word_key(keyed_seed, keyed_sidx, word_no));
+    word_no++;
 #define PUSH_IF_RULE(p)                                                                        \
   {                                                                                            \
     int _p2 = list[(p)].next;                                                                  \
@@ -743,7 +783,9 @@ int64_t oracle_encode(const oracle_model *m, const uint8_t *s, uint64_t n, int b
         for (;;) {
           if (q.n == 0) { for (uint64_t k = 0; k < ns; k++) evh_push(&q, skipped[k]); ns = 0; break; }
           ev_t t = evh_pop(&q);
-          if (rng_uniform01() < dropout) {
+          int skip = keyed_on ? keyed_skip(&ks, dropout) : rng_uniform01() < dropout;
+          if (trace) fprintf(stderr, "sent %llu word %llu: rule %d pos %d %s\n", (unsigned long long)keyed_sidx, (unsigned long long)(word_no - 1), t.prio, t.pos, skip ? "skipped" : "taken");
+          if (skip) {
             if (ns == scap) { scap = scap ? scap * 2 : 64; skipped = (ev_t *)realloc(skipped, scap * sizeof(ev_t)); }
             skipped[ns++] = t;
           } else { for (uint64_t k = 0; k < ns; k++) evh_push(&q, skipped[k]); ns = 0; ev = t; got = 1; break; }
@@ -775,14 +817,16 @@ int64_t oracle_encode(const oracle_model *m, const uint8_t *s, uint64_t n, int b
   return ret;
 }
 
-int oracle_encode_batch(const oracle_model *m, const uint8_t *bytes, const uint64_t *offsets, uint64_t n_sent, int bos, int eos,
-                        int reverse, double dropout, int32_t **ids_out, uint64_t **out_off, char *err, int errlen) {
+/* sentence i of the batch draws (keyed source) as sentence sidx_base + i of its pass */
+int oracle_encode_batch_from(const oracle_model *m, const uint8_t *bytes, const uint64_t *offsets, uint64_t n_sent, uint64_t sidx_base, int bos,
+                             int eos, int reverse, double dropout, int32_t **ids_out, uint64_t **out_off, char *err, int errlen) {
   uint64_t cap = 1024, n = 0;
   int32_t *ids = (int32_t *)malloc(cap * sizeof(int32_t));
   uint64_t *off = (uint64_t *)malloc((n_sent + 1) * sizeof(uint64_t));
   for (uint64_t i = 0; i < n_sent; i++) {
     off[i] = n;
     uint64_t len = offsets[i + 1] - offsets[i];
+    keyed_sidx = sidx_base + i;
     uint64_t need = 2 * len + 8; /* <= 1 id per byte + leading space tokens + bos/eos */
     if (n + need > cap) { while (n + need > cap) cap *= 2; ids = (int32_t *)realloc(ids, cap * sizeof(int32_t)); }
     int64_t k = oracle_encode(m, bytes + offsets[i], len, bos, eos, reverse, dropout, ids + n, cap - n, err, errlen);
@@ -792,4 +836,9 @@ int oracle_encode_batch(const oracle_model *m, const uint8_t *bytes, const uint6
   off[n_sent] = n;
   *ids_out = ids; *out_off = off;
   return 0;
+}
+
+int oracle_encode_batch(const oracle_model *m, const uint8_t *bytes, const uint64_t *offsets, uint64_t n_sent, int bos, int eos,
+                        int reverse, double dropout, int32_t **ids_out, uint64_t **out_off, char *err, int errlen) {
+  return oracle_encode_batch_from(m, bytes, offsets, n_sent, 0, bos, eos, reverse, dropout, ids_out, out_off, err, errlen);
 }

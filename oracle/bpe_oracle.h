@@ -84,7 +84,17 @@ int oracle_model_vocab_size(const oracle_model *m);
 /* Reset the emulated process-global std::mt19937 (default seed 5489), bpe.cpp:1415. */
 void oracle_rng_reset(void);
 
-/* Encode one sentence to ids (bpe.cpp:1455-1632).  Returns the number of ids (may exceed cap: then only
+/* A second draw source for dropout: the product's keyed draws ("The draw function"), written here from that text.
+ * While on, oracle_encode_batch[_from] numbers the sentences (sidx_base + i), oracle_encode numbers the words it walks, and an event is
+ * skipped iff the word's next draw is below the top 32 bits of floor(p * 2^64).  `seed` is the seed of one K5 pass of the encoder;
+ * a sentence's index is its index in that pass.  Off: mt19937, as the reference.
+ * With ORACLE_TRACE_DRAWS set in the environment, every examined event goes to stderr. */
+void oracle_rng_keyed(int on, uint64_t seed);
+/* the k-th (0-based) 32-bit draw of word `word` of sentence `sidx`; oracle_keyed_draws: the first n of them */
+uint32_t oracle_keyed_draw(uint64_t seed, uint64_t sidx, uint64_t word, uint64_t k);
+void oracle_keyed_draws(uint64_t seed, uint64_t sidx, uint64_t word, uint64_t n, uint32_t *out);
+
+/* Encode one sentence to ids (bpe.cpp:1455-1632). Returns the number of ids (may exceed cap: then only
  * cap ids were written), or -1 with err set for the bos/eos Status errors of bpe.cpp:1702-1707. */
 int64_t oracle_encode(const oracle_model *m, const uint8_t *sentence, uint64_t n, int bos, int eos, int reverse,
                       double dropout_prob, int32_t *out, uint64_t cap, char *err, int errlen);
@@ -93,6 +103,10 @@ int64_t oracle_encode(const oracle_model *m, const uint8_t *sentence, uint64_t n
 int oracle_encode_batch(const oracle_model *m, const uint8_t *bytes, const uint64_t *offsets, uint64_t n_sent,
                         int bos, int eos, int reverse, double dropout_prob, int32_t **ids_out,
                         uint64_t **out_off, char *err, int errlen);
+/* ... whose sentence i draws (keyed source) as sentence sidx_base + i */
+int oracle_encode_batch_from(const oracle_model *m, const uint8_t *bytes, const uint64_t *offsets, uint64_t n_sent,
+                             uint64_t sidx_base, int bos, int eos, int reverse, double dropout_prob, int32_t **ids_out,
+                             uint64_t **out_off, char *err, int errlen);
 
 #ifdef __cplusplus
 }

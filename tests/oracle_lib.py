@@ -1,4 +1,5 @@
 """ctypes binding of oracle/libbpe_oracle.so -- TEST INFRASTRUCTURE (the checker, never the product)."""
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -47,6 +48,12 @@ def lib():
                                     C.c_uint64, C.c_char_p, C.c_int]
         L.oracle_encode_batch.argtypes = [C.c_void_p, C.c_char_p, u64p, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                           C.c_double, C.POINTER(i32p), C.POINTER(u64p), C.c_char_p, C.c_int]
+        L.oracle_encode_batch_from.argtypes = [C.c_void_p, C.c_char_p, u64p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int,
+                                               C.c_double, C.POINTER(i32p), C.POINTER(u64p), C.c_char_p, C.c_int]
+        L.oracle_rng_keyed.argtypes = [C.c_int, C.c_uint64]
+        L.oracle_keyed_draw.restype = C.c_uint32
+        L.oracle_keyed_draw.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
+        L.oracle_keyed_draws.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, u32p]
         _LIB = L
     return _LIB
 
@@ -159,23 +166,25 @@ class Model:
     def vocab_size(self):
         return lib().oracle_model_vocab_size(self.h)
 
-    def encode(self, sentences, bos=False, eos=False, reverse=False, dropout_prob=0.0):
+    def encode(self, sentences, bos=False, eos=False, reverse=False, dropout_prob=0.0, sidx_base=0):
         """sentences: list[bytes] -> list[list[int]]"""
-        ids, off = self.encode_packed(sentences, bos, eos, reverse, dropout_prob)
-        return [ids[int(off[i]):int(off[i + 1])].tolist() for i in range(len(sentences))]
+        ids, off = self.encode_packed(sentences, bos, eos, reverse, dropout_prob, sidx_base)
+        flat, o = ids.tolist(), off.tolist()
+        return [flat[o[i]:o[i + 1]] for i in range(len(sentences))]
 
-    def encode_packed(self, sentences, bos=False, eos=False, reverse=False, dropout_prob=0.0):
+    def encode_packed(self, sentences, bos=False, eos=False, reverse=False, dropout_prob=0.0, sidx_base=0):
         blob = b"".join(sentences)
         offs = np.zeros(len(sentences) + 1, np.uint64)
         np.cumsum([len(s) for s in sentences], out=offs[1:])
-        return self.encode_blob(blob, offs, bos, eos, reverse, dropout_prob)
+        return self.encode_blob(blob, offs, bos, eos, reverse, dropout_prob, sidx_base)
 
-    def encode_blob(self, blob, offs, bos=False, eos=False, reverse=False, dropout_prob=0.0):
+    def encode_blob(self, blob, offs, bos=False, eos=False, reverse=False, dropout_prob=0.0, sidx_base=0):
+        """sidx_base: under keyed() sentence i draws as sentence sidx_base + i of the pass (the mt19937 source does not look at it)"""
         offs = np.ascontiguousarray(offs, np.uint64)
         ids, ooff = i32p(), u64p()
         err = C.create_string_buffer(1024)
-        rc = lib().oracle_encode_batch(self.h, bytes(blob), _p(offs, u64p), len(offs) - 1, int(bos), int(eos),
-                                       int(reverse), float(dropout_prob), C.byref(ids), C.byref(ooff), err, 1024)
+        rc = lib().oracle_encode_batch_from(self.h, bytes(blob), _p(offs, u64p), len(offs) - 1, int(sidx_base), int(bos), int(eos),
+                                            int(reverse), float(dropout_prob), C.byref(ids), C.byref(ooff), err, 1024)
         if rc != 0:
             raise ValueError(err.value.decode())
         off = _take(ooff, len(offs), np.uint64)
@@ -184,3 +193,42 @@ class Model:
 
 def rng_reset():
     lib().oracle_rng_reset()
+
+
+# ---- the keyed draw source ("The draw function"): the arithmetic restated here, not taken from the product ----------------
+M64 = (1 << 64) - 1
+
+
+def mix64(x):
+    x &= M64
+    x ^= x >> 33
+    x = (x * 0xff51afd7ed558ccd) & M64
+    x ^= x >> 33
+    x = (x * 0xc4ceb9fe1a85ec53) & M64
+    x ^= x >> 33
+    return x
+
+
+def call_seed(salt, call=1):
+    """the seed of an encoder's call-th (1-based) K5 pass under YTTM_DROPOUT_SEED=salt"""
+    return mix64(salt + 0x5bd1e995 * call)
+
+
+@contextlib.contextmanager
+def keyed(salt, call=1):
+    """inside, dropout draws of the oracle are the keyed ones of the call-th K5 pass of an encoder with salt `salt`; always switched off again"""
+    lib().oracle_rng_keyed(1, call_seed(salt, call))
+    try:
+        yield
+    finally:
+        lib().oracle_rng_keyed(0, 0)
+
+
+def keyed_draw(seed, sidx, word, k):
+    return lib().oracle_keyed_draw(seed, sidx, word, k)
+
+
+def keyed_draws(seed, sidx, word, n):
+    out = np.zeros(n, np.uint32)
+    lib().oracle_keyed_draws(seed, sidx, word, n, _p(out, u32p))
+    return out

@@ -100,7 +100,8 @@ __device__ inline uint32_t enc_rule_z(const EncModel &m, uint32_t r) {
 // each event is skipped with probability p, the first one not skipped is taken (stale events included: they consume the
 // pop), all-skipped ends the word.  One word per lane (the process is inherently sequential within a word); the RNG is a
 // counter-based hash of (seed, sentence, word, draw) -- a per-lane stream cannot reproduce the reference's single global
-// mt19937 order, so parity is a distribution match (BASELINE.json configs[4]).
+// mt19937 order, so parity with the reference is a distribution match (BASELINE.json configs[4]); with the oracle drawing the same keyed
+// draws the ids are equal bit for bit ("The draw function"; tests/dropout_checks.py).
 struct DropoutArgs {
   unsigned long long thr;   // skip iff hash < thr  (thr = p * 2^64); always_skip for p == 1
   unsigned long long seed;
