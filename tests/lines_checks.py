@@ -394,6 +394,26 @@ def check_file_edges(tmp_path, name="readme_small"):
     assert ids.tolist() == h_ids.tolist() and off.tolist() == h_off.tolist()
 
 
+def check_file_write_failure(tmp_path, name="readme_small"):
+    """A full disk under PREFIX.ids or PREFIX.off (a link to /dev/full: pwrite gives ENOSPC inside the download thread, whatever the piece
+    size) is this call's error -- and the same BPE object goes on to encode the file: both lanes were released and are as good as before"""
+    import pytest
+    import youtokentome_amd as yttm
+    bpe = yttm.BPE(os.path.join(G, f"train_{name}.model"))
+    data, _ = golden(name)
+    path = str(tmp_path / f"{name}.txt")
+    open(path, "wb").write(data)
+    h_ids, h_off = host_encode(bpe.bpe_cython, data)
+    for full in (".ids", ".off"):
+        prefix = str(tmp_path / f"full{full[1:]}")
+        os.symlink("/dev/full", prefix + full)
+        for chunk in (None, 1, 700):
+            with pytest.raises(ValueError, match=r"Failed to write file: .*\.ids / \.off"):
+                bpe.encode_file(path, out=prefix, chunk_bytes=chunk)
+            ids, off = bpe.encode_file(path, chunk_bytes=chunk)
+            assert ids.tolist() == h_ids.tolist() and off.tolist() == h_off.tolist(), (full, chunk)
+
+
 def check_cli(tmp_path, name="readme_small"):
     """`yttm encode_file` writes the same two files"""
     core = core_of(name)

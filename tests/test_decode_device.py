@@ -1,4 +1,4 @@
-"""Device decode and the device-to-device exits of the encoder on GPU-less machines: the UNMODIFIED product sources (k_decode.h, host_decode.h)
+"""Device decode and the device-to-device exits of the encoder on GPU-less machines: the UNMODIFIED product sources (k_decode.h, host_decode.cpp)
 built against the HIP emulator, where numpy arrays serve as device memory.  The cases live in decode_checks.py; test_gpu_decode.py runs the
 same ones on a real MI355X."""
 import pytest

@@ -67,6 +67,10 @@ def test_file_edges_and_errors(tmp_path):
     K.check_file_edges(tmp_path)
 
 
+def test_file_write_failure_releases_the_lanes(tmp_path):
+    K.check_file_write_failure(tmp_path)
+
+
 def test_command_line(tmp_path):
     K.check_cli(tmp_path)
 

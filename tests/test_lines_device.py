@@ -1,4 +1,4 @@
-"""The line split and the encoder's entries for unsplit text on GPU-less machines: the UNMODIFIED product sources (k_lines.h, host_lines.h) built
+"""The line split and the encoder's entries for unsplit text on GPU-less machines: the UNMODIFIED product sources (k_lines.h, host_lines.cpp) built
 against the HIP emulator, where numpy arrays serve as device memory.  The cases live in lines_checks.py; test_gpu_lines.py runs the same
 ones on a real MI355X."""
 import pytest
@@ -57,6 +57,10 @@ def test_file_in_pieces(name, tmp_path):
 
 def test_file_edges_and_errors(tmp_path):
     K.check_file_edges(tmp_path)
+
+
+def test_file_write_failure_releases_the_lanes(tmp_path):
+    K.check_file_write_failure(tmp_path)
 
 
 def test_command_line(tmp_path):

@@ -1,0 +1,208 @@
+// enc_lanes.h -- what the encoder's host units (host_encoder.cpp, host_decode.cpp, host_lines.cpp) share: the lanes and their device buffers,
+// the model's device state, and the small helpers every entry point is built from.  Internal: nothing outside these three units includes it.
+#pragma once
+#include <atomic>
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <string>
+
+#include "gpu_ctx.h"
+#include "host_core.h"
+
+namespace yttm {
+
+// One device allocation and its capacity in elements, freed with its owner.
+template <class T>
+struct DevBuf {
+  T *p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+  ~DevBuf() { release(); }
+  operator T *() const { return p; }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  void alloc(size_t n) {  // exactly n elements (at least one), whatever was there before
+    release();
+    void *q = nullptr;
+    HIP_CHECK(hipMalloc(&q, (n ? n : 1) * sizeof(T)));
+    p = (T *)q;
+    cap = n ? n : 1;
+  }
+  void grow(size_t need) {  // room for `need` elements and a quarter more; the contents are NOT kept (freed first: never two generations at once)
+    if (need > cap) alloc(need + need / 4 + 64);
+  }
+};
+
+// One batch in flight: a stream and the batch buffers, reused and grown on demand.  Two lanes per encoder, so that two host
+// threads (Python threads calling encode() on one BPE object -- ctypes releases the GIL, the reference's Cython binding did
+// not --, or the two workers of encode_cli) overlap their copies and kernels instead of racing on one set of buffers.
+// The results of the device-resident entries (encode, decode, line split) live side by side in buffers of their own: each is pending until the
+// next call of its own kind, whatever the others do.
+struct EncodeLane {
+  std::mutex mu;  // held for the whole of upload -> encode -> fetch
+  hipStream_t st = nullptr;
+  struct {  // a host-to-host batch or a file piece: its text and offsets
+    DevBuf<uint8_t> bytes;
+    DevBuf<unsigned long long> off;
+  } in;
+  struct {  // K5: ids per item as the kernel leaves them, its per-wave HBM scratch, the counts and their scan (scan_counts, also the other groups')
+    DevBuf<int32_t> scratch;
+    DevBuf<uint32_t> work, drop, counts;
+    DevBuf<unsigned long long> scan_tmp, total;
+  } k5;
+  struct {  // the encode result
+    DevBuf<int32_t> ids;
+    DevBuf<unsigned long long> off, misc;  // misc[0]: longest row (k_enc_longest)
+    unsigned long long n_ids = 0, n_sent = 0;
+  } res;
+  struct {  // word cache (k_wcache.hip): the batch's table of distinct words, the slot of every occurrence, the list K5 encodes, its ids
+    DevBuf<unsigned long long> slot, pos, extra, blk_off, ustart, uend;
+    DevBuf<uint32_t> occ, blk, uslot, ucounts;
+    DevBuf<unsigned int> misc;                 // [0] number of uncached words, [1] status
+    unsigned long long distinct_words = 0;     // of the last cached batch (0: the batch went straight through K5)
+  } wc;
+  struct {  // device decode (host_decode.cpp)
+    DevBuf<uint32_t> len, ign;  // ign: ignore bitmap, then the ignored ids outside [0, vocab)
+    DevBuf<unsigned long long> off, misc;  // misc[0]: smallest flat index of an invalid id
+    DevBuf<uint8_t> bytes;
+    unsigned long long n_sent = 0, n_bytes = 0;
+    bool valid = false;
+  } dec;
+  struct {  // line split (host_lines.cpp): newlines per tile, their scan, the lines' offsets
+    DevBuf<uint32_t> cnt;
+    DevBuf<unsigned long long> rank, off, misc;  // misc[0]: longest line (k_lines_longest)
+    unsigned long long n_lines = 0, n_bytes = 0, longest = 0;
+    bool valid = false;
+  } ln;
+
+  void init() {  // (on the encoder's device) the stream and the small fixed blocks
+    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    k5.total.alloc(2);
+    wc.misc.alloc(2);
+    res.misc.alloc(1);
+    dec.misc.alloc(1);
+    ln.misc.alloc(1);
+  }
+  ~EncodeLane() {
+    if (st) (void)hipStreamDestroy(st);
+  }
+};
+
+struct EncoderDevice {
+  DevBuf<uint32_t> cpmap, rule_z, bloom;
+  DevBuf<RuleSlot> rules;
+  DevBuf<unsigned long long> rule_xy;
+  EncModel m{};
+  std::shared_ptr<const Config> cfg;  // the hooks as they stood at creation (BaseEncoder::config)
+  // BPE-dropout draws: counter-based, seeded per call from a per-encoder random salt (the reference draws from a
+  // std::random_device-independent global mt19937, bpe.cpp:1415; YTTM_DROPOUT_SEED pins the salt for reproducible runs)
+  std::atomic<unsigned long long> dropout_calls{0};
+  unsigned long long seed_salt = 0;
+  // word cache: 0 = never, 1 = whenever it applies (no dropout), 2 = for batches of at least cache_min_bytes (YTTM_ENCODE_CACHE = 0 | 1;
+  // YTTM_ENCODE_CACHE_MIN_MB moves the threshold)
+  int cache_mode = 2;
+  unsigned long long cache_min_bytes = 8ull << 20;  // (tools/dbg/cache_crossover.py: text 0.9x at 4 MB, 1.1x at 8, 2.3x at 32, 3.2x at 128; random words break even at ~10 MB)
+  static constexpr int N_LANES = 2;
+  EncodeLane lane[N_LANES];
+  std::atomic<unsigned int> next_lane{0};
+  std::atomic<unsigned long long> last_distinct_words{0};  // of the most recent batch (cache_words())
+  // piece table of the device decode (host_decode.cpp), made at the first device decode
+  std::mutex dec_mu;
+  bool dec_ready = false;
+  DevBuf<uint8_t> piece_blob;
+  DevBuf<uint32_t> piece_off;
+  uint32_t dec_vocab = 0;
+  // a free lane, locked (falls back to waiting for the caller's turn-based choice)
+  // (Lane 0 last: the device-resident pair encode_device / fetch_device_result keeps its result there, unlocked, between the two
+  // calls -- a host-to-host encode from another thread in between takes another lane while one is free.)
+  EncodeLane &acquire(std::unique_lock<std::mutex> &lk) {
+    for (int k = N_LANES - 1; k >= 0; k--) {
+      lk = std::unique_lock<std::mutex>(lane[k].mu, std::try_to_lock);
+      if (lk.owns_lock()) return lane[k];
+    }
+    EncodeLane &l = lane[N_LANES - 1 - next_lane.fetch_add(1) % N_LANES];
+    lk = std::unique_lock<std::mutex>(l.mu);
+    return l;
+  }
+};
+
+// Start and stop events on a lane's stream for a call that reports its kernel time; does nothing when made with on == false.
+struct EventPair {
+  hipStream_t st;
+  bool on;
+  hipEvent_t a = nullptr, b = nullptr;
+  EventPair(hipStream_t stream, bool enabled) : st(stream), on(enabled) {}
+  EventPair(const EventPair &) = delete;
+  EventPair &operator=(const EventPair &) = delete;
+  ~EventPair() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+  void start() {
+    if (!on) return;
+    HIP_CHECK(hipEventCreate(&a));
+    HIP_CHECK(hipEventCreate(&b));
+    HIP_CHECK(hipEventRecord(a, st));
+  }
+  void stop(bool wait = false) {  // wait: for the stop event itself (else the caller synchronises the stream before elapsed_ms)
+    if (!on) return;
+    HIP_CHECK(hipEventRecord(b, st));
+    if (wait) HIP_CHECK(hipEventSynchronize(b));
+  }
+  double elapsed_ms() const {
+    float ms = 0;
+    if (on) HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+    return ms;
+  }
+};
+
+// body() -> Status on `device`; a GpuError thrown inside it becomes the call's status
+template <class F>
+Status on_device(int device, F &&body) {
+  try {
+    HIP_CHECK(hipSetDevice(device));
+    return body();
+  } catch (const GpuError &e) {
+    return Status(2, "GPU error: " + e.msg);
+  }
+}
+
+Status check_bos_eos(const BaseEncoder &enc, bool bos, bool eos);  // bpe.cpp:1702-1707: the reference's two messages, before any work
+
+// K5 on one lane (locked by the caller): input already in HBM, ids + offsets left in the lane's result buffers
+Status encode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_bytes, const void *d_offsets,
+                      unsigned long long n_sent, unsigned long long total_bytes, unsigned long long max_sentence_bytes, bool bos, bool eos, bool reverse,
+                      double dropout_prob, unsigned long long *n_ids_out, double *kernel_ms);
+// counts -> offsets (exclusive scan, the total behind the last one and on the host); synchronises the lane's stream
+unsigned long long scan_counts(EncodeLane &d, const uint32_t *counts, unsigned long long n, unsigned long long *off);
+
+// Host arrays of a large batch cross the link through the trainer's pinned chunks (gpu_ctx.cpp staged_transfer; 1e7 sentences are 1.3 GB up
+// and 1.2 GB down: a plain copy from / to pageable memory moves them at a fraction of the link's rate, and the first touch of a freshly
+// allocated result array is paid by one thread); small ones as plain copies on the lane's stream.
+constexpr size_t ENC_CHUNK = 2u << 20;  // (the encoder's arrays in chunks of 2 MB: 10^7 sentences host -> host 79 -> 75 ms against 8 MB, 64 against 70 in sub-batches)
+void copy_up(int device, void *d_dst, const void *src, size_t n, hipStream_t st);
+void copy_down(int device, void *dst, const void *d_src, size_t n, hipStream_t st);
+// A result of the lane device to device, into memory the caller owns (a framework's tensors): n_a bytes of src_a and the offsets[n_sent + 1] on
+// the lane's stream, then the stream's sync; a null destination is skipped.  n_sent == 0: nothing was launched and no buffer exists, the one
+// offset is 0.
+Status copy_out_device(int device, EncodeLane &d, void *dst_a, const void *src_a, size_t n_a, void *dst_off, const unsigned long long *src_off,
+                       unsigned long long n_sent);
+void *result_alloc(size_t bytes);  // a result array the caller releases with free(); a large one in huge pages
+
+// Items 0, 1, 2, ... through the encoder's two lanes (both locked by the caller), item i on lane i & 1, as three legs at once: upload(i) on a
+// thread of its own, work(i) on the calling thread, download(i) on a third.  upload(i) starts once download(i - 2) has finished (the lane's buffers
+// are free again), work(i) after upload(i), download(i) after work(i).  There are n_items items, or -- n_items == PIPE_UNTIL_EXHAUSTED -- as
+// many as upload finds: it sets *exhausted where there is no item i.  Every thread binds `cfg` and sets the device; the first failure -- a
+// leg's status with its code, or anything a leg throws, named after `who` -- ends all three and is returned.  *n_done: the items worked on.
+constexpr size_t PIPE_UNTIL_EXHAUSTED = ~(size_t)0;
+Status run_two_lanes(const char *who, const std::shared_ptr<const Config> &cfg, int device, size_t n_items,
+                     const std::function<Status(size_t i, bool *exhausted)> &upload, const std::function<Status(size_t i)> &work,
+                     const std::function<Status(size_t i)> &download, size_t *n_done = nullptr);
+
+}  // namespace yttm

@@ -114,7 +114,7 @@ class BaseEncoder {  // bpe.h:22-82
                        unsigned long long max_sentence_bytes, bool bos, bool eos, bool reverse, double dropout_prob,
                        unsigned long long *n_ids_out, double *kernel_ms) const;
   Status fetch_device_result(int32_t *ids, unsigned long long *out_off, unsigned long long n_sent) const;
-  // device decode (host_decode.h, k_decode.h): ids + offsets (or a padded matrix) already in HBM, the text left in HBM in lane 0 next to the
+  // device decode (host_decode.cpp, k_decode.h): ids + offsets (or a padded matrix) already in HBM, the text left in HBM in lane 0 next to the
   // encode result; ignore_ids is a host array.  replaces decode(), bpe.h:52-54, bpe.cpp:1828-1861, for a batch
   Status decode_device(const void *d_ids, const void *d_offsets, unsigned long long n_sent, unsigned long long n_ids, const int32_t *ignore_ids,
                        unsigned long long n_ignore, unsigned long long *n_bytes, double *kernel_ms) const;
@@ -126,7 +126,7 @@ class BaseEncoder {  // bpe.h:22-82
   Status copy_encode_result(void *d_ids, void *d_out_off, unsigned long long n_sent) const;
   Status copy_encode_padded(void *d_matrix, void *d_lengths, unsigned long long n_sent, unsigned long long width, int32_t pad_value,
                             unsigned long long *longest) const;
-  // text that is not cut into sentences yet (host_lines.h, k_lines.h): its lines by std::getline's rules, found on the device.  lines_device leaves
+  // text that is not cut into sentences yet (host_lines.cpp, k_lines.h): its lines by std::getline's rules, found on the device.  lines_device leaves
   // uint64 offsets[n_lines + 1] (line i WITH its newline) in lane 0, beside a pending encode / decode result; take_lines copies them out.
   Status lines_device(const void *d_text, unsigned long long n_bytes, unsigned long long *n_lines, unsigned long long *longest, double *kernel_ms) const;
   Status take_lines(void *offsets, unsigned long long n_lines, bool to_device) const;

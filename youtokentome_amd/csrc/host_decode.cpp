@@ -1,9 +1,11 @@
-// host_decode.h -- host side of the device decode (k_decode.h) and the device-to-device exits of the encoder's and the decoder's results.
-// Part of host_encoder.cpp (included there: it works on the encoder's lanes).
+// host_decode.cpp -- host side of the device decode (k_decode.h) and the device-to-device exits of the encoder's and the decoder's results,
+// on the encoder's lanes (enc_lanes.h).
 //
 // Results live in lane 0 like those of encode_device, in buffers of their own: a decode leaves a pending encode result alone and the other way
 // round.  Every call locks the lane and returns after the lane's stream has synchronised; a pair (decode_device, fetch) is not atomic.
-#pragma once
+#include <algorithm>
+
+#include "enc_lanes.h"
 
 namespace yttm {
 
@@ -29,19 +31,14 @@ static void decode_table(const BaseEncoder &enc, EncoderDevice &D) {
   }
   if (blob.size() >= (size_t)DEC_INVALID) throw GpuError{"decode: the vocabulary's text does not fit 2 GB"};
   off[(size_t)V] = (uint32_t)blob.size();
-  uint8_t *d_blob = dalloc<uint8_t>(blob.size() + 1);
-  uint32_t *d_off = nullptr;
-  try {
-    d_off = dalloc<uint32_t>(off.size());
-    if (!blob.empty()) HIP_CHECK(hipMemcpy(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-  } catch (...) {
-    (void)hipFree(d_blob);
-    if (d_off) (void)hipFree(d_off);
-    throw;
-  }
-  D.d_piece_blob = d_blob;
-  D.d_piece_off = d_off;
+  DevBuf<uint8_t> d_blob;  // (handed to the encoder once both are filled)
+  DevBuf<uint32_t> d_off;
+  d_blob.alloc(blob.size() + 1);
+  d_off.alloc(off.size());
+  if (!blob.empty()) HIP_CHECK(hipMemcpy(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+  D.piece_blob = std::move(d_blob);
+  D.piece_off = std::move(d_off);
   D.dec_vocab = (uint32_t)V;
   D.dec_ready = true;
 }
@@ -49,26 +46,17 @@ static void decode_table(const BaseEncoder &enc, EncoderDevice &D) {
 // measure -> scan -> write on the lane (locked by the caller).  n_flat: the ids the kernels walk (ragged: n_ids; padded: n_sent * stride).
 static Status decode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, DecInput in, unsigned long long n_flat,
                              const int32_t *ignore_ids, unsigned long long n_ignore, unsigned long long *n_bytes, double *kernel_ms) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  struct Events {
-    hipEvent_t &a, &b;
-    ~Events() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } events{e0, e1};
-  try {
-    HIP_CHECK(hipSetDevice(device));
-    d.dec_valid = false;
+  return on_device(device, [&]() -> Status {
+    d.dec.valid = false;
     if (n_bytes) *n_bytes = 0;
     if (kernel_ms) *kernel_ms = 0;
     if (in.n_sent == 0) {
-      d.dec_n_sent = d.dec_n_bytes = 0;
-      d.dec_valid = true;
+      d.dec.n_sent = d.dec.n_bytes = 0;
+      d.dec.valid = true;
       return Status();
     }
     decode_table(enc, D);
-    const DecTable tb{D.d_piece_blob, D.d_piece_off, D.dec_vocab};
+    const DecTable tb{D.piece_blob, D.piece_off, D.dec_vocab};
     DecIgnore ig{nullptr, nullptr, 0, 0};
     if (n_ignore) {
       const size_t words = ((size_t)D.dec_vocab + 31) / 32 + 1;
@@ -82,23 +70,19 @@ static Status decode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLan
       std::sort(extra.begin(), extra.end());
       extra.erase(std::unique(extra.begin(), extra.end()), extra.end());
       for (int32_t id : extra) host.push_back((uint32_t)id);
-      d.grow(d.d_dec_ign, d.cap_dec_ign, host.size());
-      HIP_CHECK(hipMemcpy(d.d_dec_ign, host.data(), host.size() * 4, hipMemcpyHostToDevice));  // (the lane's stream is idle; the vector ends with this call)
-      ig = DecIgnore{d.d_dec_ign, (const int32_t *)(d.d_dec_ign + words), (uint32_t)extra.size(), 1u};
+      d.dec.ign.grow(host.size());
+      HIP_CHECK(hipMemcpy(d.dec.ign, host.data(), host.size() * 4, hipMemcpyHostToDevice));  // (the lane's stream is idle; the vector ends with this call)
+      ig = DecIgnore{d.dec.ign, (const int32_t *)(d.dec.ign + words), (uint32_t)extra.size(), 1u};
     }
-    if (!d.d_dec_misc) d.d_dec_misc = dalloc<unsigned long long>(2);
-    d.grow(d.d_dec_len, d.cap_dec_len, (size_t)in.n_sent);
-    d.grow(d.d_dec_off, d.cap_dec_off, (size_t)in.n_sent + 1);
-    if (kernel_ms) {
-      HIP_CHECK(hipEventCreate(&e0));
-      HIP_CHECK(hipEventCreate(&e1));
-      HIP_CHECK(hipEventRecord(e0, d.st));
-    }
-    HIP_CHECK(hipMemsetAsync(d.d_dec_misc, 0xff, 8, d.st));
-    launch_decode_measure(in, tb, ig, n_flat, d.d_dec_len, d.d_dec_misc, d.st);
+    d.dec.len.grow((size_t)in.n_sent);
+    d.dec.off.grow((size_t)in.n_sent + 1);
+    EventPair ev(d.st, kernel_ms != nullptr);
+    ev.start();
+    HIP_CHECK(hipMemsetAsync(d.dec.misc, 0xff, 8, d.st));
+    launch_decode_measure(in, tb, ig, n_flat, d.dec.len, d.dec.misc, d.st);
     unsigned long long bad = ~0ull;
-    HIP_CHECK(hipMemcpyAsync(&bad, d.d_dec_misc, 8, hipMemcpyDeviceToHost, d.st));
-    const unsigned long long total = scan_counts(d, d.d_dec_len, in.n_sent, d.d_dec_off);  // (syncs: `bad` is here)
+    HIP_CHECK(hipMemcpyAsync(&bad, d.dec.misc, 8, hipMemcpyDeviceToHost, d.st));
+    const unsigned long long total = scan_counts(d, d.dec.len, in.n_sent, d.dec.off);  // (syncs: `bad` is here)
     if (bad != ~0ull) {  // the first id, in sentence order then position order, that is neither ignored nor valid: the host path's message
       int32_t id = 0;
       HIP_CHECK(hipMemcpyAsync(&id, in.ids + bad, 4, hipMemcpyDeviceToHost, d.st));
@@ -107,24 +91,18 @@ static Status decode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLan
       Status st = enc.id_to_subword(id, &piece, true);
       return st.ok() ? Status(1, "decode: no text for id " + std::to_string(id)) : st;
     }
-    d.grow(d.d_dec_bytes, d.cap_dec_bytes, (size_t)total + 16);
-    if (((uintptr_t)d.d_dec_bytes & 15u) != 0) throw GpuError{"decode: the output blob is not 16-byte aligned"};
-    launch_decode_write(in, tb, ig, n_flat, d.d_dec_off, d.d_dec_bytes, d.st);
-    if (kernel_ms) HIP_CHECK(hipEventRecord(e1, d.st));
+    d.dec.bytes.grow((size_t)total + 16);
+    if (((uintptr_t)d.dec.bytes.p & 15u) != 0) throw GpuError{"decode: the output blob is not 16-byte aligned"};
+    launch_decode_write(in, tb, ig, n_flat, d.dec.off, d.dec.bytes, d.st);
+    ev.stop();
     HIP_CHECK(hipStreamSynchronize(d.st));
-    if (kernel_ms) {
-      float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      *kernel_ms = ms;
-    }
-    d.dec_n_sent = in.n_sent;
-    d.dec_n_bytes = total;
-    d.dec_valid = true;
+    if (kernel_ms) *kernel_ms = ev.elapsed_ms();
+    d.dec.n_sent = in.n_sent;
+    d.dec.n_bytes = total;
+    d.dec.valid = true;
     if (n_bytes) *n_bytes = total;
-  } catch (const GpuError &e) {
-    return Status(2, "GPU error: " + e.msg);
-  }
-  return Status();
+    return Status();
+  });
 }
 
 Status BaseEncoder::decode_device(const void *d_ids, const void *d_offsets, unsigned long long n_sent, unsigned long long n_ids, const int32_t *ignore_ids,
@@ -155,30 +133,14 @@ Status BaseEncoder::fetch_decode_result(char *bytes, unsigned long long *out_off
   const CfgBind bind(dev_->cfg);
   EncodeLane &d = dev_->lane[0];
   std::lock_guard<std::mutex> lk(d.mu);
-  if (!d.dec_valid || n_sent != d.dec_n_sent) return Status(2, "fetch_decode_result: no matching result");
-  try {
-    HIP_CHECK(hipSetDevice(device_));
+  if (!d.dec.valid || n_sent != d.dec.n_sent) return Status(2, "fetch_decode_result: no matching result");
+  return on_device(device_, [&]() -> Status {
     if (n_sent == 0) { if (out_off) out_off[0] = 0; return Status(); }
-    if (bytes && d.dec_n_bytes) copy_down(device_, bytes, d.d_dec_bytes, (size_t)d.dec_n_bytes, d.st);
-    if (out_off) copy_down(device_, out_off, d.d_dec_off, (size_t)(n_sent + 1) * 8, d.st);
+    if (bytes && d.dec.n_bytes) copy_down(device_, bytes, d.dec.bytes, (size_t)d.dec.n_bytes, d.st);
+    if (out_off) copy_down(device_, out_off, d.dec.off, (size_t)(n_sent + 1) * 8, d.st);
     HIP_CHECK(hipStreamSynchronize(d.st));
-  } catch (const GpuError &e) {
-    return Status(2, "GPU error: " + e.msg);
-  }
-  return Status();
-}
-
-// device to device, into memory the caller owns (a framework's tensors): src -> dst on the lane's stream, then the stream's sync
-static Status copy_pair_device(int device, EncodeLane &d, void *dst_a, const void *src_a, size_t n_a, void *dst_b, const void *src_b, size_t n_b) {
-  try {
-    HIP_CHECK(hipSetDevice(device));
-    if (dst_a && n_a) HIP_CHECK(hipMemcpyAsync(dst_a, src_a, n_a, hipMemcpyDeviceToDevice, d.st));
-    if (dst_b && n_b) HIP_CHECK(hipMemcpyAsync(dst_b, src_b, n_b, hipMemcpyDeviceToDevice, d.st));
-    HIP_CHECK(hipStreamSynchronize(d.st));
-  } catch (const GpuError &e) {
-    return Status(2, "GPU error: " + e.msg);
-  }
-  return Status();
+    return Status();
+  });
 }
 
 Status BaseEncoder::copy_decode_result(void *d_bytes, void *d_out_off, unsigned long long n_sent) const {
@@ -186,18 +148,8 @@ Status BaseEncoder::copy_decode_result(void *d_bytes, void *d_out_off, unsigned 
   const CfgBind bind(dev_->cfg);
   EncodeLane &d = dev_->lane[0];
   std::lock_guard<std::mutex> lk(d.mu);
-  if (!d.dec_valid || n_sent != d.dec_n_sent) return Status(2, "copy_decode_result: no matching result");
-  if (n_sent == 0) {  // (nothing was launched and no buffer exists: the one offset is 0)
-    try {
-      HIP_CHECK(hipSetDevice(device_));
-      if (d_out_off) HIP_CHECK(hipMemsetAsync(d_out_off, 0, 8, d.st));
-      HIP_CHECK(hipStreamSynchronize(d.st));
-    } catch (const GpuError &e) {
-      return Status(2, "GPU error: " + e.msg);
-    }
-    return Status();
-  }
-  return copy_pair_device(device_, d, d_bytes, d.d_dec_bytes, (size_t)d.dec_n_bytes, d_out_off, d.d_dec_off, (size_t)(n_sent + 1) * 8);
+  if (!d.dec.valid || n_sent != d.dec.n_sent) return Status(2, "copy_decode_result: no matching result");
+  return copy_out_device(device_, d, d_bytes, d.dec.bytes, (size_t)d.dec.n_bytes, d_out_off, d.dec.off, n_sent);
 }
 
 Status BaseEncoder::copy_encode_result(void *d_ids, void *d_out_off, unsigned long long n_sent) const {
@@ -205,18 +157,8 @@ Status BaseEncoder::copy_encode_result(void *d_ids, void *d_out_off, unsigned lo
   const CfgBind bind(dev_->cfg);
   EncodeLane &d = dev_->lane[0];
   std::lock_guard<std::mutex> lk(d.mu);
-  if (n_sent != d.last_n_sent) return Status(2, "copy_encode_result: no matching result");
-  if (n_sent == 0) {
-    try {
-      HIP_CHECK(hipSetDevice(device_));
-      if (d_out_off) HIP_CHECK(hipMemsetAsync(d_out_off, 0, 8, d.st));
-      HIP_CHECK(hipStreamSynchronize(d.st));
-    } catch (const GpuError &e) {
-      return Status(2, "GPU error: " + e.msg);
-    }
-    return Status();
-  }
-  return copy_pair_device(device_, d, d_ids, d.d_ids, (size_t)d.last_n_ids * 4, d_out_off, d.d_out_off, (size_t)(n_sent + 1) * 8);
+  if (n_sent != d.res.n_sent) return Status(2, "copy_encode_result: no matching result");
+  return copy_out_device(device_, d, d_ids, d.res.ids, (size_t)d.res.n_ids * 4, d_out_off, d.res.off, n_sent);
 }
 
 Status BaseEncoder::copy_encode_padded(void *d_matrix, void *d_lengths, unsigned long long n_sent, unsigned long long width, int32_t pad_value,
@@ -226,15 +168,13 @@ Status BaseEncoder::copy_encode_padded(void *d_matrix, void *d_lengths, unsigned
   const CfgBind bind(dev_->cfg);
   EncodeLane &d = dev_->lane[0];
   std::lock_guard<std::mutex> lk(d.mu);
-  if (n_sent != d.last_n_sent) return Status(2, "copy_encode_padded: no matching result");
+  if (n_sent != d.res.n_sent) return Status(2, "copy_encode_padded: no matching result");
   if (n_sent == 0) return Status();
-  try {
-    HIP_CHECK(hipSetDevice(device_));
-    if (!d.d_dec_misc) d.d_dec_misc = dalloc<unsigned long long>(2);
-    HIP_CHECK(hipMemsetAsync(d.d_dec_misc + 1, 0, 8, d.st));
-    launch_enc_longest(d.d_out_off, n_sent, (unsigned int *)(d.d_dec_misc + 1), d.st);
+  return on_device(device_, [&]() -> Status {
+    HIP_CHECK(hipMemsetAsync(d.res.misc, 0, 8, d.st));
+    launch_enc_longest(d.res.off, n_sent, (unsigned int *)d.res.misc.p, d.st);
     unsigned long long need = 0;
-    HIP_CHECK(hipMemcpyAsync(&need, d.d_dec_misc + 1, 8, hipMemcpyDeviceToHost, d.st));
+    HIP_CHECK(hipMemcpyAsync(&need, d.res.misc, 8, hipMemcpyDeviceToHost, d.st));
     HIP_CHECK(hipStreamSynchronize(d.st));
     if (longest) *longest = need;
     if (need > width)  // nothing is truncated, and nothing was written
@@ -242,12 +182,10 @@ Status BaseEncoder::copy_encode_padded(void *d_matrix, void *d_lengths, unsigned
     if (need > 0x7fffffffull) return Status(2, "copy_encode_padded: a row is too long for int32 lengths");
     if (!d_matrix || !d_lengths) return Status(2, "copy_encode_padded: no output");
     if (((uintptr_t)d_matrix & 3u) != 0) return Status(2, "copy_encode_padded: the matrix must be 4-byte aligned");
-    launch_enc_pad(d.d_ids, d.d_out_off, n_sent, width, pad_value, (int32_t *)d_matrix, (int32_t *)d_lengths, d.st);
+    launch_enc_pad(d.res.ids, d.res.off, n_sent, width, pad_value, (int32_t *)d_matrix, (int32_t *)d_lengths, d.st);
     HIP_CHECK(hipStreamSynchronize(d.st));
-  } catch (const GpuError &e) {
-    return Status(2, "GPU error: " + e.msg);
-  }
-  return Status();
+    return Status();
+  });
 }
 
 }  // namespace yttm

@@ -1,65 +1,53 @@
-// host_lines.h -- host side of the line split (k_lines.h) and the encoder's entries for text that is not yet cut into sentences: a buffer in HBM
-// (lines_device, encode_text_device) and a file of any size (encode_file).
-// Part of host_encoder.cpp (included at its end: it works on the encoder's lanes and uses encode_on_lane, staged_transfer and result_alloc).
+// host_lines.cpp -- host side of the line split (k_lines.h) and the encoder's entries for text that is not yet cut into sentences: a buffer in HBM
+// (lines_device, encode_text_device) and a file of any size (encode_file), on the encoder's lanes (enc_lanes.h).
 //
 // The offsets of a split live in the lane like the results of encode_device and decode_device, in buffers of their own: a split leaves a pending
 // encode or decode result alone.  Every call locks the lane and returns after the lane's stream has synchronised.
-#pragma once
 #include <errno.h>
 #include <fcntl.h>
+#include <string.h>
 #include <sys/stat.h>
 #include <unistd.h>
+
+#include <algorithm>
+#include <chrono>
+
+#include "enc_lanes.h"
 
 namespace yttm {
 
 // count -> scan -> write -> longest on the lane (locked by the caller).  Throws GpuError.
 static void split_on_lane(EncodeLane &d, const void *d_text, unsigned long long n_bytes, unsigned long long *n_lines_out, unsigned long long *longest_out,
                           double *kernel_ms) {
-  d.ln_valid = false;
+  d.ln.valid = false;
   if (kernel_ms) *kernel_ms = 0;
   unsigned long long n_lines = 0, longest = 0;
   if (n_bytes) {
     const uint8_t *text = (const uint8_t *)d_text;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    struct Events {
-      hipEvent_t &a, &b;
-      ~Events() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-      }
-    } events{e0, e1};
-    if (kernel_ms) {
-      HIP_CHECK(hipEventCreate(&e0));
-      HIP_CHECK(hipEventCreate(&e1));
-      HIP_CHECK(hipEventRecord(e0, d.st));
-    }
+    EventPair ev(d.st, kernel_ms != nullptr);
+    ev.start();
     const unsigned long long n_tiles = lines_tiles(d_text, n_bytes);
     unsigned long long inner = 0;  // newlines in front of the last byte: each one starts a line
     if (n_tiles) {
-      d.grow(d.d_ln_cnt, d.cap_ln_cnt, (size_t)n_tiles);
-      d.grow(d.d_ln_rank, d.cap_ln_rank, (size_t)n_tiles + 1);
-      launch_lines_count(text, n_bytes, d.d_ln_cnt, d.st);
-      inner = scan_counts(d, d.d_ln_cnt, n_tiles, d.d_ln_rank);  // (syncs)
+      d.ln.cnt.grow((size_t)n_tiles);
+      d.ln.rank.grow((size_t)n_tiles + 1);
+      launch_lines_count(text, n_bytes, d.ln.cnt, d.st);
+      inner = scan_counts(d, d.ln.cnt, n_tiles, d.ln.rank);  // (syncs)
     }
     n_lines = inner + 1;
-    d.grow(d.d_ln_off, d.cap_ln_off, (size_t)n_lines + 1);
-    if (!d.d_ln_misc) d.d_ln_misc = dalloc<unsigned long long>(1);
-    HIP_CHECK(hipMemsetAsync(d.d_ln_misc, 0, 8, d.st));
-    launch_lines_write(text, n_bytes, d.d_ln_rank, d.d_ln_off, n_lines, d.st);
-    launch_lines_longest(d.d_ln_off, n_lines, d.d_ln_misc, d.st);
-    if (kernel_ms) HIP_CHECK(hipEventRecord(e1, d.st));
-    HIP_CHECK(hipMemcpyAsync(&longest, d.d_ln_misc, 8, hipMemcpyDeviceToHost, d.st));
+    d.ln.off.grow((size_t)n_lines + 1);
+    HIP_CHECK(hipMemsetAsync(d.ln.misc, 0, 8, d.st));
+    launch_lines_write(text, n_bytes, d.ln.rank, d.ln.off, n_lines, d.st);
+    launch_lines_longest(d.ln.off, n_lines, d.ln.misc, d.st);
+    ev.stop();
+    HIP_CHECK(hipMemcpyAsync(&longest, d.ln.misc, 8, hipMemcpyDeviceToHost, d.st));
     HIP_CHECK(hipStreamSynchronize(d.st));
-    if (kernel_ms) {
-      float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      *kernel_ms = ms;
-    }
+    if (kernel_ms) *kernel_ms = ev.elapsed_ms();
   }
-  d.ln_n_lines = n_lines;
-  d.ln_n_bytes = n_bytes;
-  d.ln_longest = longest;
-  d.ln_valid = true;
+  d.ln.n_lines = n_lines;
+  d.ln.n_bytes = n_bytes;
+  d.ln.longest = longest;
+  d.ln.valid = true;
   if (n_lines_out) *n_lines_out = n_lines;
   if (longest_out) *longest_out = longest;
 }
@@ -73,13 +61,10 @@ Status BaseEncoder::lines_device(const void *d_text, unsigned long long n_bytes,
   const CfgBind bind(dev_->cfg);
   EncodeLane &d = dev_->lane[0];
   std::lock_guard<std::mutex> lk(d.mu);
-  try {
-    HIP_CHECK(hipSetDevice(device_));
+  return on_device(device_, [&]() -> Status {
     split_on_lane(d, d_text, n_bytes, n_lines, longest, kernel_ms);
-  } catch (const GpuError &e) {
-    return Status(2, "GPU error: " + e.msg);
-  }
-  return Status();
+    return Status();
+  });
 }
 
 // the offsets of the last lines_device / encode_text_device: to a host array (to_device == false) or to device memory the caller owns
@@ -89,41 +74,31 @@ Status BaseEncoder::take_lines(void *offsets, unsigned long long n_lines, bool t
   const CfgBind bind(dev_->cfg);
   EncodeLane &d = dev_->lane[0];
   std::lock_guard<std::mutex> lk(d.mu);
-  if (!d.ln_valid || n_lines != d.ln_n_lines) return Status(2, who);
+  if (!d.ln.valid || n_lines != d.ln.n_lines) return Status(2, who);
   if (!offsets) return Status();
-  try {
-    HIP_CHECK(hipSetDevice(device_));
-    if (n_lines == 0) {  // (nothing was launched: the one offset is 0)
-      if (to_device) HIP_CHECK(hipMemsetAsync(offsets, 0, 8, d.st));
-      else *(unsigned long long *)offsets = 0;
-    } else if (to_device) {
-      HIP_CHECK(hipMemcpyAsync(offsets, d.d_ln_off, (size_t)(n_lines + 1) * 8, hipMemcpyDeviceToDevice, d.st));
-    } else {
-      copy_down(device_, offsets, d.d_ln_off, (size_t)(n_lines + 1) * 8, d.st);
-    }
+  if (to_device) return copy_out_device(device_, d, nullptr, nullptr, 0, offsets, d.ln.off, n_lines);
+  return on_device(device_, [&]() -> Status {
+    if (n_lines == 0) *(unsigned long long *)offsets = 0;  // (nothing was launched: the one offset is 0)
+    else copy_down(device_, offsets, d.ln.off, (size_t)(n_lines + 1) * 8, d.st);
     HIP_CHECK(hipStreamSynchronize(d.st));
-  } catch (const GpuError &e) {
-    return Status(2, "GPU error: " + e.msg);
-  }
-  return Status();
+    return Status();
+  });
 }
 
 // split, then the batch encoder on the lane's own offsets: the lines keep their newline, which is white space to the encoder
 static Status encode_text_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_text, unsigned long long n_bytes, bool bos,
                                   bool eos, bool reverse, double dropout_prob, unsigned long long *n_lines, unsigned long long *n_ids, double *split_ms,
                                   double *encode_ms) {
-  // bpe.cpp:1702-1707 (before any work, as every encode entry does)
-  if (bos && enc.bpe_state.special_tokens.bos_id == -1) return Status(1, "Can't add <BOS> token. Model was trained without it.");
-  if (eos && enc.bpe_state.special_tokens.eos_id == -1) return Status(1, "Can't add <EOS> token. Model was trained without it.");
+  Status s = check_bos_eos(enc, bos, eos);  // (before any work, as every encode entry does)
+  if (!s.ok()) return s;
   unsigned long long nl = 0, longest = 0;
-  try {
-    HIP_CHECK(hipSetDevice(device));
+  s = on_device(device, [&]() -> Status {
     split_on_lane(d, d_text, n_bytes, &nl, &longest, split_ms);
-  } catch (const GpuError &e) {
-    return Status(2, "GPU error: " + e.msg);
-  }
+    return Status();
+  });
+  if (!s.ok()) return s;
   if (n_lines) *n_lines = nl;
-  return encode_on_lane(enc, D, d, device, d_text, d.d_ln_off, nl, n_bytes, longest, bos, eos, reverse, dropout_prob, n_ids, encode_ms);
+  return encode_on_lane(enc, D, d, device, d_text, d.ln.off, nl, n_bytes, longest, bos, eos, reverse, dropout_prob, n_ids, encode_ms);
 }
 
 Status BaseEncoder::encode_text_device(const void *d_text, unsigned long long n_bytes, bool bos, bool eos, bool reverse, double dropout_prob,
@@ -145,7 +120,7 @@ Status BaseEncoder::encode_text_device(const void *d_text, unsigned long long n_
 // ---- a file of any size ------------------------------------------------------------------------------------------------------------------
 // The file crosses in pieces of about piece_bytes, each cut behind the last newline inside it (a line longer than a piece extends the piece
 // to that line's end), through both lanes: while piece k is split and encoded, piece k + 1 is read (pread into the pinned chunks of
-// staged_transfer) and uploaded and the ids of piece k - 1 come down -- three threads, as encode_pipelined.  The result is appended in file
+// staged_transfer) and uploaded and the ids of piece k - 1 come down (run_two_lanes).  The result is appended in file
 // order, the pieces' offsets moved behind the ids so far; it does not depend on the cuts (no word and no line crosses one).
 constexpr unsigned long long FILE_PIECE_DEFAULT = 256ull << 20;
 
@@ -224,8 +199,8 @@ Status BaseEncoder::encode_file(const std::string &path, const char *out_prefix,
   if (off_out) *off_out = nullptr;
   if (n_lines_out) *n_lines_out = 0;
   if (n_ids_out) *n_ids_out = 0;
-  if (bos && bpe_state.special_tokens.bos_id == -1) return Status(1, "Can't add <BOS> token. Model was trained without it.");
-  if (eos && bpe_state.special_tokens.eos_id == -1) return Status(1, "Can't add <EOS> token. Model was trained without it.");
+  const Status tokens = check_bos_eos(*this, bos, eos);
+  if (!tokens.ok()) return tokens;
   if (!dev_) return Status(2, "encoder has no device state");
   if (!out_prefix && (!ids_out || !off_out)) return Status(2, "encode_file: no output");
   if (!piece_bytes) piece_bytes = FILE_PIECE_DEFAULT;
@@ -254,180 +229,98 @@ Status BaseEncoder::encode_file(const std::string &path, const char *out_prefix,
 
   struct Piece {
     unsigned long long pos = 0, bytes = 0, n_lines = 0, n_ids = 0;
-  };
-  std::mutex mu;
-  std::condition_variable cv;
-  std::vector<Piece> pieces;  // (guarded by mu)
-  size_t up_n = 0, enc_n = 0, down_n = 0;
-  bool up_end = false, enc_end = false, failed = false;
-  int fail_code = 2;
-  std::string error;
-  auto fail = [&](int code, const std::string &msg) {
-    std::lock_guard<std::mutex> g(mu);
-    if (!failed) { error = msg; fail_code = code; }
-    failed = true;
-    cv.notify_all();
-  };
+  } piece[2];  // of the item in flight on each lane: upload(i) fills it, work(i) adds the counts, download(i) reads it
   double s_up = 0, s_split = 0, s_enc = 0, s_down = 0;
   Growing<int32_t> ids;
   Growing<unsigned long long> off;
-  unsigned long long lines_total = 0, ids_total = 0;
+  unsigned long long next_pos = 0, lines_total = 0, ids_total = 0;  // (the upload leg's; the download leg's two)
 
-  std::thread up([&] {
-    const CfgBind b(C);
+  auto upload = [&](size_t i, bool *exhausted) {
+    const unsigned long long pos = next_pos;
+    if (pos >= size) { *exhausted = true; return Status(); }
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned long long end = size;
+    if (!piece_end(in.fd, pos, piece_bytes, size, &end)) return Status(1, "Failed to read file: " + path);
+    const unsigned long long nb = end - pos;
+    EncodeLane &d = dev->lane[i & 1];
+    d.in.bytes.grow((size_t)nb + 16);
+    std::atomic<bool> read_ok{true};
     try {
-      HIP_CHECK(hipSetDevice(device));
-      unsigned long long pos = 0;
-      for (size_t i = 0; pos < size; i++) {
-        {
-          std::unique_lock<std::mutex> g(mu);
-          cv.wait(g, [&] { return failed || i < 2 || down_n + 2 > i; });  // the lane's buffers are free again
-          if (failed) break;
+      staged_transfer(device, d.in.bytes, nb, true, [&](void *chunk, unsigned long long o, size_t len) {
+        size_t got = 0;
+        while (got < len) {
+          const ssize_t r = pread(in.fd, (char *)chunk + got, len - got, (off_t)(pos + o + got));
+          if (r < 0 && errno == EINTR) continue;
+          if (r <= 0) { read_ok.store(false); return false; }  // (an error, or the file shrank)
+          got += (size_t)r;
         }
-        const auto t0 = std::chrono::steady_clock::now();
-        unsigned long long end = size;
-        if (!piece_end(in.fd, pos, piece_bytes, size, &end)) { fail(1, "Failed to read file: " + path); break; }
-        const unsigned long long nb = end - pos;
-        EncodeLane &d = dev->lane[i & 1];
-        d.grow(d.d_bytes, d.cap_bytes, (size_t)nb + 16);
-        std::atomic<bool> read_ok{true};
-        try {
-          staged_transfer(device, d.d_bytes, nb, true, [&](void *chunk, unsigned long long o, size_t len) {
-            size_t got = 0;
-            while (got < len) {
-              const ssize_t r = pread(in.fd, (char *)chunk + got, len - got, (off_t)(pos + o + got));
-              if (r < 0 && errno == EINTR) continue;
-              if (r <= 0) { read_ok.store(false); return false; }  // (an error, or the file shrank)
-              got += (size_t)r;
-            }
-            return true;
-          });
-        } catch (const GpuError &) {
-          if (!read_ok.load()) { fail(1, "Failed to read file: " + path); break; }
-          throw;
-        }
-        s_up += secs(t0);
-        {
-          std::lock_guard<std::mutex> g(mu);
-          Piece p;
-          p.pos = pos;
-          p.bytes = nb;
-          pieces.push_back(p);
-          up_n = i + 1;
-        }
-        cv.notify_all();
-        pos = end;
-      }
-    } catch (const GpuError &e) {
-      fail(2, "GPU error: " + e.msg);
-    } catch (const std::exception &e) {
-      fail(2, std::string("encode_file (upload thread): ") + e.what());
+        return true;
+      });
+    } catch (const GpuError &) {
+      if (!read_ok.load()) return Status(1, "Failed to read file: " + path);
+      throw;
     }
-    std::lock_guard<std::mutex> g(mu);
-    up_end = true;
-    cv.notify_all();
-  });
-  std::thread down([&] {
-    const CfgBind b(C);
-    try {
-      HIP_CHECK(hipSetDevice(device));
-      for (size_t i = 0;; i++) {
-        Piece p;
-        {
-          std::unique_lock<std::mutex> g(mu);
-          cv.wait(g, [&] { return failed || enc_n > i || enc_end; });
-          if (failed || enc_n <= i) break;
-          p = pieces[i];
-        }
-        const auto t0 = std::chrono::steady_clock::now();
-        EncodeLane &d = dev->lane[i & 1];
-        const unsigned long long ids_base = ids_total, lines_base = lines_total;
-        std::atomic<bool> write_ok{true};
-        if (!out_prefix) {  // room for this piece, asked for at what the pieces so far say about the whole file
-          const double whole = (double)size / (double)(p.pos + p.bytes) * 1.03;
-          ids.used = (size_t)ids_base;
-          off.used = (size_t)lines_base + (lines_base ? 1 : 0);
-          if (!ids.need((size_t)(ids_base + p.n_ids) + 1, (size_t)((double)(ids_base + p.n_ids) * whole) + 1024) ||
-              !off.need((size_t)(lines_base + p.n_lines) + 1, (size_t)((double)(lines_base + p.n_lines) * whole) + 1024)) {
-            fail(2, "out of memory");
-            break;
-          }
-        }
-        try {
-          if (p.n_ids)
-            staged_transfer(device, (uint8_t *)d.d_ids, p.n_ids * 4, false, [&](void *chunk, unsigned long long o, size_t len) {
-              if (!out_prefix) { memcpy((uint8_t *)(ids.p + ids_base) + o, chunk, len); return true; }
-              if (!pwrite_all(out_ids.fd, chunk, len, ids_base * 4 + o)) { write_ok.store(false); return false; }
-              return true;
-            }, nullptr, ENC_CHUNK);
-          // (the piece's offsets start at 0: moved behind the ids so far; its last entry is the next piece's first, written twice, the same)
-          if (p.n_lines)
-            staged_transfer(device, (uint8_t *)d.d_out_off, (p.n_lines + 1) * 8, false, [&](void *chunk, unsigned long long o, size_t len) {
-              unsigned long long *v = (unsigned long long *)chunk;
-              if (!out_prefix) {
-                unsigned long long *dst = off.p + lines_base + o / 8;
-                for (size_t j = 0; j < len / 8; j++) dst[j] = v[j] + ids_base;
-                return true;
-              }
-              for (size_t j = 0; j < len / 8; j++) v[j] += ids_base;
-              if (!pwrite_all(out_off.fd, chunk, len, lines_base * 8 + o)) { write_ok.store(false); return false; }
-              return true;
-            }, nullptr, ENC_CHUNK);
-        } catch (const GpuError &) {
-          if (!write_ok.load()) { fail(1, "Failed to write file: " + (ids_path.empty() ? std::string("?") : std::string(out_prefix) + ".ids / .off")); break; }
-          throw;
-        }
-        ids_total += p.n_ids;
-        lines_total += p.n_lines;
-        s_down += secs(t0);
-        {
-          std::lock_guard<std::mutex> g(mu);
-          down_n = i + 1;
-        }
-        cv.notify_all();
-      }
-    } catch (const GpuError &e) {
-      fail(2, "GPU error: " + e.msg);
-    } catch (const std::exception &e) {
-      fail(2, std::string("encode_file (download thread): ") + e.what());
-    }
-  });
-  size_t n_pieces = 0;
-  for (size_t i = 0;; i++) {
-    Piece p;
-    {
-      std::unique_lock<std::mutex> g(mu);
-      cv.wait(g, [&] { return failed || up_n > i || up_end; });
-      if (failed || up_n <= i) break;
-      p = pieces[i];
-    }
+    s_up += secs(t0);
+    piece[i & 1] = Piece{pos, nb, 0, 0};
+    next_pos = end;
+    return Status();
+  };
+  auto work = [&](size_t i) {
+    Piece &p = piece[i & 1];
     EncodeLane &d = dev->lane[i & 1];
     double ms_split = 0;
     const auto t0 = std::chrono::steady_clock::now();
-    Status st = encode_text_on_lane(*this, *dev, d, device, d.d_bytes, p.bytes, bos, eos, reverse, dropout_prob, &p.n_lines, &p.n_ids, &ms_split, nullptr);
-    if (!st.ok()) {
-      fail(st.code, st.message);
-      break;
-    }
+    const Status st = encode_text_on_lane(*this, *dev, d, device, d.in.bytes, p.bytes, bos, eos, reverse, dropout_prob, &p.n_lines, &p.n_ids, &ms_split, nullptr);
     s_split += ms_split * 1e-3;
     s_enc += secs(t0) - ms_split * 1e-3;
-    {
-      std::lock_guard<std::mutex> g(mu);
-      pieces[i].n_lines = p.n_lines;
-      pieces[i].n_ids = p.n_ids;
-      enc_n = i + 1;
+    return st;
+  };
+  auto download = [&](size_t i) {
+    const Piece p = piece[i & 1];
+    const auto t0 = std::chrono::steady_clock::now();
+    EncodeLane &d = dev->lane[i & 1];
+    const unsigned long long ids_base = ids_total, lines_base = lines_total;
+    std::atomic<bool> write_ok{true};
+    if (!out_prefix) {  // room for this piece, asked for at what the pieces so far say about the whole file
+      const double whole = (double)size / (double)(p.pos + p.bytes) * 1.03;
+      ids.used = (size_t)ids_base;
+      off.used = (size_t)lines_base + (lines_base ? 1 : 0);
+      if (!ids.need((size_t)(ids_base + p.n_ids) + 1, (size_t)((double)(ids_base + p.n_ids) * whole) + 1024) ||
+          !off.need((size_t)(lines_base + p.n_lines) + 1, (size_t)((double)(lines_base + p.n_lines) * whole) + 1024))
+        return Status(2, "out of memory");
     }
-    cv.notify_all();
-    n_pieces = i + 1;
-  }
-  {
-    std::lock_guard<std::mutex> g(mu);
-    enc_end = true;
-  }
-  cv.notify_all();
-  up.join();
-  down.join();
-  if (failed) return Status(fail_code, error);
+    try {
+      if (p.n_ids)
+        staged_transfer(device, (uint8_t *)d.res.ids.p, p.n_ids * 4, false, [&](void *chunk, unsigned long long o, size_t len) {
+          if (!out_prefix) { memcpy((uint8_t *)(ids.p + ids_base) + o, chunk, len); return true; }
+          if (!pwrite_all(out_ids.fd, chunk, len, ids_base * 4 + o)) { write_ok.store(false); return false; }
+          return true;
+        }, nullptr, ENC_CHUNK);
+      // (the piece's offsets start at 0: moved behind the ids so far; its last entry is the next piece's first, written twice, the same)
+      if (p.n_lines)
+        staged_transfer(device, (uint8_t *)d.res.off.p, (p.n_lines + 1) * 8, false, [&](void *chunk, unsigned long long o, size_t len) {
+          unsigned long long *v = (unsigned long long *)chunk;
+          if (!out_prefix) {
+            unsigned long long *dst = off.p + lines_base + o / 8;
+            for (size_t j = 0; j < len / 8; j++) dst[j] = v[j] + ids_base;
+            return true;
+          }
+          for (size_t j = 0; j < len / 8; j++) v[j] += ids_base;
+          if (!pwrite_all(out_off.fd, chunk, len, lines_base * 8 + o)) { write_ok.store(false); return false; }
+          return true;
+        }, nullptr, ENC_CHUNK);
+    } catch (const GpuError &) {
+      if (!write_ok.load()) return Status(1, "Failed to write file: " + (ids_path.empty() ? std::string("?") : std::string(out_prefix) + ".ids / .off"));
+      throw;
+    }
+    ids_total += p.n_ids;
+    lines_total += p.n_lines;
+    s_down += secs(t0);
+    return Status();
+  };
+  size_t n_pieces = 0;
+  const Status piped = run_two_lanes("encode_file", C, device, PIPE_UNTIL_EXHAUSTED, upload, work, download, &n_pieces);
+  if (!piped.ok()) return piped;
   if (out_prefix) {
     if (size == 0 || lines_total == 0) {  // (no piece wrote the offsets' first entry)
       const unsigned long long zero = 0;

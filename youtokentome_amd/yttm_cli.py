@@ -61,7 +61,7 @@ def encode(model, output_type, n_threads, bos, eos, reverse, stream, dropout_pro
 def encode_file(model, input_path, output, bos, eos, reverse, dropout_prob):
     """Encode a text file to binary ids and line offsets."""
     core = _Core(model)
-    core.encode_file(input_path, out=output, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob)  # the C++ pipeline: yttm_encode_file (host_lines.h)
+    core.encode_file(input_path, out=output, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob)  # the C++ pipeline: yttm_encode_file (host_lines.cpp)
 
 
 def _parse_ignore_ids(ctx, param, value):
