@@ -59,6 +59,22 @@ int yttm_gpu_download_pairs(yttm_ctx *ctx, uint64_t *pairs /* x<<32|y */, uint64
  * (rule_intersection, bpe.cpp:145-147; at most one x==y rule, last): applies them to every word and updates the
  * pair table exactly. */
 int yttm_gpu_merge_apply(yttm_ctx *ctx, const uint32_t *xyz, uint32_t k);
+/* The same round the way the trainer's merge loop runs it (host_trainer.cpp): rule_counts[k] are the pairs' exact global counts (what the
+ * candidate filter returned for them), and the threshold of the candidate scan that will follow rides along -- next_want != 0: that scan
+ * may raise the threshold to keep about so many candidates.  When the round's last launch can carry the scan (single GPU: hot and top
+ * list active, no class-C tiles) the following yttm_gpu_candidates(next_tau_cnt, next_tau_mx) takes its answer from the mailbox instead
+ * of scanning.
+ * ORDER: the whole-table read-back of yttm_gpu_download_pairs lies over that mailbox, and until the scan's answer has been read the
+ * host does not know whether the scan zeroed the batch's pairs (a scan that found its list overflowed did not).  So after this call
+ * the next call that looks at the pair table must be yttm_gpu_candidates; yttm_gpu_download_pairs and yttm_gpu_pair_query in between
+ * fail (they do not wait, and they do not disturb the pending scan).  yttm_gpu_download_word_table may come at any time. */
+int yttm_gpu_merge_apply_scan(yttm_ctx *ctx, const uint32_t *xyz, uint32_t k, const uint64_t *rule_counts, uint64_t next_tau_cnt,
+                              uint32_t next_tau_mx, uint32_t next_want);
+/* Which paths the context's merge rounds and candidate scans took so far -- the counters of the training report, in this order:
+ * [0] merge_rounds, [1] word_rounds, [2] word_all_rounds, [3] word_fused_rounds, [4] index_builds, [5] classb_word_rounds,
+ * [6] fused_rounds, [7] fused_overflows, [8] hot_rebuilds, [9] top_refills, [10] word_switch_round.  The first min(n, 11) go to out. */
+#define YTTM_ROUND_STATS 11
+int yttm_gpu_round_stats(yttm_ctx *ctx, uint64_t *out, uint32_t n);
 /* Measurement mode of K4 (bench.py's untimed pass behind roofline.algorithmic_bytes_8d): on != 0 makes the following
  * yttm_gpu_merge_apply calls also count the WORDS that hold a merge site and their tokens (W_touched, T_touched).
  * out (optional) receives the totals so far: [0] merge sites, [1] tiles with a site, [2] their tokens, [3] words with a site,

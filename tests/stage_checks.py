@@ -130,6 +130,35 @@ def make_batch(xs, ys, cs, first_id, max_rules, rng=None):
     return batch
 
 
+def assert_whole_state(c, tok, off, cnt, batch, when, same_words=None):
+    """The device's whole state against the oracle's word table (tok, off, cnt) after `batch` was applied to both: every word with its
+    weight, every pair with its count (a from-scratch recount by the oracle), and the batch's own pairs at zero.  same_words(c, tok, off, cnt)
+    -> (bool, what differs) may stand in for the comparison of the two sorted word lists (tests/round_checks.py: the same comparison,
+    word by word through a map it keeps between rounds); returns the oracle's recount."""
+    if same_words is None:
+        want = sorted((tuple(tok[int(off[i]):int(off[i + 1])].tolist()), int(cnt[i])) for i in range(len(cnt)))
+        assert c.words_as_multiset() == want, f"word table differs after {when}"
+    else:
+        same, what = same_words(c, tok, off, cnt)
+        assert same, f"word table differs after {when}: {what}"
+    keys, cnts = c.pairs()
+    xs2, ys2, cs2 = O.pair_counts(tok, off, cnt)
+    wk = (xs2.astype(np.uint64) << np.uint64(32)) | ys2.astype(np.uint64)
+    assert np.array_equal(keys, wk), f"pair set differs after {when}" + _first_pair_difference(keys, cnts, wk, cs2)
+    assert np.array_equal(cnts, cs2), f"pair counts differ after {when}" + _first_pair_difference(keys, cnts, wk, cs2)
+    # the merged pairs are gone
+    q = c.pair_query(np.array([(x << 32) | y for x, y, _ in batch], np.uint64))
+    assert not q.any()
+    return xs2, ys2, cs2
+
+
+def _first_pair_difference(keys, cnts, want_keys, want_cnts):
+    """(for the assertion's message) the first pairs the device and the oracle disagree on: (x, y): device count / oracle count"""
+    got, want = dict(zip(keys.tolist(), cnts.tolist())), dict(zip(want_keys.tolist(), want_cnts.tolist()))
+    bad = [k for k in sorted(set(got) | set(want)) if got.get(k, 0) != want.get(k, 0)][:5]
+    return "".join(f"; ({k >> 32}, {k & 0xffffffff}): {got.get(k, 0)} / {want.get(k, 0)}" for k in bad)
+
+
 def check_merge_rounds(text, rounds=6, seed=0, coverage=1.0, id_shift=0):
     """K4: apply batches; after every round the device word table and the whole pair table must equal a from-scratch
     recount by the oracle on the oracle-merged table.  id_shift > 0 moves every second char id and all new ids up by that
@@ -153,16 +182,7 @@ def check_merge_rounds(text, rounds=6, seed=0, coverage=1.0, id_shift=0):
         next_id += len(batch)
         c.merge_apply(np.array(batch, np.uint32))
         tok, off = O.apply_rules(tok, off, np.array(batch, np.uint32))
-        want = sorted((tuple(tok[int(off[i]):int(off[i + 1])].tolist()), int(cnt[i])) for i in range(len(cnt)))
-        assert c.words_as_multiset() == want, f"word table differs after round {r}"
-        keys, cnts = c.pairs()
-        xs2, ys2, cs2 = O.pair_counts(tok, off, cnt)
-        wk = ((xs2.astype(np.uint64) << np.uint64(32)) | ys2.astype(np.uint64)).tolist()
-        assert keys.tolist() == wk, f"pair set differs after round {r}"
-        assert cnts.tolist() == cs2.tolist(), f"pair counts differ after round {r}"
-        # the merged pairs are gone
-        q = c.pair_query(np.array([(x << 32) | y for x, y, _ in batch], np.uint64))
-        assert not q.any()
+        assert_whole_state(c, tok, off, cnt, batch, f"round {r}")
     c.close()
 
 

@@ -80,6 +80,22 @@ class Ctx:
         r = np.ascontiguousarray(rules_xyz, np.uint32).reshape(-1)
         self._chk(self.L.yttm_gpu_merge_apply(self.h, r.ctypes.data_as(_lib.u32p), len(r) // 3))
 
+    def merge_apply_scan(self, rules_xyz, rule_counts, next_tau_cnt, next_tau_mx=0xFFFFFFFF, next_want=0):
+        """the round as the trainer runs it: the next candidate scan rides in its last launch when it can (candidates() must come next)"""
+        r = np.ascontiguousarray(rules_xyz, np.uint32).reshape(-1)
+        rc = np.ascontiguousarray(rule_counts, np.uint64)
+        assert len(rc) * 3 == len(r)
+        self._chk(self.L.yttm_gpu_merge_apply_scan(self.h, r.ctypes.data_as(_lib.u32p), len(rc), rc.ctypes.data_as(_lib.u64p), int(next_tau_cnt),
+                                                   next_tau_mx, next_want))
+
+    ROUND_STATS = ("merge_rounds", "word_rounds", "word_all_rounds", "word_fused_rounds", "index_builds", "classb_word_rounds", "fused_rounds",
+                   "fused_overflows", "hot_rebuilds", "top_refills", "word_switch_round")
+
+    def round_stats(self):
+        out = np.zeros(len(self.ROUND_STATS), np.uint64)
+        self._chk(self.L.yttm_gpu_round_stats(self.h, out.ctypes.data_as(_lib.u64p), len(out)))
+        return dict(zip(self.ROUND_STATS, (int(v) for v in out)))
+
     def k4_measure(self, on=True, read=False):
         out = np.zeros(6, np.uint64)
         self._chk(self.L.yttm_gpu_k4_measure(self.h, int(on), out.ctypes.data_as(_lib.u64p) if read else None))

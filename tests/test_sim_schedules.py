@@ -12,6 +12,7 @@ import pytest
 
 import gen
 import oracle_lib as O
+import round_checks as R
 import stage_checks as S
 
 pytestmark = pytest.mark.usefixtures("sim_lib")
@@ -76,6 +77,15 @@ def test_word_mode(sched, tmp_path, monkeypatch):
         for k in cfg:
             monkeypatch.delenv(k)
     S.check_train_vs_oracle(gen.disjoint_words_corpus(150), 4 + 600 + 375, tmp_path, tag="wmsplit")
+
+
+@pytest.mark.parametrize("sched", SCHEDULES)
+def test_word_mode_round_state(sched, monkeypatch):
+    """word-mode rounds with the candidate scan in their tail, the whole state against the oracle after every round (tests/round_checks.py):
+    ordinary class-A rounds, and class-B tiles launched before k_words"""
+    monkeypatch.setenv("HIPSIM_SCHED", sched)
+    R.run_scenario(monkeypatch, "a", "default", rounds=20)
+    R.run_scenario(monkeypatch, "c", "default", rounds=20)
 
 
 @pytest.mark.parametrize("sched", SCHEDULES)

@@ -31,7 +31,7 @@ EXPORTS = [
     "yttm_gpu_upload_corpus",
     "yttm_gpu_attach_corpus", "yttm_gpu_char_hist", "yttm_gpu_build_word_table", "yttm_gpu_download_word_table",
     "yttm_gpu_pair_count", "yttm_gpu_download_pairs", "yttm_gpu_merge_apply", "yttm_gpu_pair_query",
-    "yttm_gpu_candidates", "yttm_gpu_k4_measure",
+    "yttm_gpu_candidates", "yttm_gpu_k4_measure", "yttm_gpu_merge_apply_scan", "yttm_gpu_round_stats",
 ]
 
 _lib = None
@@ -114,6 +114,8 @@ def load():
     L.yttm_gpu_pair_count.argtypes = [cvp, u64p]
     L.yttm_gpu_download_pairs.argtypes = [cvp, u64p, u64p, u64p]
     L.yttm_gpu_merge_apply.argtypes = [cvp, u32p, C.c_uint32]
+    L.yttm_gpu_merge_apply_scan.argtypes = [cvp, u32p, C.c_uint32, u64p, C.c_uint64, C.c_uint32, C.c_uint32]
+    L.yttm_gpu_round_stats.argtypes = [cvp, u64p, C.c_uint32]
     L.yttm_gpu_pair_query.argtypes = [cvp, u64p, C.c_uint32, u64p]
     L.yttm_gpu_k4_measure.argtypes = [cvp, ci, u64p]
     L.yttm_gpu_candidates.argtypes = [cvp, C.c_uint64, C.c_uint32, u64p, u64p, u32p]

@@ -402,6 +402,21 @@ int yttm_gpu_download_pairs(yttm_ctx *c, uint64_t *pairs, uint64_t *counts, uint
   })
 }
 int yttm_gpu_merge_apply(yttm_ctx *c, const uint32_t *xyz, uint32_t k) { GUARD_CTX(c->g->merge_apply(xyz, k, nullptr)) }
+int yttm_gpu_merge_apply_scan(yttm_ctx *c, const uint32_t *xyz, uint32_t k, const uint64_t *rule_counts, uint64_t next_tau_cnt, uint32_t next_tau_mx,
+                              uint32_t next_want) {
+  GUARD_CTX({
+    const unsigned long long tau = next_tau_cnt;
+    c->g->merge_apply(xyz, k, (const unsigned long long *)rule_counts, &tau, next_tau_mx, next_want);
+  })
+}
+int yttm_gpu_round_stats(yttm_ctx *c, uint64_t *out, uint32_t n) {
+  GUARD_CTX({
+    const GpuCtx &g = *c->g;
+    const unsigned long long v[YTTM_ROUND_STATS] = {g.merge_rounds, g.word_rounds, g.word_all_rounds, g.word_fused_rounds, g.index_builds, g.classb_word_rounds,
+                                                    g.fused_rounds, g.fused_overflows, g.hot_rebuilds, g.top_refills, g.word_switch_round};
+    for (uint32_t i = 0; i < std::min<uint32_t>(n, YTTM_ROUND_STATS); i++) out[i] = v[i];
+  })
+}
 int yttm_gpu_pair_query(yttm_ctx *c, const uint64_t *pairs, uint32_t n, uint64_t *counts) {
   GUARD_CTX(c->g->pair_query((const unsigned long long *)pairs, n, (unsigned long long *)counts))
 }

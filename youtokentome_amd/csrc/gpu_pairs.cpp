@@ -128,6 +128,8 @@ void GpuCtx::pair_count() {
 }
 
 void GpuCtx::download_pairs(std::vector<unsigned long long> &keys, std::vector<unsigned long long> &cnts) {
+  // (scan_full's read-back lies over the mailbox, and whether the fused scan zeroed its batch's pairs is known only from its answer)
+  if (fused_pending_) throw GpuError{"download_pairs: a candidate scan rides in the last merge round -- call candidates first"};
   std::vector<CandRec> out;
   uint32_t n = scan_full(0, 0xffffffffu, out, nullptr);
   if (n > out.size()) throw GpuError{"download_pairs: more than 2^20 live pairs"};
@@ -480,6 +482,7 @@ uint32_t GpuCtx::candidates(unsigned long long tau_cnt, uint32_t tau_mx, std::ve
 
 void GpuCtx::pair_query(const unsigned long long *keys, uint32_t n, unsigned long long *outv) {
   if (!n) return;
+  if (fused_pending_) throw GpuError{"pair_query: a candidate scan rides in the last merge round -- call candidates first"};
   flush_pending_zero();
   unsigned long long *d_k = dmalloc<unsigned long long>(n), *d_o = dmalloc<unsigned long long>(n);
   HIP_CHECK(hipMemcpyAsync(d_k, keys, (size_t)n * 8, hipMemcpyHostToDevice, strm()));
