@@ -111,6 +111,36 @@ int yttm_encode_file(yttm_encoder *enc, const char *path, const char *out_prefix
                      uint64_t chunk_bytes, int32_t **ids, uint64_t **offsets, uint64_t *n_lines, uint64_t *n_ids, char *report_json, int report_len,
                      char *err, int errlen);
 
+/* SUBWORD output on the device: the text `yttm encode --output_type subword` prints for the batch -- per sentence every piece followed by one
+ * space, then '\n' (utils.h:92-103); an empty sentence is "\n".  The ids are exactly those of yttm_encode_device with the same arguments, in
+ * the order it stores them; the piece of an id is id_to_subword(id, replace_space = false), and the k-th unk_id of a sentence in forward order is
+ * the text of its k-th run of unknown chars (its valid code points; invalid bytes are dropped and do not end a run).
+ * yttm_subword_device encodes exactly as yttm_encode_device, then formats: afterwards the ids are pending as after yttm_encode_device, and the
+ * text is pending in the encoder's text slot, THE SAME ONE a decode result uses -- a pending yttm_decode_device[_padded] result is replaced, and
+ * the text is taken with yttm_decode_fetch / yttm_decode_copy_device: char bytes[*n_text_bytes], uint64 out_offsets[n_sent + 1],
+ * out_offsets[0] = 0, line i = bytes[out_offsets[i] .. out_offsets[i+1]) including its '\n'.  kernel_ms (optional) = HIP-event time of encode +
+ * measure + scan + write.  bos / eos on a model trained without them: the message and code (1) of yttm_encode_as_subwords, nothing is written
+ * and nothing that was pending is replaced.
+ * replaces: encode_as_subwords, bpe.h:41-46, bpe.cpp:1757 (the pieces: bpe.cpp:1597-1613), and the text formatting of encode_cli,
+ * bpe.cpp:1942-2014 */
+int yttm_subword_device(yttm_encoder *enc, const void *d_bytes, const void *d_offsets, uint64_t n_sent, uint64_t total_bytes,
+                        uint64_t max_sentence_bytes, int bos, int eos, int reverse, double dropout_prob, uint64_t *n_ids, uint64_t *n_text_bytes,
+                        double *kernel_ms, char *err, int errlen);
+/* yttm_encode_text_device, then the format: lines, ids and the lines' offsets are pending as after yttm_encode_text_device (n_sent = *n_lines), the
+ * text as after yttm_subword_device.  kernel_ms (optional) = split + encode + format.  bpe.h:41-46, bpe.cpp:1757, :1597-1613, :1942-2014 */
+int yttm_subword_text_device(yttm_encoder *enc, const void *d_text, uint64_t n_bytes, int bos, int eos, int reverse, double dropout_prob,
+                             uint64_t *n_lines, uint64_t *n_ids, uint64_t *n_text_bytes, double *kernel_ms, char *err, int errlen);
+/* A text file of any size -> the text file `yttm encode --output_type subword < path` prints, byte for byte, written to out_path.  The pipeline
+ * of yttm_encode_file: upload of one piece beside split + encode + format of the one before and the download and write of the text of the one
+ * before that.  With dropout_prob == 0 the file does not depend on chunk_bytes.  report_json (optional): the keys of yttm_encode_file plus
+ * "seconds_format" and "text_bytes".  A file that cannot be read or written is code 1 with a plain message; so are an empty out_path and an
+ * out_path that names the input file itself (same device and inode: refused before anything is truncated).  out_path is emptied when the call
+ * begins; a call that fails later leaves a partial file there, as yttm_encode_file leaves partial PREFIX.ids / PREFIX.off.  Uses both lanes: a pending device
+ * result does not survive the call.  bpe.h:41-46, bpe.cpp:1757, :1597-1613, :1942-2014 */
+int yttm_encode_file_subword(yttm_encoder *enc, const char *path, const char *out_path, int bos, int eos, int reverse, double dropout_prob,
+                             uint64_t chunk_bytes, uint64_t *n_lines, uint64_t *n_ids, uint64_t *n_text_bytes, char *report_json, int report_len,
+                             char *err, int errlen);
+
 /* Word-level encode cache (SURVEY.md 8f "N4"; the reference has no counterpart: bpe.cpp:1497-1632 encodes every word occurrence).
  * mode 0: every batch goes straight through the encode kernel; 1: distinct words are encoded once whenever that is possible
  * (dropout_prob == 0); 2 (default): the same for batches of at least min_bytes.  The ids are identical either way.

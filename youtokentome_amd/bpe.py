@@ -230,6 +230,39 @@ class _Core:
             res += (json.loads(rep.value.decode()),)
         return res
 
+    # ---- SUBWORD output on the device (include/yttm_mi355x.h): the text stays in the encoder until fetch_decode / copy_decode_device takes it
+    def subword_device_raw(self, d_bytes, d_offsets, n_sent, total_bytes, max_sentence_bytes, bos=False, eos=False, reverse=False, dropout_prob=0.0):
+        """-> (n_ids, n_text_bytes, kernel_ms); the ids are pending as after encode_device_raw, the text replaces a pending decode result"""
+        ni, nt, ms, err = C.c_uint64(), C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_subword_device(self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n_sent, total_bytes, max_sentence_bytes, int(bos),
+                                                    int(eos), int(reverse), float(dropout_prob), C.byref(ni), C.byref(nt), C.byref(ms), err, _lib.ERRLEN), err)
+        return ni.value, nt.value, ms.value
+
+    def subword_text_device_raw(self, d_text, n_bytes, bos=False, eos=False, reverse=False, dropout_prob=0.0):
+        """-> (n_lines, n_ids, n_text_bytes, kernel_ms)"""
+        nl, ni, nt, ms, err = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_subword_text_device(self._h, C.c_void_p(d_text), n_bytes, int(bos), int(eos), int(reverse), float(dropout_prob),
+                                                         C.byref(nl), C.byref(ni), C.byref(nt), C.byref(ms), err, _lib.ERRLEN), err)
+        return nl.value, ni.value, nt.value, ms.value
+
+    def encode_file_subword(self, path, out, bos=False, eos=False, reverse=False, dropout_prob=0.0, chunk_bytes=None, report=False):
+        """a text file -> the text file `yttm encode --output_type subword` prints for it, written to `out`: (n_lines, n_ids, n_text_bytes), or with
+        report=True the call's report (a dict)"""
+        if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
+            raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+        if out is None:
+            raise ValueError("encode_file with output_type SUBWORD needs out, the path of the text file to write")
+        nl, ni, nt, err = C.c_uint64(), C.c_uint64(), C.c_uint64(), _err()
+        rep = C.create_string_buffer(1024)
+        rc = _lib.load().yttm_encode_file_subword(self._h, os.fsencode(path), os.fsencode(out), int(bos), int(eos), int(reverse), float(dropout_prob),
+                                                  int(chunk_bytes or 0), C.byref(nl), C.byref(ni), C.byref(nt), rep, len(rep), err, _lib.ERRLEN)
+        if rc != 0:
+            raise ValueError(err.value.decode(errors="replace"))
+        if report:
+            import json
+            return json.loads(rep.value.decode())
+        return nl.value, ni.value, nt.value
+
     def encode(self, sentences, output_type, bos, eos, reverse, dropout_prob):
         if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
             raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
@@ -409,10 +442,31 @@ class BPE:
         return tensor.text_lines_tensor(self, text)
 
     def encode_file(self, path, out: Optional[str] = None, bos: bool = False, eos: bool = False, reverse: bool = False, dropout_prob: float = 0,
-                    chunk_bytes: Optional[int] = None):
+                    chunk_bytes: Optional[int] = None, output_type: OutputType = OutputType.ID, report: bool = False):
         """A text file, one sentence per line -> (ids np.int32, offsets np.uint64 [n_lines + 1]); with out=PREFIX the raw little-endian files
-        PREFIX.ids (int32) and PREFIX.off (uint64) are written instead and (n_lines, n_ids) is returned.  Needs no torch."""
-        return self.bpe_cython.encode_file(path, out=out, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, chunk_bytes=chunk_bytes)
+        PREFIX.ids (int32) and PREFIX.off (uint64) are written instead and (n_lines, n_ids) is returned.  Needs no torch.
+        output_type=OutputType.SUBWORD: `out` is required and is the path of a text file, written as `yttm encode --output_type subword` prints it
+        (every piece followed by a space, a newline per sentence); returns (n_lines, n_ids, n_text_bytes).  report=True: the call's report (a dict)
+        is appended to the ID result, and is the SUBWORD result."""
+        if not isinstance(output_type, OutputType):
+            raise TypeError("parameter output_type must be youtokentome.OutputType, not %s}" % str(type(output_type)))
+        if output_type == OutputType.SUBWORD:
+            return self.bpe_cython.encode_file_subword(path, out, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, chunk_bytes=chunk_bytes,
+                                                       report=report)
+        return self.bpe_cython.encode_file(path, out=out, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, chunk_bytes=chunk_bytes,
+                                           report=report)
+
+    def encode_subword_tensor(self, sentences, bos: bool = False, eos: bool = False, reverse: bool = False, dropout_prob: float = 0, device=None,
+                              as_str: bool = False):
+        """SUBWORD output made on the device: `sentences` as encode_tensor takes them -> (uint8 text tensor, int64 line_off [n + 1]) on the device,
+        line i = text[line_off[i]:line_off[i + 1]] = every piece followed by a space, then a newline; as_str=True: the lines as list[str]"""
+        from . import tensor
+        return tensor.encode_subword_tensor(self, sentences, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, device=device, as_str=as_str)
+
+    def encode_text_subword_tensor(self, text, bos: bool = False, eos: bool = False, reverse: bool = False, dropout_prob: float = 0, as_str: bool = False):
+        """the same for `text` as encode_text_tensor takes it, one sentence per line"""
+        from . import tensor
+        return tensor.encode_text_subword_tensor(self, text, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, as_str=as_str)
 
     def decode_tensor(self, ids, lengths=None, offsets=None, ignore_ids: Optional[Collection] = None, as_str: bool = True):
         from . import tensor

@@ -242,6 +242,35 @@ int yttm_encode_file(yttm_encoder *h, const char *path, const char *out_prefix, 
   return finish(s, err, errlen);
 }
 
+int yttm_subword_device(yttm_encoder *h, const void *d_bytes, const void *d_offsets, uint64_t n_sent, uint64_t total_bytes, uint64_t max_sentence_bytes, int bos,
+                        int eos, int reverse, double dropout_prob, uint64_t *n_ids, uint64_t *n_text_bytes, double *kernel_ms, char *err, int errlen) {
+  unsigned long long ni = 0, nt = 0;
+  Status s = h->enc->subword_device(d_bytes, d_offsets, n_sent, total_bytes, max_sentence_bytes, bos, eos, reverse, dropout_prob, &ni, &nt, kernel_ms);
+  if (n_ids) *n_ids = ni;
+  if (n_text_bytes) *n_text_bytes = nt;
+  return finish(s, err, errlen);
+}
+int yttm_subword_text_device(yttm_encoder *h, const void *d_text, uint64_t n_bytes, int bos, int eos, int reverse, double dropout_prob, uint64_t *n_lines,
+                             uint64_t *n_ids, uint64_t *n_text_bytes, double *kernel_ms, char *err, int errlen) {
+  unsigned long long nl = 0, ni = 0, nt = 0;
+  Status s = h->enc->subword_text_device(d_text, n_bytes, bos, eos, reverse, dropout_prob, &nl, &ni, &nt, kernel_ms);
+  if (n_lines) *n_lines = nl;
+  if (n_ids) *n_ids = ni;
+  if (n_text_bytes) *n_text_bytes = nt;
+  return finish(s, err, errlen);
+}
+int yttm_encode_file_subword(yttm_encoder *h, const char *path, const char *out_path, int bos, int eos, int reverse, double dropout_prob, uint64_t chunk_bytes,
+                             uint64_t *n_lines, uint64_t *n_ids, uint64_t *n_text_bytes, char *report_json, int report_len, char *err, int errlen) {
+  unsigned long long nl = 0, ni = 0, nt = 0;
+  std::string report;
+  Status s = h->enc->encode_file_subword(path ? path : "", out_path ? out_path : "", bos, eos, reverse, dropout_prob, chunk_bytes, &nl, &ni, &nt, &report);
+  if (n_lines) *n_lines = nl;
+  if (n_ids) *n_ids = ni;
+  if (n_text_bytes) *n_text_bytes = nt;
+  if (s.ok() && report_json && report_len > 0) snprintf(report_json, (size_t)report_len, "%s", report.c_str());
+  return finish(s, err, errlen);
+}
+
 int yttm_encoder_set_cache(yttm_encoder *h, int mode, uint64_t min_bytes) {
   h->enc->set_cache(mode, min_bytes);
   return 0;

@@ -1,5 +1,5 @@
 // enc_lanes.h -- what the encoder's host units (host_encoder.cpp, host_decode.cpp, host_lines.cpp) share: the lanes and their device buffers,
-// the model's device state, and the small helpers every entry point is built from.  Internal: nothing outside these three units includes it.
+// the model's device state, and the small helpers every entry point is built from.  Internal: nothing outside these units includes it.
 #pragma once
 #include <atomic>
 #include <functional>
@@ -67,7 +67,7 @@ struct EncodeLane {
     DevBuf<unsigned int> misc;                 // [0] number of uncached words, [1] status
     unsigned long long distinct_words = 0;     // of the last cached batch (0: the batch went straight through K5)
   } wc;
-  struct {  // device decode (host_decode.cpp)
+  struct {  // device decode (host_decode.cpp); the SUBWORD formatter leaves its text here too (len, off, bytes)
     DevBuf<uint32_t> len, ign;  // ign: ignore bitmap, then the ignored ids outside [0, vocab)
     DevBuf<unsigned long long> off, misc;  // misc[0]: smallest flat index of an invalid id
     DevBuf<uint8_t> bytes;
@@ -118,6 +118,10 @@ struct EncoderDevice {
   DevBuf<uint8_t> piece_blob;
   DevBuf<uint32_t> piece_off;
   uint32_t dec_vocab = 0;
+  // piece table of the SUBWORD formatter (host_decode.cpp): id_to_subword(id, replace_space = false), made at the first format (under dec_mu)
+  bool sub_ready = false;
+  DevBuf<uint8_t> sub_blob;
+  DevBuf<uint32_t> sub_off;
   // a free lane, locked (falls back to waiting for the caller's turn-based choice)
   // (Lane 0 last: the device-resident pair encode_device / fetch_device_result keeps its result there, unlocked, between the two
   // calls -- a host-to-host encode from another thread in between takes another lane while one is free.)
@@ -181,6 +185,11 @@ Status encode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, i
                       double dropout_prob, unsigned long long *n_ids_out, double *kernel_ms);
 // counts -> offsets (exclusive scan, the total behind the last one and on the host); synchronises the lane's stream
 unsigned long long scan_counts(EncodeLane &d, const uint32_t *counts, unsigned long long n, unsigned long long *off);
+
+// SUBWORD text of the encode result pending on the lane (locked by the caller; sentence s = d_text[d_soff[s] .. d_soff[s+1]), the input that
+// result was made from), left in the lane's text slot (dec) as a decode leaves its text: measure -> scan -> write (k_subword.h)
+Status format_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_text, const void *d_soff, bool reverse,
+                      unsigned long long *n_text_bytes, double *kernel_ms);
 
 // Host arrays of a large batch cross the link through the trainer's pinned chunks (gpu_ctx.cpp staged_transfer; 1e7 sentences are 1.3 GB up
 // and 1.2 GB down: a plain copy from / to pageable memory moves them at a fraction of the link's rate, and the first touch of a freshly

@@ -136,6 +136,18 @@ class BaseEncoder {  // bpe.h:22-82
   // a file of any size in pieces through both lanes; out_prefix: PREFIX.ids / PREFIX.off instead of malloc'ed arrays
   Status encode_file(const std::string &path, const char *out_prefix, bool bos, bool eos, bool reverse, double dropout_prob, unsigned long long piece_bytes,
                      int32_t **ids, unsigned long long **out_off, unsigned long long *n_lines, unsigned long long *n_ids, std::string *report) const;
+  // SUBWORD output on the device (host_decode.cpp, host_lines.cpp, k_subword.h): encode_device / encode_text_device / encode_file, then the text
+  // `yttm encode --output_type subword` prints -- every piece followed by a space, '\n' per sentence -- left in lane 0's text slot (taken with
+  // fetch_decode_result / copy_decode_result: it replaces a pending decode result), the ids pending as after encode_device.
+  // replaces encode_as_subwords, bpe.h:41-46, bpe.cpp:1757, :1597-1613, and the formatting of encode_cli, bpe.cpp:1942-2014
+  Status subword_device(const void *d_bytes, const void *d_offsets, unsigned long long n_sent, unsigned long long total_bytes,
+                        unsigned long long max_sentence_bytes, bool bos, bool eos, bool reverse, double dropout_prob, unsigned long long *n_ids,
+                        unsigned long long *n_text_bytes, double *kernel_ms) const;
+  Status subword_text_device(const void *d_text, unsigned long long n_bytes, bool bos, bool eos, bool reverse, double dropout_prob,
+                             unsigned long long *n_lines, unsigned long long *n_ids, unsigned long long *n_text_bytes, double *kernel_ms) const;
+  Status encode_file_subword(const std::string &path, const std::string &out_path, bool bos, bool eos, bool reverse, double dropout_prob,
+                             unsigned long long piece_bytes, unsigned long long *n_lines, unsigned long long *n_ids, unsigned long long *n_text_bytes,
+                             std::string *report) const;
   // the YTTM_* hooks as they stood when THIS encoder was made: every entry point binds them to its thread (yttm_config.h CfgBind), so that a
   // later encoder or training never changes the paths of this one
   std::shared_ptr<const Config> config() const;

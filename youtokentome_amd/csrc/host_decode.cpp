@@ -1,5 +1,5 @@
-// host_decode.cpp -- host side of the device decode (k_decode.h) and the device-to-device exits of the encoder's and the decoder's results,
-// on the encoder's lanes (enc_lanes.h).
+// host_decode.cpp -- host side of the device decode (k_decode.h), of the SUBWORD formatter (k_subword.h), which leaves its text in the decode's
+// slot, and the device-to-device exits of the encoder's and the decoder's results, on the encoder's lanes (enc_lanes.h).
 //
 // Results live in lane 0 like those of encode_device, in buffers of their own: a decode leaves a pending encode result alone and the other way
 // round.  Every call locks the lane and returns after the lane's stream has synchronised; a pair (decode_device, fetch) is not atomic.
@@ -186,6 +186,95 @@ Status BaseEncoder::copy_encode_padded(void *d_matrix, void *d_lengths, unsigned
     HIP_CHECK(hipStreamSynchronize(d.st));
     return Status();
   });
+}
+
+// ---- SUBWORD output (k_subword.h) ----------------------------------------------------------------------------------------------------------
+// The text `yttm encode --output_type subword` prints for a batch, made on the device from the ids K5 left and the batch's own text.  It lands
+// in the lane's text slot, the one a device decode uses: it is taken with fetch_decode_result / copy_decode_result and replaces a pending
+// decode result; the ids stay pending as after encode_device.
+// The text of every id, once per encoder: from the host's id_to_subword(id, replace_space = false), so that the device path cannot drift from
+// the host path ("▁" stays, the special ids give their names, a hole of the id space is "").
+static void subword_table(const BaseEncoder &enc, EncoderDevice &D) {
+  std::lock_guard<std::mutex> lk(D.dec_mu);
+  if (D.sub_ready) return;
+  const int V = enc.vocab_size();
+  std::string blob, piece;
+  std::vector<uint32_t> off((size_t)V + 1, 0);
+  for (int id = 0; id < V; id++) {
+    off[(size_t)id] = (uint32_t)blob.size();
+    piece.clear();
+    if (enc.id_to_subword(id, &piece, false).ok()) blob += piece;
+    if (blob.size() >= (size_t)DEC_INVALID) throw GpuError{"subword: the vocabulary's text does not fit 2 GB"};
+  }
+  off[(size_t)V] = (uint32_t)blob.size();
+  DevBuf<uint8_t> d_blob;  // (handed to the encoder once both are filled)
+  DevBuf<uint32_t> d_off;
+  d_blob.alloc(blob.size() + 1);
+  d_off.alloc(off.size());
+  if (!blob.empty()) HIP_CHECK(hipMemcpy(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+  D.sub_blob = std::move(d_blob);
+  D.sub_off = std::move(d_off);
+  D.sub_ready = true;
+}
+
+Status format_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_text, const void *d_soff, bool reverse,
+                      unsigned long long *n_text_bytes, double *kernel_ms) {
+  return on_device(device, [&]() -> Status {
+    d.dec.valid = false;
+    if (n_text_bytes) *n_text_bytes = 0;
+    if (kernel_ms) *kernel_ms = 0;
+    const unsigned long long n_sent = d.res.n_sent;
+    if (n_sent == 0) {
+      d.dec.n_sent = d.dec.n_bytes = 0;
+      d.dec.valid = true;
+      return Status();
+    }
+    subword_table(enc, D);
+    const DecTable tb{D.sub_blob, D.sub_off, (uint32_t)enc.vocab_size()};
+    const SubInput in{(const uint8_t *)d_text, (const unsigned long long *)d_soff, d.res.ids, d.res.off, n_sent, (int32_t)enc.bpe_state.special_tokens.unk_id,
+                      reverse ? 1 : 0};
+    d.dec.len.grow((size_t)n_sent);
+    d.dec.off.grow((size_t)n_sent + 1);
+    EventPair ev(d.st, kernel_ms != nullptr);
+    ev.start();
+    launch_subword_measure(D.m, in, tb, d.res.n_ids, d.dec.len, d.st);
+    const unsigned long long total = scan_counts(d, d.dec.len, n_sent, d.dec.off);  // (syncs)
+    d.dec.bytes.grow((size_t)total + 16);
+    if (((uintptr_t)d.dec.bytes.p & 15u) != 0) throw GpuError{"subword: the output blob is not 16-byte aligned"};
+    launch_subword_write(D.m, in, tb, d.res.n_ids, d.dec.off, d.dec.bytes, d.st);
+    ev.stop();
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    if (kernel_ms) *kernel_ms = ev.elapsed_ms();
+    d.dec.n_sent = n_sent;
+    d.dec.n_bytes = total;
+    d.dec.valid = true;
+    if (n_text_bytes) *n_text_bytes = total;
+    return Status();
+  });
+}
+
+Status BaseEncoder::subword_device(const void *d_bytes, const void *d_offsets, unsigned long long n_sent, unsigned long long total_bytes,
+                                   unsigned long long max_sentence_bytes, bool bos, bool eos, bool reverse, double dropout_prob,
+                                   unsigned long long *n_ids, unsigned long long *n_text_bytes, double *kernel_ms) const {
+  if (n_ids) *n_ids = 0;
+  if (n_text_bytes) *n_text_bytes = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work: nothing that was pending is touched)
+  if (!tokens.ok()) return tokens;
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (n_sent && !d_offsets) return Status(2, "subword_device: no offsets");
+  const CfgBind bind(dev_->cfg);
+  EncodeLane &d = dev_->lane[0];
+  std::lock_guard<std::mutex> lk(d.mu);
+  const bool timed = kernel_ms != nullptr;
+  double ms_enc = 0, ms_fmt = 0;
+  Status s = encode_on_lane(*this, *dev_, d, device_, d_bytes, d_offsets, n_sent, total_bytes, max_sentence_bytes, bos, eos, reverse, dropout_prob, n_ids,
+                            timed ? &ms_enc : nullptr);
+  if (!s.ok()) return s;
+  s = format_on_lane(*this, *dev_, d, device_, d_bytes, d_offsets, reverse, n_text_bytes, timed ? &ms_fmt : nullptr);
+  if (kernel_ms) *kernel_ms = ms_enc + ms_fmt;
+  return s;
 }
 
 }  // namespace yttm

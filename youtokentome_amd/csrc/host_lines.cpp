@@ -1,5 +1,6 @@
 // host_lines.cpp -- host side of the line split (k_lines.h) and the encoder's entries for text that is not yet cut into sentences: a buffer in HBM
-// (lines_device, encode_text_device) and a file of any size (encode_file), on the encoder's lanes (enc_lanes.h).
+// (lines_device, encode_text_device, subword_text_device) and a file of any size (encode_file, encode_file_subword), on the encoder's lanes
+// (enc_lanes.h).
 //
 // The offsets of a split live in the lane like the results of encode_device and decode_device, in buffers of their own: a split leaves a pending
 // encode or decode result alone.  Every call locks the lane and returns after the lane's stream has synchronised.
@@ -117,6 +118,34 @@ Status BaseEncoder::encode_text_device(const void *d_text, unsigned long long n_
   return s;
 }
 
+// split, encode, then the SUBWORD text of those ids (host_decode.cpp): the lines' offsets are the formatter's sentence offsets
+static Status subword_text_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_text, unsigned long long n_bytes, bool bos,
+                                   bool eos, bool reverse, double dropout_prob, unsigned long long *n_lines, unsigned long long *n_ids,
+                                   unsigned long long *n_text_bytes, double *split_ms, double *encode_ms, double *format_ms) {
+  const Status s = encode_text_on_lane(enc, D, d, device, d_text, n_bytes, bos, eos, reverse, dropout_prob, n_lines, n_ids, split_ms, encode_ms);
+  if (!s.ok()) return s;
+  return format_on_lane(enc, D, d, device, d_text, d.ln.off, reverse, n_text_bytes, format_ms);
+}
+
+Status BaseEncoder::subword_text_device(const void *d_text, unsigned long long n_bytes, bool bos, bool eos, bool reverse, double dropout_prob,
+                                        unsigned long long *n_lines, unsigned long long *n_ids, unsigned long long *n_text_bytes, double *kernel_ms) const {
+  if (n_lines) *n_lines = 0;
+  if (n_ids) *n_ids = 0;
+  if (n_text_bytes) *n_text_bytes = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work: nothing that was pending is touched)
+  if (!tokens.ok()) return tokens;
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (n_bytes && !d_text) return Status(2, "subword_text_device: no text");
+  const CfgBind bind(dev_->cfg);
+  std::lock_guard<std::mutex> lk(dev_->lane[0].mu);
+  double ms_split = 0, ms_enc = 0, ms_fmt = 0;
+  Status s = subword_text_on_lane(*this, *dev_, dev_->lane[0], device_, d_text, n_bytes, bos, eos, reverse, dropout_prob, n_lines, n_ids, n_text_bytes,
+                                  kernel_ms ? &ms_split : nullptr, kernel_ms ? &ms_enc : nullptr, kernel_ms ? &ms_fmt : nullptr);
+  if (kernel_ms) *kernel_ms = ms_split + ms_enc + ms_fmt;
+  return s;
+}
+
 // ---- a file of any size ------------------------------------------------------------------------------------------------------------------
 // The file crosses in pieces of about piece_bytes, each cut behind the last newline inside it (a line longer than a piece extends the piece
 // to that line's end), through both lanes: while piece k is split and encoded, piece k + 1 is read (pread into the pinned chunks of
@@ -169,6 +198,32 @@ bool pwrite_all(int fd, const void *p, size_t n, unsigned long long at) {
     at += (unsigned long long)w;
   }
   return true;
+}
+// The piece that starts at pos (piece_end) from the file into the lane's input buffer: pread into the pinned chunks of staged_transfer.
+Status upload_piece(int fd, const std::string &path, int device, EncodeLane &d, unsigned long long pos, unsigned long long piece_bytes,
+                    unsigned long long size, unsigned long long *end_out) {
+  unsigned long long end = size;
+  if (!piece_end(fd, pos, piece_bytes, size, &end)) return Status(1, "Failed to read file: " + path);
+  const unsigned long long nb = end - pos;
+  d.in.bytes.grow((size_t)nb + 16);
+  std::atomic<bool> read_ok{true};
+  try {
+    staged_transfer(device, d.in.bytes, nb, true, [&](void *chunk, unsigned long long o, size_t len) {
+      size_t got = 0;
+      while (got < len) {
+        const ssize_t r = pread(fd, (char *)chunk + got, len - got, (off_t)(pos + o + got));
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) { read_ok.store(false); return false; }  // (an error, or the file shrank)
+        got += (size_t)r;
+      }
+      return true;
+    });
+  } catch (const GpuError &) {
+    if (!read_ok.load()) return Status(1, "Failed to read file: " + path);
+    throw;
+  }
+  *end_out = end;
+  return Status();
 }
 // A result array that is filled as the pieces arrive.  Its size is not known before the last piece; `hint` is the caller's estimate of the
 // whole from the pieces so far, so that a file of even lines is one allocation (result_alloc: huge pages for a large one, the first touch of
@@ -240,28 +295,10 @@ Status BaseEncoder::encode_file(const std::string &path, const char *out_prefix,
     if (pos >= size) { *exhausted = true; return Status(); }
     const auto t0 = std::chrono::steady_clock::now();
     unsigned long long end = size;
-    if (!piece_end(in.fd, pos, piece_bytes, size, &end)) return Status(1, "Failed to read file: " + path);
-    const unsigned long long nb = end - pos;
-    EncodeLane &d = dev->lane[i & 1];
-    d.in.bytes.grow((size_t)nb + 16);
-    std::atomic<bool> read_ok{true};
-    try {
-      staged_transfer(device, d.in.bytes, nb, true, [&](void *chunk, unsigned long long o, size_t len) {
-        size_t got = 0;
-        while (got < len) {
-          const ssize_t r = pread(in.fd, (char *)chunk + got, len - got, (off_t)(pos + o + got));
-          if (r < 0 && errno == EINTR) continue;
-          if (r <= 0) { read_ok.store(false); return false; }  // (an error, or the file shrank)
-          got += (size_t)r;
-        }
-        return true;
-      });
-    } catch (const GpuError &) {
-      if (!read_ok.load()) return Status(1, "Failed to read file: " + path);
-      throw;
-    }
+    const Status st = upload_piece(in.fd, path, device, dev->lane[i & 1], pos, piece_bytes, size, &end);
+    if (!st.ok()) return st;
     s_up += secs(t0);
-    piece[i & 1] = Piece{pos, nb, 0, 0};
+    piece[i & 1] = Piece{pos, end - pos, 0, 0};
     next_pos = end;
     return Status();
   };
@@ -349,6 +386,111 @@ Status BaseEncoder::encode_file(const std::string &path, const char *out_prefix,
              "{\"pieces\": %zu, \"piece_bytes\": %llu, \"bytes\": %llu, \"lines\": %llu, \"ids\": %llu, \"seconds_total\": %.6f, \"seconds_read_upload\": %.6f, "
              "\"seconds_split\": %.6f, \"seconds_encode\": %.6f, \"seconds_download_write\": %.6f}",
              n_pieces, piece_bytes, size, lines_total, ids_total, secs(t_begin), s_up, s_split, s_enc, s_down);
+    *report = tmp;
+  }
+  return Status();
+}
+
+// The same pipeline with the SUBWORD formatter behind the encode and the text as the only thing that comes down: piece k's text is written to
+// out_path behind the text of the pieces before it.
+Status BaseEncoder::encode_file_subword(const std::string &path, const std::string &out_path, bool bos, bool eos, bool reverse, double dropout_prob,
+                                        unsigned long long piece_bytes, unsigned long long *n_lines_out, unsigned long long *n_ids_out,
+                                        unsigned long long *n_text_out, std::string *report) const {
+  if (n_lines_out) *n_lines_out = 0;
+  if (n_ids_out) *n_ids_out = 0;
+  if (n_text_out) *n_text_out = 0;
+  const Status tokens = check_bos_eos(*this, bos, eos);
+  if (!tokens.ok()) return tokens;
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (out_path.empty()) return Status(1, "Failed to open file for writing: no output path");
+  if (!piece_bytes) piece_bytes = FILE_PIECE_DEFAULT;
+  const auto t_begin = std::chrono::steady_clock::now();
+  auto secs = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
+  Fd in, out;
+  in.fd = open(path.c_str(), O_RDONLY | O_CLOEXEC);
+  struct stat sb;
+  if (in.fd < 0 || fstat(in.fd, &sb) != 0) return Status(1, "Failed to open file: " + path + " (" + strerror(errno) + ")");
+  if (!S_ISREG(sb.st_mode)) return Status(1, "Failed to read file: " + path + " is not a regular file");
+  const unsigned long long size = (unsigned long long)sb.st_size;
+  // (opened without O_TRUNC, emptied only once it is known not to be the input itself: the text is longer than the input it would overwrite)
+  out.fd = open(out_path.c_str(), O_WRONLY | O_CREAT | O_CLOEXEC, 0644);
+  struct stat ob;
+  if (out.fd < 0 || fstat(out.fd, &ob) != 0) return Status(1, "Failed to open file for writing: " + out_path + " (" + strerror(errno) + ")");
+  if (ob.st_dev == sb.st_dev && ob.st_ino == sb.st_ino) return Status(1, "Failed to open file for writing: " + out_path + " is the input file");
+  if (S_ISREG(ob.st_mode) && ftruncate(out.fd, 0) != 0) return Status(1, "Failed to open file for writing: " + out_path + " (" + strerror(errno) + ")");
+  const std::shared_ptr<const Config> C = dev_->cfg;
+  const CfgBind bind(C);
+  const int device = device_;
+  EncoderDevice *dev = dev_;
+  std::lock_guard<std::mutex> lk0(dev->lane[0].mu), lk1(dev->lane[1].mu);  // (lane 0 first, always: nobody else waits for two lanes)
+
+  struct Piece {
+    unsigned long long pos = 0, bytes = 0, n_lines = 0, n_ids = 0, n_text = 0;
+  } piece[2];  // of the item in flight on each lane: upload(i) fills it, work(i) adds the counts, download(i) reads it
+  double s_up = 0, s_split = 0, s_enc = 0, s_fmt = 0, s_down = 0;
+  unsigned long long next_pos = 0, lines_total = 0, ids_total = 0, text_total = 0;  // (the upload leg's; the download leg's three)
+
+  auto upload = [&](size_t i, bool *exhausted) {
+    const unsigned long long pos = next_pos;
+    if (pos >= size) { *exhausted = true; return Status(); }
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned long long end = size;
+    const Status st = upload_piece(in.fd, path, device, dev->lane[i & 1], pos, piece_bytes, size, &end);
+    if (!st.ok()) return st;
+    s_up += secs(t0);
+    piece[i & 1] = Piece{pos, end - pos, 0, 0, 0};
+    next_pos = end;
+    return Status();
+  };
+  auto work = [&](size_t i) {
+    Piece &p = piece[i & 1];
+    EncodeLane &d = dev->lane[i & 1];
+    double ms_split = 0, ms_fmt = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const Status st = subword_text_on_lane(*this, *dev, d, device, d.in.bytes, p.bytes, bos, eos, reverse, dropout_prob, &p.n_lines, &p.n_ids, &p.n_text,
+                                           &ms_split, nullptr, &ms_fmt);
+    s_split += ms_split * 1e-3;
+    s_fmt += ms_fmt * 1e-3;
+    s_enc += secs(t0) - (ms_split + ms_fmt) * 1e-3;
+    return st;
+  };
+  auto download = [&](size_t i) {
+    const Piece p = piece[i & 1];
+    const auto t0 = std::chrono::steady_clock::now();
+    EncodeLane &d = dev->lane[i & 1];
+    const unsigned long long text_base = text_total;
+    std::atomic<bool> write_ok{true};
+    try {
+      if (p.n_text)
+        staged_transfer(device, d.dec.bytes.p, p.n_text, false, [&](void *chunk, unsigned long long o, size_t len) {
+          if (!pwrite_all(out.fd, chunk, len, text_base + o)) { write_ok.store(false); return false; }
+          return true;
+        }, nullptr, ENC_CHUNK);
+    } catch (const GpuError &) {
+      if (!write_ok.load()) return Status(1, "Failed to write file: " + out_path);
+      throw;
+    }
+    text_total += p.n_text;
+    ids_total += p.n_ids;
+    lines_total += p.n_lines;
+    s_down += secs(t0);
+    return Status();
+  };
+  size_t n_pieces = 0;
+  const Status piped = run_two_lanes("encode_file_subword", C, device, PIPE_UNTIL_EXHAUSTED, upload, work, download, &n_pieces);
+  if (!piped.ok()) return piped;
+  const int fd = out.fd;
+  out.fd = -1;
+  if (close(fd) != 0) return Status(1, "Failed to write file: " + out_path);
+  if (n_lines_out) *n_lines_out = lines_total;
+  if (n_ids_out) *n_ids_out = ids_total;
+  if (n_text_out) *n_text_out = text_total;
+  if (report) {
+    char tmp[640];
+    snprintf(tmp, sizeof tmp,
+             "{\"pieces\": %zu, \"piece_bytes\": %llu, \"bytes\": %llu, \"lines\": %llu, \"ids\": %llu, \"text_bytes\": %llu, \"seconds_total\": %.6f, "
+             "\"seconds_read_upload\": %.6f, \"seconds_split\": %.6f, \"seconds_encode\": %.6f, \"seconds_format\": %.6f, \"seconds_download_write\": %.6f}",
+             n_pieces, piece_bytes, size, lines_total, ids_total, text_total, secs(t_begin), s_up, s_split, s_enc, s_fmt, s_down);
     *report = tmp;
   }
   return Status();

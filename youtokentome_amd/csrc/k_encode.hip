@@ -425,6 +425,27 @@ __device__ int dropout_merge(const EncModel &m, A wt, A wr /*next*/, A wm /*prev
   return base;
 }
 
+// What byte i of a sentence is to the encoder: the first byte of a valid char (invalid bytes are dropped, utf8.cpp:111-128) and that char's
+// class by the model's map -- white space, a char of the alphabet (id), or an unknown one.  The one definition of it: enc_tokenize and the
+// SUBWORD formatter's unknown runs (k_subword.h) both read the text through this.
+struct EncChar {
+  bool valid = false, space = false, unk = false;
+  uint32_t id = 0, len = 0;  // the map's value; bytes of the char
+};
+__device__ inline void enc_classify(const EncModel &m, const uint8_t *__restrict__ s, unsigned long long i, unsigned long long nbytes, EncChar &c) {
+  if (i < nbytes && u8_is_start(s, i, nbytes)) {
+    uint32_t len;
+    const uint32_t cp = u8_decode_at(s, i, nbytes, &len);
+    if (cp != INVALID_CP) {
+      c.valid = true;
+      c.id = m.cpmap[cp];
+      c.space = c.id == CP_SPACE;
+      c.unk = c.id == CP_UNK;
+      c.len = len;
+    }
+  }
+}
+
 // UTF-8 decode + char -> token, word starts, unknown-run collapse (bpe.cpp:1497-1530).  Appends the sentence's tokens to
 // wt[n0...) and returns the new end.  A sentence of B bytes yields at most B+1 tokens.
 template <class A>
@@ -435,18 +456,10 @@ __device__ int enc_tokenize(const EncModel &m, const uint8_t *__restrict__ s, un
   bool carry_space = true, carry_unk = false;  // class of the last valid char before this step (start of text acts like a space)
   for (unsigned long long b0 = 0; b0 < nbytes; b0 += 64) {
     const unsigned long long i = b0 + (unsigned long long)lane;
-    bool valid = false, space = false, unk = false;
-    uint32_t id = 0;
-    if (i < nbytes && u8_is_start(s, i, nbytes)) {
-      uint32_t len;
-      const uint32_t cp = u8_decode_at(s, i, nbytes, &len);
-      if (cp != INVALID_CP) {  // invalid bytes are dropped (utf8.cpp:111-128)
-        valid = true;
-        id = m.cpmap[cp];
-        space = id == CP_SPACE;
-        unk = id == CP_UNK;
-      }
-    }
+    EncChar ch;
+    enc_classify(m, s, i, nbytes, ch);
+    const bool valid = ch.valid, space = ch.space, unk = ch.unk;
+    const uint32_t id = ch.id;
     const unsigned long long V = __ballot(valid), S = __ballot(space), U = __ballot(unk);
     bool prev_space = carry_space, prev_unk = carry_unk;
     const unsigned long long pv = V & lt;
@@ -1147,3 +1160,4 @@ void launch_encode_gather(const int32_t *scratch_ids, const unsigned long long *
 
 #include "k_decode.h"  // device decode and the padded encode result: kernels and launchers of this translation unit
 #include "k_lines.h"   // the lines of a text in HBM: kernels and launchers of this translation unit
+#include "k_subword.h"  // SUBWORD output of the ids K5 left: kernels and launchers of this translation unit

@@ -405,6 +405,22 @@ void launch_enc_longest(const unsigned long long *out_off, unsigned long long n_
 void launch_enc_pad(const int32_t *ids, const unsigned long long *out_off, unsigned long long n_sent, unsigned long long width, int32_t pad_value,
                     int32_t *matrix /* 4-byte aligned */, int32_t *lengths, hipStream_t st);
 
+// ---- SUBWORD output (k_subword.h, compiled with k_encode.hip): measure -> launch_exclusive_scan -> write ----
+struct SubInput {  // sentence s = text[soff[s] .. soff[s+1]) and the ids K5 left for it, ids[ioff[s] .. ioff[s+1])
+  const uint8_t *text;
+  const unsigned long long *soff;
+  const int32_t *ids;
+  const unsigned long long *ioff;
+  unsigned long long n_sent;
+  int32_t unk_id;
+  int reverse;  // the ids are stored back to front
+};
+// tb: the pieces as id_to_subword(id, replace_space = false) gives them (no DEC_INVALID marks).  n_ids sizes the groups of sentences.
+void launch_subword_measure(const EncModel &m, const SubInput &in, const DecTable &tb, unsigned long long n_ids, uint32_t *out_len, hipStream_t st);
+// out: 16-byte aligned; out_off: the exclusive scan of out_len, [n_sent + 1]
+void launch_subword_write(const EncModel &m, const SubInput &in, const DecTable &tb, unsigned long long n_ids, const unsigned long long *out_off,
+                          uint8_t *out, hipStream_t st);
+
 // ---- the lines of a text in HBM (k_lines.h, compiled with k_encode.hip): count -> launch_exclusive_scan -> write, then the longest line ----
 // d_text: any address.  lines_tiles: entries of cnt (the scan's input; 0: a text of fewer than two bytes holds no newline that starts a line).
 unsigned long long lines_tiles(const void *d_text, unsigned long long n_bytes);

@@ -1,4 +1,5 @@
-"""Device tensors in, device tensors out: `BPE.encode_tensor` / `BPE.encode_text_tensor` / `BPE.text_lines_tensor` / `BPE.decode_tensor` on top
+"""Device tensors in, device tensors out: `BPE.encode_tensor` / `BPE.encode_text_tensor` / `BPE.text_lines_tensor` / `BPE.decode_tensor` /
+`BPE.encode_subword_tensor` / `BPE.encode_text_subword_tensor` on top
 of the raw device layer of `bpe._Core` (include/yttm_mi355x.h: yttm_encode_device, yttm_encode_text_device, yttm_lines_*, yttm_encode_copy_*,
 yttm_decode_device*, yttm_decode_copy_device).  torch is imported at call
 time; the rest of the package does not need it.
@@ -39,16 +40,8 @@ def _offsets_u64(torch, offsets, dev, what="offsets"):
     return offsets.contiguous()
 
 
-def encode_tensor(bpe, sentences, bos=False, eos=False, reverse=False, dropout_prob=0, padded=True, width=None, pad_id=None, device=None):
-    torch = _torch()
-    core = bpe.bpe_cython
-    dev = _device_of(bpe, device)
-    if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
-        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
-    if padded and pad_id is None:
-        pad_id = bpe.subword_to_id("<PAD>")
-        if pad_id == -1 or bpe.id_to_subword(pad_id) != "<PAD>":
-            raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
+def _sentences_on(torch, sentences, dev):
+    """list[str], or a pair (uint8 bytes [B], int64 / uint64 offsets [n + 1]) on the device -> (bytes, offsets, n, total bytes, longest sentence)"""
     if isinstance(sentences, (list, tuple)) and not (len(sentences) == 2 and hasattr(sentences[0], "data_ptr")):
         from .bpe import _pack
         blob, offs = _pack(list(sentences))
@@ -71,6 +64,20 @@ def encode_tensor(bpe, sentences, bos=False, eos=False, reverse=False, dropout_p
                 raise ValueError("offsets[0] must be 0")
         else:
             total = longest_in = 0
+    return d_bytes, d_off, n, total, longest_in
+
+
+def encode_tensor(bpe, sentences, bos=False, eos=False, reverse=False, dropout_prob=0, padded=True, width=None, pad_id=None, device=None):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, device)
+    if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
+        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+    if padded and pad_id is None:
+        pad_id = bpe.subword_to_id("<PAD>")
+        if pad_id == -1 or bpe.id_to_subword(pad_id) != "<PAD>":
+            raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
+    d_bytes, d_off, n, total, longest_in = _sentences_on(torch, sentences, dev)
     torch.cuda.current_stream(dev).synchronize()  # the inputs are complete before the library's own stream reads them
     n_ids, _ = core.encode_device_raw(d_bytes.data_ptr(), d_off.data_ptr(), n, total, longest_in, bos, eos, reverse, dropout_prob)
     return _take_encoded(torch, core, dev, n, n_ids, padded, width, pad_id)
@@ -188,3 +195,40 @@ def decode_tensor(bpe, ids, lengths=None, offsets=None, ignore_ids=None, as_str=
     torch.cuda.current_stream(dev).synchronize()
     core.copy_decode_device(text.data_ptr(), out_off.data_ptr(), n)
     return text, out_off
+
+
+def _take_text(torch, core, dev, n, n_bytes, as_str):
+    """the pending text of n lines: list[str], or (uint8 text, int64 line_off [n + 1]) tensors that torch owns"""
+    if as_str:
+        raw, off = core.fetch_decode(n, n_bytes)
+        raw, o = raw.tobytes(), off.tolist()
+        return [raw[o[i]:o[i + 1]].decode(errors="replace") for i in range(n)]
+    text = torch.empty(n_bytes, dtype=torch.uint8, device=dev)
+    out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()
+    core.copy_decode_device(text.data_ptr(), out_off.data_ptr(), n)
+    return text, out_off
+
+
+def encode_subword_tensor(bpe, sentences, bos=False, eos=False, reverse=False, dropout_prob=0, device=None, as_str=False):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, device)
+    if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
+        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+    d_bytes, d_off, n, total, longest_in = _sentences_on(torch, sentences, dev)
+    torch.cuda.current_stream(dev).synchronize()  # the inputs are complete before the library's own stream reads them
+    _, n_text, _ = core.subword_device_raw(d_bytes.data_ptr(), d_off.data_ptr(), n, total, longest_in, bos, eos, reverse, dropout_prob)
+    return _take_text(torch, core, dev, n, n_text, as_str)
+
+
+def encode_text_subword_tensor(bpe, text, bos=False, eos=False, reverse=False, dropout_prob=0, as_str=False):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
+        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+    d_text, n_bytes = _text_on(torch, text, dev)
+    torch.cuda.current_stream(dev).synchronize()  # the text is complete before the library's own stream reads it
+    n, _, n_text, _ = core.subword_text_device_raw(d_text.data_ptr(), n_bytes, bos, eos, reverse, dropout_prob)
+    return _take_text(torch, core, dev, n, n_text, as_str)

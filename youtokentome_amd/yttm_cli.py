@@ -52,15 +52,21 @@ def encode(model, output_type, n_threads, bos, eos, reverse, stream, dropout_pro
 @main.command(name="encode_file")
 @click.option("--model", type=click.Path(exists=True), required=True, help="Path to file with learned model.")
 @click.option("--input", "input_path", type=click.Path(exists=True, dir_okay=False), required=True, help="Text file, one sentence per line.")
-@click.option("--output", type=click.Path(), required=True, help="Prefix of the output: PREFIX.ids (int32) and PREFIX.off (uint64), little-endian.")
+@click.option("--output", type=click.Path(), required=True,
+              help="Prefix of the output: PREFIX.ids (int32) and PREFIX.off (uint64), little-endian; with --output_type subword the text file to write.")
+@click.option("--output_type", type=click.Choice(["id", "subword"]), default="id", show_default=True,
+              help="'id': binary ids and offsets; 'subword': the text `encode --output_type subword` prints.")
 @click.option("--bos", is_flag=True, help="Add tab begin of sentence.")
 @click.option("--eos", is_flag=True, help="Add tab end of sentence.")
 @click.option("--reverse", is_flag=True, help="Reverse output sequence of tokens.")
 @click.option("--dropout_prob", type=click.FLOAT, default=0, show_default=True,
               help="BPE-dropout probability (the probability of a merge being dropped)")
-def encode_file(model, input_path, output, bos, eos, reverse, dropout_prob):
-    """Encode a text file to binary ids and line offsets."""
+def encode_file(model, input_path, output, output_type, bos, eos, reverse, dropout_prob):
+    """Encode a text file to binary ids and line offsets, or to a text file of subwords."""
     core = _Core(model)
+    if output_type == "subword":  # the same pipeline with the formatter behind the encode: yttm_encode_file_subword (host_lines.cpp)
+        core.encode_file_subword(input_path, output, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob)
+        return
     core.encode_file(input_path, out=output, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob)  # the C++ pipeline: yttm_encode_file (host_lines.cpp)
 
 
