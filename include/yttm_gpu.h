@@ -72,8 +72,9 @@ int yttm_gpu_merge_apply_scan(yttm_ctx *ctx, const uint32_t *xyz, uint32_t k, co
                               uint32_t next_tau_mx, uint32_t next_want);
 /* Which paths the context's merge rounds and candidate scans took so far -- the counters of the training report, in this order:
  * [0] merge_rounds, [1] word_rounds, [2] word_all_rounds, [3] word_fused_rounds, [4] index_builds, [5] classb_word_rounds,
- * [6] fused_rounds, [7] fused_overflows, [8] hot_rebuilds, [9] top_refills, [10] word_switch_round.  The first min(n, 11) go to out. */
-#define YTTM_ROUND_STATS 11
+ * [6] fused_rounds, [7] fused_overflows, [8] hot_rebuilds, [9] top_refills, [10] word_switch_round, [11] exchange_retries (multi-GPU: rounds
+ * whose exchange was repeated with wider blocks), [12] k3_radix (1: K3 counted class A by radix partition).  The first min(n, 13) go to out. */
+#define YTTM_ROUND_STATS 13
 int yttm_gpu_round_stats(yttm_ctx *ctx, uint64_t *out, uint32_t n);
 /* Measurement mode of K4 (bench.py's untimed pass behind roofline.algorithmic_bytes_8d): on != 0 makes the following
  * yttm_gpu_merge_apply calls also count the WORDS that hold a merge site and their tokens (W_touched, T_touched).

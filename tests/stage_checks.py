@@ -130,11 +130,13 @@ def make_batch(xs, ys, cs, first_id, max_rules, rng=None):
     return batch
 
 
-def assert_whole_state(c, tok, off, cnt, batch, when, same_words=None):
+def assert_whole_state(c, tok, off, cnt, batch, when, same_words=None, recount=None):
     """The device's whole state against the oracle's word table (tok, off, cnt) after `batch` was applied to both: every word with its
     weight, every pair with its count (a from-scratch recount by the oracle), and the batch's own pairs at zero.  same_words(c, tok, off, cnt)
     -> (bool, what differs) may stand in for the comparison of the two sorted word lists (tests/round_checks.py: the same comparison,
-    word by word through a map it keeps between rounds); returns the oracle's recount."""
+    word by word through a map it keeps between rounds); returns the oracle's recount.  recount(tok, off, cnt) -> (xs, ys, cs) sorted by pair
+    stands in for the recount of this table alone where the context's pair table holds more than its own words' pairs (a rank of a
+    multi-GPU run, tests/xchg_checks.py: the recounts of every rank's oracle table, summed)."""
     if same_words is None:
         want = sorted((tuple(tok[int(off[i]):int(off[i + 1])].tolist()), int(cnt[i])) for i in range(len(cnt)))
         assert c.words_as_multiset() == want, f"word table differs after {when}"
@@ -142,7 +144,7 @@ def assert_whole_state(c, tok, off, cnt, batch, when, same_words=None):
         same, what = same_words(c, tok, off, cnt)
         assert same, f"word table differs after {when}: {what}"
     keys, cnts = c.pairs()
-    xs2, ys2, cs2 = O.pair_counts(tok, off, cnt)
+    xs2, ys2, cs2 = (recount or O.pair_counts)(tok, off, cnt)
     wk = (xs2.astype(np.uint64) << np.uint64(32)) | ys2.astype(np.uint64)
     assert np.array_equal(keys, wk), f"pair set differs after {when}" + _first_pair_difference(keys, cnts, wk, cs2)
     assert np.array_equal(cnts, cs2), f"pair counts differ after {when}" + _first_pair_difference(keys, cnts, wk, cs2)

@@ -25,6 +25,10 @@ class Ctx:
     def __del__(self):
         self.close()
 
+    def set_comm(self, comm):
+        """multi-GPU: a communicator (yttm_comm*) before the stages run; the context then holds ITS shard, the pair table GLOBAL counts"""
+        self._chk(self.L.yttm_gpu_ctx_set_comm(self.h, comm))
+
     def upload(self, text: bytes):
         self._chk(self.L.yttm_gpu_upload_corpus(self.h, text, len(text)))
 
@@ -89,7 +93,7 @@ class Ctx:
                                                    next_tau_mx, next_want))
 
     ROUND_STATS = ("merge_rounds", "word_rounds", "word_all_rounds", "word_fused_rounds", "index_builds", "classb_word_rounds", "fused_rounds",
-                   "fused_overflows", "hot_rebuilds", "top_refills", "word_switch_round")
+                   "fused_overflows", "hot_rebuilds", "top_refills", "word_switch_round", "exchange_retries", "k3_radix")
 
     def round_stats(self):
         out = np.zeros(len(self.ROUND_STATS), np.uint64)

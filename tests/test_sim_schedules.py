@@ -14,6 +14,7 @@ import gen
 import oracle_lib as O
 import round_checks as R
 import stage_checks as S
+import xchg_checks as X
 
 pytestmark = pytest.mark.usefixtures("sim_lib")
 
@@ -86,6 +87,18 @@ def test_word_mode_round_state(sched, monkeypatch):
     monkeypatch.setenv("HIPSIM_SCHED", sched)
     R.run_scenario(monkeypatch, "a", "default", rounds=20)
     R.run_scenario(monkeypatch, "c", "default", rounds=20)
+
+
+@pytest.mark.parametrize("sched", SCHEDULES)
+def test_multi_rank_exchange_round_state(sched, monkeypatch):
+    """two and three ranks' per-round delta exchange, every rank's state against the oracle after every round (tests/xchg_checks.py), where the
+    order of workgroups and lanes matters most: dt_add's claim of a slot and publication of its record number, the fold's appends to the
+    lists -- blocks too small and the notes overflowed (a repeat behind a walk over every block), tiny lists over mirrored shards, and class-C
+    words on one rank"""
+    monkeypatch.setenv("HIPSIM_SCHED", sched)
+    X.run_row(monkeypatch, "notes", "with_repeats", 2, rounds=20)
+    X.run_row(monkeypatch, "mirrored", "tiny_lists", 3)  # (all its rounds: the crossings by the ranks' sum are a few in forty)
+    X.run_row(monkeypatch, "giant", "small_blocks", 2, rounds=20)
 
 
 @pytest.mark.parametrize("sched", SCHEDULES)

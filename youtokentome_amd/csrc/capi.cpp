@@ -442,7 +442,7 @@ int yttm_gpu_round_stats(yttm_ctx *c, uint64_t *out, uint32_t n) {
   GUARD_CTX({
     const GpuCtx &g = *c->g;
     const unsigned long long v[YTTM_ROUND_STATS] = {g.merge_rounds, g.word_rounds, g.word_all_rounds, g.word_fused_rounds, g.index_builds, g.classb_word_rounds,
-                                                    g.fused_rounds, g.fused_overflows, g.hot_rebuilds, g.top_refills, g.word_switch_round};
+                                                    g.fused_rounds, g.fused_overflows, g.hot_rebuilds, g.top_refills, g.word_switch_round, g.exchange_retries, g.k3_radix};
     for (uint32_t i = 0; i < std::min<uint32_t>(n, YTTM_ROUND_STATS); i++) out[i] = v[i];
   })
 }

@@ -132,8 +132,8 @@ bool GpuCtx::settle_exchange(unsigned long long xmask, unsigned long long xmax, 
   }
   blk_ = std::max(blk_, want);
   exchange_retries++;
-  // the scan that came too early also zeroed the finished batch's pairs; deltas that arrived after that (k_giant.hip retracts
-  // every old adjacency of a re-counted tile, the merged pairs included) must be zeroed again
+  // the scan that came too early also zeroed the finished batch's pairs: should a delta for one of them arrive with the repeat, it is
+  // zeroed again.  (A safeguard: the tile and word kernels send none, and k_giant.hip's retraction leaves the batch's pairs alone.)
   pending_zero_ = zero_valid_;
   return true;
 }
