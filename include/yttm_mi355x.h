@@ -141,6 +141,43 @@ int yttm_encode_file_subword(yttm_encoder *enc, const char *path, const char *ou
                              uint64_t chunk_bytes, uint64_t *n_lines, uint64_t *n_ids, uint64_t *n_text_bytes, char *report_json, int report_len,
                              char *err, int errlen);
 
+/* Decimal id text on the device: the format `yttm encode --output_type id` prints and `yttm decode` reads, one sentence per line.
+ * yttm_ids_parse_device = yttm_lines_device, then the ids `while (ss >> x) ids.push_back(x)` reads from every line in the C locale
+ * (bpe.cpp:1863-1873): white space is 0x20 and 0x09 .. 0x0D; a number is a maximal run of digits, negated iff the byte just before it is '-'
+ * (so "12-3" is 12, -3); a line ends at its first fail point -- a byte that is neither white space, a digit nor a sign, a sign whose next byte in
+ * the line is not a digit, or a number outside int32, which is itself dropped -- and nothing carries over to the next line.  The lines' offsets
+ * are pending as after yttm_lines_device, the ids exactly as after yttm_encode_device with n_sent = *n_lines (yttm_encode_fetch,
+ * yttm_encode_copy_device, yttm_encode_copy_padded).  kernel_ms (optional) = split + measure + scan + write.  d_text: any address. */
+int yttm_ids_parse_device(yttm_encoder *enc, const void *d_text, uint64_t n_bytes, uint64_t *n_lines, uint64_t *n_ids, double *kernel_ms, char *err,
+                          int errlen);
+/* yttm_ids_parse_device, then the device decode of those ids with a '\n' behind every line: lines and ids are pending as after the parse, the text
+ * in the encoder's text slot (yttm_decode_fetch / yttm_decode_copy_device: out_offsets[*n_lines + 1], line i = bytes[out_offsets[i] ..
+ * out_offsets[i+1]) including its '\n') -- concatenated, byte for byte what yttm_decode_cli writes for the same input.  A kept id outside
+ * [0, vocab_size) that is not ignored fails the call with the message and code (1) of yttm_decode, naming the first such id in line order, then
+ * position order (ids behind a line's fail point are not ids); then the parse's results are pending and no text is.  kernel_ms (optional) =
+ * split + parse + decode.  replaces: decode_cli, bpe.h:70, bpe.cpp:2016-2028, on decode(const vector<string>&, ...) bpe.cpp:1863-1882 */
+int yttm_decode_text_device(yttm_encoder *enc, const void *d_text, uint64_t n_bytes, const int32_t *ignore_ids, uint64_t n_ignore, uint64_t *n_lines,
+                            uint64_t *n_ids, uint64_t *n_text_bytes, double *kernel_ms, char *err, int errlen);
+/* A file of decimal ids of any size -> the file `yttm decode < path` prints, byte for byte, written to out_path.  The pipeline of
+ * yttm_encode_file_subword: upload of one piece beside split + parse + decode of the one before and the download and write of the text of the one
+ * before that; the same file errors and messages, the same refusal to write over the input; the file does not depend on chunk_bytes.
+ * report_json (optional): the keys of yttm_encode_file ("seconds_encode" is 0) plus "seconds_parse", "seconds_decode" and "text_bytes".  An id
+ * that is neither ignored nor valid ends the call with the decode's message for the first such id in file order and leaves a partial file.
+ * Uses both lanes: a pending device result does not survive the call.  bpe.h:70, bpe.cpp:2016-2028, :1863-1882 */
+int yttm_decode_file(yttm_encoder *enc, const char *path, const char *out_path, const int32_t *ignore_ids, uint64_t n_ignore, uint64_t chunk_bytes,
+                     uint64_t *n_lines, uint64_t *n_ids, uint64_t *n_text_bytes, char *report_json, int report_len, char *err, int errlen);
+/* The pending encode result (of yttm_encode_device, yttm_encode_text_device, yttm_ids_parse_device, ...; n_sent must be its) as the text `yttm encode
+ * --output_type id` prints: every id in decimal, '-' for a negative one, followed by one space, then '\n' per sentence (utils.h:92-103); an empty
+ * sentence is "\n".  The text is pending in the encoder's text slot as after yttm_subword_device, the ids stay pending.  No pending result of
+ * n_sent sentences: code 1, and nothing that was pending is replaced.  kernel_ms (optional) = measure + scan + write.
+ * replaces: the id formatting of encode_cli, bpe.cpp:1942-2014 */
+int yttm_idtext_device(yttm_encoder *enc, uint64_t n_sent, uint64_t *n_text_bytes, double *kernel_ms, char *err, int errlen);
+/* A text file of any size -> the file `yttm encode --output_type id < path` prints, byte for byte: yttm_encode_file_subword with the id printer in
+ * place of the SUBWORD formatter (same pipeline, errors, report keys).  bpe.h:66-68, bpe.cpp:1942-2014 */
+int yttm_encode_file_idtext(yttm_encoder *enc, const char *path, const char *out_path, int bos, int eos, int reverse, double dropout_prob,
+                            uint64_t chunk_bytes, uint64_t *n_lines, uint64_t *n_ids, uint64_t *n_text_bytes, char *report_json, int report_len,
+                            char *err, int errlen);
+
 /* Word-level encode cache (SURVEY.md 8f "N4"; the reference has no counterpart: bpe.cpp:1497-1632 encodes every word occurrence).
  * mode 0: every batch goes straight through the encode kernel; 1: distinct words are encoded once whenever that is possible
  * (dropout_prob == 0); 2 (default): the same for batches of at least min_bytes.  The ids are identical either way.

@@ -25,6 +25,7 @@ EXPORTS = [
     "yttm_decode_device", "yttm_decode_device_padded", "yttm_decode_fetch", "yttm_decode_copy_device", "yttm_encode_copy_device", "yttm_encode_copy_padded",
     "yttm_lines_device", "yttm_lines_copy_device", "yttm_lines_fetch", "yttm_encode_text_device", "yttm_encode_file",
     "yttm_subword_device", "yttm_subword_text_device", "yttm_encode_file_subword",
+    "yttm_ids_parse_device", "yttm_decode_text_device", "yttm_decode_file", "yttm_idtext_device", "yttm_encode_file_idtext",
     "yttm_device_info", "yttm_comm_rccl_unique_id", "yttm_comm_rccl_create", "yttm_comm_callback_create",
     "yttm_comm_destroy", "yttm_train_bpe_comm", "yttm_train_bpe_from_device_comm", "yttm_train_bpe_from_memory_comm",
     # include/yttm_gpu.h
@@ -75,6 +76,11 @@ def load():
     L.yttm_subword_device.argtypes = [cvp, cvp, cvp, C.c_uint64, C.c_uint64, C.c_uint64, ci, ci, ci, cd, u64p, u64p, C.POINTER(cd), cs, ci]
     L.yttm_subword_text_device.argtypes = [cvp, cvp, C.c_uint64, ci, ci, ci, cd, u64p, u64p, u64p, C.POINTER(cd), cs, ci]
     L.yttm_encode_file_subword.argtypes = [cvp, cs, cs, ci, ci, ci, cd, C.c_uint64, u64p, u64p, u64p, cs, ci, cs, ci]
+    L.yttm_ids_parse_device.argtypes = [cvp, cvp, C.c_uint64, u64p, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_decode_text_device.argtypes = [cvp, cvp, C.c_uint64, i32p, C.c_uint64, u64p, u64p, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_decode_file.argtypes = [cvp, cs, cs, i32p, C.c_uint64, C.c_uint64, u64p, u64p, u64p, cs, ci, cs, ci]
+    L.yttm_idtext_device.argtypes = [cvp, C.c_uint64, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_encode_file_idtext.argtypes = [cvp, cs, cs, ci, ci, ci, cd, C.c_uint64, u64p, u64p, u64p, cs, ci, cs, ci]
     L.yttm_encoder_set_cache.argtypes = [cvp, ci, C.c_uint64]
     L.yttm_encode_cache_words.argtypes = [cvp]
     L.yttm_encode_cache_words.restype = C.c_uint64

@@ -263,6 +263,62 @@ class _Core:
             return json.loads(rep.value.decode())
         return nl.value, ni.value, nt.value
 
+    # ---- decimal id text on the device (include/yttm_mi355x.h): the format `yttm encode --output_type id` prints and `yttm decode` reads
+    def ids_parse_device_raw(self, d_text, n_bytes):
+        """-> (n_lines, n_ids, kernel_ms); the ids `while (ss >> x)` reads from every line are pending as after encode_device_raw with n_sent = n_lines"""
+        nl, ni, ms, err = C.c_uint64(), C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_ids_parse_device(self._h, C.c_void_p(d_text), n_bytes, C.byref(nl), C.byref(ni), C.byref(ms), err, _lib.ERRLEN), err)
+        return nl.value, ni.value, ms.value
+
+    def decode_text_device_raw(self, d_text, n_bytes, ignore_ids=None):
+        """-> (n_lines, n_ids, n_text_bytes, kernel_ms); the decoded lines, a newline behind each, are pending in the text slot"""
+        ign, ign_p, n_ign = self._ignore(ignore_ids)
+        nl, ni, nt, ms, err = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_decode_text_device(self._h, C.c_void_p(d_text), n_bytes, ign_p, n_ign, C.byref(nl), C.byref(ni), C.byref(nt), C.byref(ms),
+                                                        err, _lib.ERRLEN), err)
+        return nl.value, ni.value, nt.value, ms.value
+
+    def idtext_device_raw(self, n_sent):
+        """the pending encode result of n_sent sentences as decimal text in the text slot -> (n_text_bytes, kernel_ms)"""
+        nt, ms, err = C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_idtext_device(self._h, n_sent, C.byref(nt), C.byref(ms), err, _lib.ERRLEN), err)
+        return nt.value, ms.value
+
+    def decode_file(self, path, out, ignore_ids=None, chunk_bytes=None, report=False):
+        """a text file of decimal ids, one sentence per line -> the text file `yttm decode` prints for it, written to `out`:
+        (n_lines, n_ids, n_text_bytes), or with report=True the call's report (a dict)"""
+        if out is None:
+            raise ValueError("decode_file needs out, the path of the text file to write")
+        ign, ign_p, n_ign = self._ignore(ignore_ids)
+        nl, ni, nt, err = C.c_uint64(), C.c_uint64(), C.c_uint64(), _err()
+        rep = C.create_string_buffer(1024)
+        rc = _lib.load().yttm_decode_file(self._h, os.fsencode(path), os.fsencode(out), ign_p, n_ign, int(chunk_bytes or 0), C.byref(nl), C.byref(ni),
+                                          C.byref(nt), rep, len(rep), err, _lib.ERRLEN)
+        if rc != 0:
+            raise ValueError(err.value.decode(errors="replace"))
+        if report:
+            import json
+            return json.loads(rep.value.decode())
+        return nl.value, ni.value, nt.value
+
+    def encode_file_idtext(self, path, out, bos=False, eos=False, reverse=False, dropout_prob=0.0, chunk_bytes=None, report=False):
+        """a text file -> the text file `yttm encode --output_type id` prints for it, written to `out`: (n_lines, n_ids, n_text_bytes), or with
+        report=True the call's report (a dict)"""
+        if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
+            raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+        if out is None:
+            raise ValueError("encode_file with id_text=True needs out, the path of the text file to write")
+        nl, ni, nt, err = C.c_uint64(), C.c_uint64(), C.c_uint64(), _err()
+        rep = C.create_string_buffer(1024)
+        rc = _lib.load().yttm_encode_file_idtext(self._h, os.fsencode(path), os.fsencode(out), int(bos), int(eos), int(reverse), float(dropout_prob),
+                                                 int(chunk_bytes or 0), C.byref(nl), C.byref(ni), C.byref(nt), rep, len(rep), err, _lib.ERRLEN)
+        if rc != 0:
+            raise ValueError(err.value.decode(errors="replace"))
+        if report:
+            import json
+            return json.loads(rep.value.decode())
+        return nl.value, ni.value, nt.value
+
     def encode(self, sentences, output_type, bos, eos, reverse, dropout_prob):
         if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
             raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
@@ -442,14 +498,21 @@ class BPE:
         return tensor.text_lines_tensor(self, text)
 
     def encode_file(self, path, out: Optional[str] = None, bos: bool = False, eos: bool = False, reverse: bool = False, dropout_prob: float = 0,
-                    chunk_bytes: Optional[int] = None, output_type: OutputType = OutputType.ID, report: bool = False):
+                    chunk_bytes: Optional[int] = None, output_type: OutputType = OutputType.ID, report: bool = False, id_text: bool = False):
         """A text file, one sentence per line -> (ids np.int32, offsets np.uint64 [n_lines + 1]); with out=PREFIX the raw little-endian files
         PREFIX.ids (int32) and PREFIX.off (uint64) are written instead and (n_lines, n_ids) is returned.  Needs no torch.
         output_type=OutputType.SUBWORD: `out` is required and is the path of a text file, written as `yttm encode --output_type subword` prints it
         (every piece followed by a space, a newline per sentence); returns (n_lines, n_ids, n_text_bytes).  report=True: the call's report (a dict)
-        is appended to the ID result, and is the SUBWORD result."""
+        is appended to the ID result, and is the SUBWORD result.
+        output_type=OutputType.ID with id_text=True: `out` is required and is the path of a text file, written as `yttm encode --output_type id`
+        prints it (every id in decimal followed by a space, a newline per sentence); returns (n_lines, n_ids, n_text_bytes), or the report."""
         if not isinstance(output_type, OutputType):
             raise TypeError("parameter output_type must be youtokentome.OutputType, not %s}" % str(type(output_type)))
+        if id_text:
+            if output_type != OutputType.ID:
+                raise ValueError("id_text goes with output_type ID")
+            return self.bpe_cython.encode_file_idtext(path, out, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, chunk_bytes=chunk_bytes,
+                                                      report=report)
         if output_type == OutputType.SUBWORD:
             return self.bpe_cython.encode_file_subword(path, out, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, chunk_bytes=chunk_bytes,
                                                        report=report)
@@ -467,6 +530,23 @@ class BPE:
         """the same for `text` as encode_text_tensor takes it, one sentence per line"""
         from . import tensor
         return tensor.encode_text_subword_tensor(self, text, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, as_str=as_str)
+
+    # ---- decimal id text, one sentence per line: the format `yttm encode --output_type id` prints and `yttm decode` reads
+    def decode_file(self, path, out: str, ignore_ids: Optional[Collection] = None, chunk_bytes: Optional[int] = None, report: bool = False):
+        """A text file of decimal ids -> the text file `yttm decode < path` prints, written to `out`, made on the device file to file.  Returns
+        (n_lines, n_ids, n_text_bytes), or with report=True the call's report (a dict).  Needs no torch."""
+        return self.bpe_cython.decode_file(path, out, ignore_ids=ignore_ids, chunk_bytes=chunk_bytes, report=report)
+
+    def decode_text_tensor(self, text, ignore_ids: Optional[Collection] = None, as_str: bool = True):
+        """`text` as encode_text_tensor takes it, holding decimal ids, one sentence per line -> the decoded lines as list[str] (without their
+        newlines), or with as_str=False (uint8 text, int64 line_off [n_lines + 1]) on the device, every line with its newline"""
+        from . import tensor
+        return tensor.decode_text_tensor(self, text, ignore_ids=ignore_ids, as_str=as_str)
+
+    def parse_ids_tensor(self, text, padded: bool = False, width: Optional[int] = None, pad_id: Optional[int] = None):
+        """`text` as encode_text_tensor takes it, holding decimal ids, one sentence per line -> the ids as encode_text_tensor returns them"""
+        from . import tensor
+        return tensor.parse_ids_tensor(self, text, padded=padded, width=width, pad_id=pad_id)
 
     def decode_tensor(self, ids, lengths=None, offsets=None, ignore_ids: Optional[Collection] = None, as_str: bool = True):
         from . import tensor

@@ -271,6 +271,51 @@ int yttm_encode_file_subword(yttm_encoder *h, const char *path, const char *out_
   return finish(s, err, errlen);
 }
 
+int yttm_ids_parse_device(yttm_encoder *h, const void *d_text, uint64_t n_bytes, uint64_t *n_lines, uint64_t *n_ids, double *kernel_ms, char *err, int errlen) {
+  unsigned long long nl = 0, ni = 0;
+  Status s = h->enc->ids_parse_device(d_text, n_bytes, &nl, &ni, kernel_ms);
+  if (n_lines) *n_lines = nl;
+  if (n_ids) *n_ids = ni;
+  return finish(s, err, errlen);
+}
+int yttm_decode_text_device(yttm_encoder *h, const void *d_text, uint64_t n_bytes, const int32_t *ignore_ids, uint64_t n_ignore, uint64_t *n_lines,
+                            uint64_t *n_ids, uint64_t *n_text_bytes, double *kernel_ms, char *err, int errlen) {
+  unsigned long long nl = 0, ni = 0, nt = 0;
+  Status s = h->enc->decode_text_device(d_text, n_bytes, ignore_ids, n_ignore, &nl, &ni, &nt, kernel_ms);
+  if (n_lines) *n_lines = nl;
+  if (n_ids) *n_ids = ni;
+  if (n_text_bytes) *n_text_bytes = nt;
+  return finish(s, err, errlen);
+}
+int yttm_decode_file(yttm_encoder *h, const char *path, const char *out_path, const int32_t *ignore_ids, uint64_t n_ignore, uint64_t chunk_bytes,
+                     uint64_t *n_lines, uint64_t *n_ids, uint64_t *n_text_bytes, char *report_json, int report_len, char *err, int errlen) {
+  unsigned long long nl = 0, ni = 0, nt = 0;
+  std::string report;
+  Status s = h->enc->decode_file(path ? path : "", out_path ? out_path : "", ignore_ids, n_ignore, chunk_bytes, &nl, &ni, &nt, &report);
+  if (n_lines) *n_lines = nl;
+  if (n_ids) *n_ids = ni;
+  if (n_text_bytes) *n_text_bytes = nt;
+  if (s.ok() && report_json && report_len > 0) snprintf(report_json, (size_t)report_len, "%s", report.c_str());
+  return finish(s, err, errlen);
+}
+int yttm_idtext_device(yttm_encoder *h, uint64_t n_sent, uint64_t *n_text_bytes, double *kernel_ms, char *err, int errlen) {
+  unsigned long long nt = 0;
+  Status s = h->enc->idtext_device(n_sent, &nt, kernel_ms);
+  if (n_text_bytes) *n_text_bytes = nt;
+  return finish(s, err, errlen);
+}
+int yttm_encode_file_idtext(yttm_encoder *h, const char *path, const char *out_path, int bos, int eos, int reverse, double dropout_prob, uint64_t chunk_bytes,
+                            uint64_t *n_lines, uint64_t *n_ids, uint64_t *n_text_bytes, char *report_json, int report_len, char *err, int errlen) {
+  unsigned long long nl = 0, ni = 0, nt = 0;
+  std::string report;
+  Status s = h->enc->encode_file_idtext(path ? path : "", out_path ? out_path : "", bos, eos, reverse, dropout_prob, chunk_bytes, &nl, &ni, &nt, &report);
+  if (n_lines) *n_lines = nl;
+  if (n_ids) *n_ids = ni;
+  if (n_text_bytes) *n_text_bytes = nt;
+  if (s.ok() && report_json && report_len > 0) snprintf(report_json, (size_t)report_len, "%s", report.c_str());
+  return finish(s, err, errlen);
+}
+
 int yttm_encoder_set_cache(yttm_encoder *h, int mode, uint64_t min_bytes) {
   h->enc->set_cache(mode, min_bytes);
   return 0;

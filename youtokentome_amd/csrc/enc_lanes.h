@@ -191,6 +191,14 @@ unsigned long long scan_counts(EncodeLane &d, const uint32_t *counts, unsigned l
 Status format_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_text, const void *d_soff, bool reverse,
                       unsigned long long *n_text_bytes, double *kernel_ms);
 
+// Device decode of ids in HBM on the lane (locked by the caller), the text left in the lane's text slot: measure -> scan -> write (k_decode.h).
+// n_flat: the ids the kernels walk; newline (ragged input only): a '\n' behind every sentence.  An id that is neither ignored nor valid: the
+// host path's message, code 1, and no text is pending.
+Status decode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, DecInput in, unsigned long long n_flat,
+                      const int32_t *ignore_ids, unsigned long long n_ignore, unsigned long long *n_bytes, double *kernel_ms, bool newline);
+// The decimal text of the encode result pending on the lane (locked by the caller), left in the lane's text slot (k_idtext.h)
+Status idtext_on_lane(EncodeLane &d, int device, unsigned long long *n_text_bytes, double *kernel_ms);
+
 // Host arrays of a large batch cross the link through the trainer's pinned chunks (gpu_ctx.cpp staged_transfer; 1e7 sentences are 1.3 GB up
 // and 1.2 GB down: a plain copy from / to pageable memory moves them at a fraction of the link's rate, and the first touch of a freshly
 // allocated result array is paid by one thread); small ones as plain copies on the lane's stream.

@@ -148,6 +148,22 @@ class BaseEncoder {  // bpe.h:22-82
   Status encode_file_subword(const std::string &path, const std::string &out_path, bool bos, bool eos, bool reverse, double dropout_prob,
                              unsigned long long piece_bytes, unsigned long long *n_lines, unsigned long long *n_ids, unsigned long long *n_text_bytes,
                              std::string *report) const;
+  // Decimal id text on the device (host_lines.cpp, host_decode.cpp, k_idtext.h), the format `yttm encode --output_type id` prints and `yttm decode`
+  // reads.  ids_parse_device: split + the ids `while (ss >> x)` reads from every line (bpe.cpp:1863-1873), pending as after encode_device with
+  // n_sent = *n_lines; decode_text_device: the same, then the device decode of those ids with a '\n' behind every line (decode_cli,
+  // bpe.cpp:2016-2028), the text in lane 0's text slot; decode_file: a file of such text -> the file `yttm decode` prints, through both lanes;
+  // idtext_device: the pending encode result -> its decimal text (utils.h:92-103) in the text slot; encode_file_idtext: encode_file_subword with
+  // that printer in place of the SUBWORD formatter.
+  Status ids_parse_device(const void *d_text, unsigned long long n_bytes, unsigned long long *n_lines, unsigned long long *n_ids, double *kernel_ms) const;
+  Status decode_text_device(const void *d_text, unsigned long long n_bytes, const int32_t *ignore_ids, unsigned long long n_ignore,
+                            unsigned long long *n_lines, unsigned long long *n_ids, unsigned long long *n_text_bytes, double *kernel_ms) const;
+  Status decode_file(const std::string &path, const std::string &out_path, const int32_t *ignore_ids, unsigned long long n_ignore,
+                     unsigned long long piece_bytes, unsigned long long *n_lines, unsigned long long *n_ids, unsigned long long *n_text_bytes,
+                     std::string *report) const;
+  Status idtext_device(unsigned long long n_sent, unsigned long long *n_text_bytes, double *kernel_ms) const;
+  Status encode_file_idtext(const std::string &path, const std::string &out_path, bool bos, bool eos, bool reverse, double dropout_prob,
+                            unsigned long long piece_bytes, unsigned long long *n_lines, unsigned long long *n_ids, unsigned long long *n_text_bytes,
+                            std::string *report) const;
   // the YTTM_* hooks as they stood when THIS encoder was made: every entry point binds them to its thread (yttm_config.h CfgBind), so that a
   // later encoder or training never changes the paths of this one
   std::shared_ptr<const Config> config() const;

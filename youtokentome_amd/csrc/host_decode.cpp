@@ -1,5 +1,6 @@
-// host_decode.cpp -- host side of the device decode (k_decode.h), of the SUBWORD formatter (k_subword.h), which leaves its text in the decode's
-// slot, and the device-to-device exits of the encoder's and the decoder's results, on the encoder's lanes (enc_lanes.h).
+// host_decode.cpp -- host side of the device decode (k_decode.h), of the SUBWORD formatter (k_subword.h) and the id printer (k_idtext.h), which
+// leave their text in the decode's slot, and the device-to-device exits of the encoder's and the decoder's results, on the encoder's lanes
+// (enc_lanes.h).
 //
 // Results live in lane 0 like those of encode_device, in buffers of their own: a decode leaves a pending encode result alone and the other way
 // round.  Every call locks the lane and returns after the lane's stream has synchronised; a pair (decode_device, fetch) is not atomic.
@@ -44,8 +45,9 @@ static void decode_table(const BaseEncoder &enc, EncoderDevice &D) {
 }
 
 // measure -> scan -> write on the lane (locked by the caller).  n_flat: the ids the kernels walk (ragged: n_ids; padded: n_sent * stride).
-static Status decode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, DecInput in, unsigned long long n_flat,
-                             const int32_t *ignore_ids, unsigned long long n_ignore, unsigned long long *n_bytes, double *kernel_ms) {
+// newline (ragged input only): a '\n' behind every sentence, as decode_cli writes its lines.
+Status decode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, DecInput in, unsigned long long n_flat,
+                      const int32_t *ignore_ids, unsigned long long n_ignore, unsigned long long *n_bytes, double *kernel_ms, bool newline) {
   return on_device(device, [&]() -> Status {
     d.dec.valid = false;
     if (n_bytes) *n_bytes = 0;
@@ -79,7 +81,7 @@ static Status decode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLan
     EventPair ev(d.st, kernel_ms != nullptr);
     ev.start();
     HIP_CHECK(hipMemsetAsync(d.dec.misc, 0xff, 8, d.st));
-    launch_decode_measure(in, tb, ig, n_flat, d.dec.len, d.dec.misc, d.st);
+    launch_decode_measure(in, tb, ig, n_flat, d.dec.len, d.dec.misc, d.st, newline);
     unsigned long long bad = ~0ull;
     HIP_CHECK(hipMemcpyAsync(&bad, d.dec.misc, 8, hipMemcpyDeviceToHost, d.st));
     const unsigned long long total = scan_counts(d, d.dec.len, in.n_sent, d.dec.off);  // (syncs: `bad` is here)
@@ -93,7 +95,7 @@ static Status decode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLan
     }
     d.dec.bytes.grow((size_t)total + 16);
     if (((uintptr_t)d.dec.bytes.p & 15u) != 0) throw GpuError{"decode: the output blob is not 16-byte aligned"};
-    launch_decode_write(in, tb, ig, n_flat, d.dec.off, d.dec.bytes, d.st);
+    launch_decode_write(in, tb, ig, n_flat, d.dec.off, d.dec.bytes, d.st, newline);
     ev.stop();
     HIP_CHECK(hipStreamSynchronize(d.st));
     if (kernel_ms) *kernel_ms = ev.elapsed_ms();
@@ -112,7 +114,7 @@ Status BaseEncoder::decode_device(const void *d_ids, const void *d_offsets, unsi
   const CfgBind bind(dev_->cfg);
   std::lock_guard<std::mutex> lk(dev_->lane[0].mu);
   const DecInput in{(const int32_t *)d_ids, (const unsigned long long *)d_offsets, nullptr, 0, 0, n_sent};
-  return decode_on_lane(*this, *dev_, dev_->lane[0], device_, in, n_ids, ignore_ids, n_ignore, n_bytes, kernel_ms);
+  return decode_on_lane(*this, *dev_, dev_->lane[0], device_, in, n_ids, ignore_ids, n_ignore, n_bytes, kernel_ms, false);
 }
 
 Status BaseEncoder::decode_device_padded(const void *d_ids, unsigned long long n_sent, unsigned long long width, unsigned long long row_stride,
@@ -125,7 +127,7 @@ Status BaseEncoder::decode_device_padded(const void *d_ids, unsigned long long n
   const CfgBind bind(dev_->cfg);
   std::lock_guard<std::mutex> lk(dev_->lane[0].mu);
   const DecInput in{(const int32_t *)d_ids, nullptr, (const int32_t *)d_lengths, width, row_stride, n_sent};
-  return decode_on_lane(*this, *dev_, dev_->lane[0], device_, in, n_sent * row_stride, ignore_ids, n_ignore, n_bytes, kernel_ms);
+  return decode_on_lane(*this, *dev_, dev_->lane[0], device_, in, n_sent * row_stride, ignore_ids, n_ignore, n_bytes, kernel_ms, false);
 }
 
 Status BaseEncoder::fetch_decode_result(char *bytes, unsigned long long *out_off, unsigned long long n_sent) const {
@@ -252,6 +254,51 @@ Status format_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, i
     if (n_text_bytes) *n_text_bytes = total;
     return Status();
   });
+}
+
+// ---- id text (k_idtext.h) ------------------------------------------------------------------------------------------------------------------
+// The text `yttm encode --output_type id` prints for the encode result pending on the lane (utils.h:92-103: every id and a space, a newline per
+// sentence), left in the lane's text slot like the SUBWORD text; the ids stay pending.  Needs no input text and no table.
+Status idtext_on_lane(EncodeLane &d, int device, unsigned long long *n_text_bytes, double *kernel_ms) {
+  return on_device(device, [&]() -> Status {
+    d.dec.valid = false;
+    if (n_text_bytes) *n_text_bytes = 0;
+    if (kernel_ms) *kernel_ms = 0;
+    const unsigned long long n_sent = d.res.n_sent;
+    if (n_sent == 0) {
+      d.dec.n_sent = d.dec.n_bytes = 0;
+      d.dec.valid = true;
+      return Status();
+    }
+    d.dec.len.grow((size_t)n_sent);
+    d.dec.off.grow((size_t)n_sent + 1);
+    EventPair ev(d.st, kernel_ms != nullptr);
+    ev.start();
+    launch_idprint_measure(d.res.ids, d.res.off, n_sent, d.res.n_ids, d.dec.len, d.st);
+    const unsigned long long total = scan_counts(d, d.dec.len, n_sent, d.dec.off);  // (syncs)
+    d.dec.bytes.grow((size_t)total + 16);
+    if (((uintptr_t)d.dec.bytes.p & 15u) != 0) throw GpuError{"idtext: the output blob is not 16-byte aligned"};
+    launch_idprint_write(d.res.ids, d.res.off, n_sent, d.res.n_ids, d.dec.off, d.dec.bytes, d.st);
+    ev.stop();
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    if (kernel_ms) *kernel_ms = ev.elapsed_ms();
+    d.dec.n_sent = n_sent;
+    d.dec.n_bytes = total;
+    d.dec.valid = true;
+    if (n_text_bytes) *n_text_bytes = total;
+    return Status();
+  });
+}
+
+Status BaseEncoder::idtext_device(unsigned long long n_sent, unsigned long long *n_text_bytes, double *kernel_ms) const {
+  if (n_text_bytes) *n_text_bytes = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  if (!dev_) return Status(1, "idtext_device: no matching encode result");
+  const CfgBind bind(dev_->cfg);
+  EncodeLane &d = dev_->lane[0];
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (n_sent != d.res.n_sent) return Status(1, "idtext_device: no matching encode result");  // (before any work: a pending text stays)
+  return idtext_on_lane(d, device_, n_text_bytes, kernel_ms);
 }
 
 Status BaseEncoder::subword_device(const void *d_bytes, const void *d_offsets, unsigned long long n_sent, unsigned long long total_bytes,

@@ -1,6 +1,6 @@
 // host_lines.cpp -- host side of the line split (k_lines.h) and the encoder's entries for text that is not yet cut into sentences: a buffer in HBM
-// (lines_device, encode_text_device, subword_text_device) and a file of any size (encode_file, encode_file_subword), on the encoder's lanes
-// (enc_lanes.h).
+// (lines_device, encode_text_device, subword_text_device; decimal id text: ids_parse_device, decode_text_device) and a file of any size
+// (encode_file; text to text: encode_file_subword, encode_file_idtext, decode_file), on the encoder's lanes (enc_lanes.h).
 //
 // The offsets of a split live in the lane like the results of encode_device and decode_device, in buffers of their own: a split leaves a pending
 // encode or decode result alone.  Every call locks the lane and returns after the lane's stream has synchronised.
@@ -143,6 +143,93 @@ Status BaseEncoder::subword_text_device(const void *d_text, unsigned long long n
   Status s = subword_text_on_lane(*this, *dev_, dev_->lane[0], device_, d_text, n_bytes, bos, eos, reverse, dropout_prob, n_lines, n_ids, n_text_bytes,
                                   kernel_ms ? &ms_split : nullptr, kernel_ms ? &ms_enc : nullptr, kernel_ms ? &ms_fmt : nullptr);
   if (kernel_ms) *kernel_ms = ms_split + ms_enc + ms_fmt;
+  return s;
+}
+
+// ---- decimal id text (k_idtext.h) ----------------------------------------------------------------------------------------------------------
+// The ids `while (ss >> x) ids.push_back(x)` reads from every line of the split pending on the lane (bpe.cpp:1863-1873), left in the lane's
+// encode-result buffers exactly as encode_on_lane leaves its ids, n_sent = the lines: measure -> scan -> write.
+static Status parse_on_lane(EncodeLane &d, int device, const void *d_text, unsigned long long n_bytes, unsigned long long *n_ids_out, double *kernel_ms) {
+  return on_device(device, [&]() -> Status {
+    const unsigned long long n_lines = d.ln.n_lines;
+    d.res.n_sent = n_lines;
+    d.res.n_ids = 0;
+    if (n_ids_out) *n_ids_out = 0;
+    if (kernel_ms) *kernel_ms = 0;
+    if (n_lines == 0) return Status();
+    d.k5.counts.grow((size_t)n_lines);
+    d.res.off.grow((size_t)n_lines + 1);
+    EventPair ev(d.st, kernel_ms != nullptr);
+    ev.start();
+    launch_idparse_measure((const uint8_t *)d_text, d.ln.off, n_lines, n_bytes, d.k5.counts, d.st);
+    const unsigned long long total = scan_counts(d, d.k5.counts, n_lines, d.res.off);  // (syncs)
+    d.res.ids.grow((size_t)total + 1);
+    launch_idparse_write((const uint8_t *)d_text, d.ln.off, n_lines, n_bytes, d.res.off, d.res.ids, d.st);
+    ev.stop();
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    if (kernel_ms) *kernel_ms = ev.elapsed_ms();
+    d.res.n_ids = total;
+    if (n_ids_out) *n_ids_out = total;
+    return Status();
+  });
+}
+
+// split, then the parse of those lines
+static Status parse_text_on_lane(EncodeLane &d, int device, const void *d_text, unsigned long long n_bytes, unsigned long long *n_lines,
+                                 unsigned long long *n_ids, double *split_ms, double *parse_ms) {
+  unsigned long long nl = 0;
+  const Status s = on_device(device, [&]() -> Status {
+    split_on_lane(d, d_text, n_bytes, &nl, nullptr, split_ms);
+    return Status();
+  });
+  if (!s.ok()) return s;
+  if (n_lines) *n_lines = nl;
+  return parse_on_lane(d, device, d_text, n_bytes, n_ids, parse_ms);
+}
+
+// split, parse, then the device decode of those ids with a newline behind every line: what decode_cli writes for the text (bpe.cpp:2016-2028)
+static Status decode_text_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_text, unsigned long long n_bytes,
+                                  const int32_t *ignore_ids, unsigned long long n_ignore, unsigned long long *n_lines, unsigned long long *n_ids,
+                                  unsigned long long *n_text_bytes, double *split_ms, double *parse_ms, double *decode_ms) {
+  unsigned long long nl = 0, ni = 0;
+  const Status s = parse_text_on_lane(d, device, d_text, n_bytes, &nl, &ni, split_ms, parse_ms);
+  if (!s.ok()) return s;
+  if (n_lines) *n_lines = nl;
+  if (n_ids) *n_ids = ni;
+  const DecInput in{d.res.ids, d.res.off, nullptr, 0, 0, nl};
+  return decode_on_lane(enc, D, d, device, in, ni, ignore_ids, n_ignore, n_text_bytes, decode_ms, true);
+}
+
+Status BaseEncoder::ids_parse_device(const void *d_text, unsigned long long n_bytes, unsigned long long *n_lines, unsigned long long *n_ids,
+                                     double *kernel_ms) const {
+  if (n_lines) *n_lines = 0;
+  if (n_ids) *n_ids = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (n_bytes && !d_text) return Status(2, "ids_parse_device: no text");
+  const CfgBind bind(dev_->cfg);
+  std::lock_guard<std::mutex> lk(dev_->lane[0].mu);
+  double ms_split = 0, ms_parse = 0;
+  const Status s = parse_text_on_lane(dev_->lane[0], device_, d_text, n_bytes, n_lines, n_ids, kernel_ms ? &ms_split : nullptr, kernel_ms ? &ms_parse : nullptr);
+  if (kernel_ms) *kernel_ms = ms_split + ms_parse;
+  return s;
+}
+
+Status BaseEncoder::decode_text_device(const void *d_text, unsigned long long n_bytes, const int32_t *ignore_ids, unsigned long long n_ignore,
+                                       unsigned long long *n_lines, unsigned long long *n_ids, unsigned long long *n_text_bytes, double *kernel_ms) const {
+  if (n_lines) *n_lines = 0;
+  if (n_ids) *n_ids = 0;
+  if (n_text_bytes) *n_text_bytes = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (n_bytes && !d_text) return Status(2, "decode_text_device: no text");
+  if (n_ignore && !ignore_ids) return Status(2, "decode_text_device: no ignore_ids");
+  const CfgBind bind(dev_->cfg);
+  std::lock_guard<std::mutex> lk(dev_->lane[0].mu);
+  double ms_split = 0, ms_parse = 0, ms_dec = 0;
+  const Status s = decode_text_on_lane(*this, *dev_, dev_->lane[0], device_, d_text, n_bytes, ignore_ids, n_ignore, n_lines, n_ids, n_text_bytes,
+                                       kernel_ms ? &ms_split : nullptr, kernel_ms ? &ms_parse : nullptr, kernel_ms ? &ms_dec : nullptr);
+  if (kernel_ms) *kernel_ms = ms_split + ms_parse + ms_dec;
   return s;
 }
 
@@ -391,17 +478,26 @@ Status BaseEncoder::encode_file(const std::string &path, const char *out_prefix,
   return Status();
 }
 
-// The same pipeline with the SUBWORD formatter behind the encode and the text as the only thing that comes down: piece k's text is written to
-// out_path behind the text of the pieces before it.
-Status BaseEncoder::encode_file_subword(const std::string &path, const std::string &out_path, bool bos, bool eos, bool reverse, double dropout_prob,
-                                        unsigned long long piece_bytes, unsigned long long *n_lines_out, unsigned long long *n_ids_out,
-                                        unsigned long long *n_text_out, std::string *report) const {
-  if (n_lines_out) *n_lines_out = 0;
-  if (n_ids_out) *n_ids_out = 0;
-  if (n_text_out) *n_text_out = 0;
-  const Status tokens = check_bos_eos(*this, bos, eos);
-  if (!tokens.ok()) return tokens;
-  if (!dev_) return Status(2, "encoder has no device state");
+// ---- a text file to a text file ---------------------------------------------------------------------------------------------------------
+// The same pipeline with text as the only thing that comes down: piece k's text, left in the lane's text slot by `work`, is written to out_path
+// behind the text of the pieces before it.  Three routes share it: the SUBWORD formatter and the id printer behind the encode, and the decode
+// of a file of decimal ids.
+namespace {
+struct PieceWork {  // what `work` reports for one piece: counts, and kernel times in milliseconds (split; two more, named by the route)
+  unsigned long long n_lines = 0, n_ids = 0, n_text = 0;
+  double ms_split = 0, ms_a = 0, ms_b = 0;
+};
+struct TextRoute {
+  const char *who;           // for run_two_lanes' messages
+  const char *key_a, *key_b;  // report keys of ms_a, ms_b ("seconds_...")
+  bool has_encode;            // the wall time of `work` beyond the three kernel times is the encode's ("seconds_encode"; else it is 0)
+};
+using PieceFn = std::function<Status(EncodeLane &d, unsigned long long bytes, PieceWork *w)>;
+
+Status file_to_text(EncoderDevice *dev, int device, const TextRoute &route, const std::string &path, const std::string &out_path, unsigned long long piece_bytes,
+                    const PieceFn &work_piece, unsigned long long *n_lines_out, unsigned long long *n_ids_out, unsigned long long *n_text_out,
+                    std::string *report) {
+  if (!dev) return Status(2, "encoder has no device state");
   if (out_path.empty()) return Status(1, "Failed to open file for writing: no output path");
   if (!piece_bytes) piece_bytes = FILE_PIECE_DEFAULT;
   const auto t_begin = std::chrono::steady_clock::now();
@@ -412,22 +508,21 @@ Status BaseEncoder::encode_file_subword(const std::string &path, const std::stri
   if (in.fd < 0 || fstat(in.fd, &sb) != 0) return Status(1, "Failed to open file: " + path + " (" + strerror(errno) + ")");
   if (!S_ISREG(sb.st_mode)) return Status(1, "Failed to read file: " + path + " is not a regular file");
   const unsigned long long size = (unsigned long long)sb.st_size;
-  // (opened without O_TRUNC, emptied only once it is known not to be the input itself: the text is longer than the input it would overwrite)
+  // (opened without O_TRUNC, emptied only once it is known not to be the input itself: the output may be longer than the input it would overwrite)
   out.fd = open(out_path.c_str(), O_WRONLY | O_CREAT | O_CLOEXEC, 0644);
   struct stat ob;
   if (out.fd < 0 || fstat(out.fd, &ob) != 0) return Status(1, "Failed to open file for writing: " + out_path + " (" + strerror(errno) + ")");
   if (ob.st_dev == sb.st_dev && ob.st_ino == sb.st_ino) return Status(1, "Failed to open file for writing: " + out_path + " is the input file");
   if (S_ISREG(ob.st_mode) && ftruncate(out.fd, 0) != 0) return Status(1, "Failed to open file for writing: " + out_path + " (" + strerror(errno) + ")");
-  const std::shared_ptr<const Config> C = dev_->cfg;
+  const std::shared_ptr<const Config> C = dev->cfg;
   const CfgBind bind(C);
-  const int device = device_;
-  EncoderDevice *dev = dev_;
   std::lock_guard<std::mutex> lk0(dev->lane[0].mu), lk1(dev->lane[1].mu);  // (lane 0 first, always: nobody else waits for two lanes)
 
   struct Piece {
-    unsigned long long pos = 0, bytes = 0, n_lines = 0, n_ids = 0, n_text = 0;
+    unsigned long long pos = 0, bytes = 0;
+    PieceWork w;
   } piece[2];  // of the item in flight on each lane: upload(i) fills it, work(i) adds the counts, download(i) reads it
-  double s_up = 0, s_split = 0, s_enc = 0, s_fmt = 0, s_down = 0;
+  double s_up = 0, s_split = 0, s_enc = 0, s_a = 0, s_b = 0, s_down = 0;
   unsigned long long next_pos = 0, lines_total = 0, ids_total = 0, text_total = 0;  // (the upload leg's; the download leg's three)
 
   auto upload = [&](size_t i, bool *exhausted) {
@@ -438,20 +533,18 @@ Status BaseEncoder::encode_file_subword(const std::string &path, const std::stri
     const Status st = upload_piece(in.fd, path, device, dev->lane[i & 1], pos, piece_bytes, size, &end);
     if (!st.ok()) return st;
     s_up += secs(t0);
-    piece[i & 1] = Piece{pos, end - pos, 0, 0, 0};
+    piece[i & 1] = Piece{pos, end - pos, PieceWork{}};
     next_pos = end;
     return Status();
   };
   auto work = [&](size_t i) {
     Piece &p = piece[i & 1];
-    EncodeLane &d = dev->lane[i & 1];
-    double ms_split = 0, ms_fmt = 0;
     const auto t0 = std::chrono::steady_clock::now();
-    const Status st = subword_text_on_lane(*this, *dev, d, device, d.in.bytes, p.bytes, bos, eos, reverse, dropout_prob, &p.n_lines, &p.n_ids, &p.n_text,
-                                           &ms_split, nullptr, &ms_fmt);
-    s_split += ms_split * 1e-3;
-    s_fmt += ms_fmt * 1e-3;
-    s_enc += secs(t0) - (ms_split + ms_fmt) * 1e-3;
+    const Status st = work_piece(dev->lane[i & 1], p.bytes, &p.w);
+    s_split += p.w.ms_split * 1e-3;
+    s_a += p.w.ms_a * 1e-3;
+    s_b += p.w.ms_b * 1e-3;
+    if (route.has_encode) s_enc += secs(t0) - (p.w.ms_split + p.w.ms_a + p.w.ms_b) * 1e-3;
     return st;
   };
   auto download = [&](size_t i) {
@@ -461,8 +554,8 @@ Status BaseEncoder::encode_file_subword(const std::string &path, const std::stri
     const unsigned long long text_base = text_total;
     std::atomic<bool> write_ok{true};
     try {
-      if (p.n_text)
-        staged_transfer(device, d.dec.bytes.p, p.n_text, false, [&](void *chunk, unsigned long long o, size_t len) {
+      if (p.w.n_text)
+        staged_transfer(device, d.dec.bytes.p, p.w.n_text, false, [&](void *chunk, unsigned long long o, size_t len) {
           if (!pwrite_all(out.fd, chunk, len, text_base + o)) { write_ok.store(false); return false; }
           return true;
         }, nullptr, ENC_CHUNK);
@@ -470,14 +563,14 @@ Status BaseEncoder::encode_file_subword(const std::string &path, const std::stri
       if (!write_ok.load()) return Status(1, "Failed to write file: " + out_path);
       throw;
     }
-    text_total += p.n_text;
-    ids_total += p.n_ids;
-    lines_total += p.n_lines;
+    text_total += p.w.n_text;
+    ids_total += p.w.n_ids;
+    lines_total += p.w.n_lines;
     s_down += secs(t0);
     return Status();
   };
   size_t n_pieces = 0;
-  const Status piped = run_two_lanes("encode_file_subword", C, device, PIPE_UNTIL_EXHAUSTED, upload, work, download, &n_pieces);
+  const Status piped = run_two_lanes(route.who, C, device, PIPE_UNTIL_EXHAUSTED, upload, work, download, &n_pieces);
   if (!piped.ok()) return piped;
   const int fd = out.fd;
   out.fd = -1;
@@ -486,14 +579,79 @@ Status BaseEncoder::encode_file_subword(const std::string &path, const std::stri
   if (n_ids_out) *n_ids_out = ids_total;
   if (n_text_out) *n_text_out = text_total;
   if (report) {
-    char tmp[640];
+    char tmp[768];
     snprintf(tmp, sizeof tmp,
              "{\"pieces\": %zu, \"piece_bytes\": %llu, \"bytes\": %llu, \"lines\": %llu, \"ids\": %llu, \"text_bytes\": %llu, \"seconds_total\": %.6f, "
-             "\"seconds_read_upload\": %.6f, \"seconds_split\": %.6f, \"seconds_encode\": %.6f, \"seconds_format\": %.6f, \"seconds_download_write\": %.6f}",
-             n_pieces, piece_bytes, size, lines_total, ids_total, text_total, secs(t_begin), s_up, s_split, s_enc, s_fmt, s_down);
+             "\"seconds_read_upload\": %.6f, \"seconds_split\": %.6f, \"seconds_encode\": %.6f, \"%s\": %.6f",
+             n_pieces, piece_bytes, size, lines_total, ids_total, text_total, secs(t_begin), s_up, s_split, s_enc, route.key_a, s_a);
     *report = tmp;
+    if (route.key_b) {
+      snprintf(tmp, sizeof tmp, ", \"%s\": %.6f", route.key_b, s_b);
+      *report += tmp;
+    }
+    snprintf(tmp, sizeof tmp, ", \"seconds_download_write\": %.6f}", s_down);
+    *report += tmp;
   }
   return Status();
+}
+}  // namespace
+
+Status BaseEncoder::encode_file_subword(const std::string &path, const std::string &out_path, bool bos, bool eos, bool reverse, double dropout_prob,
+                                        unsigned long long piece_bytes, unsigned long long *n_lines_out, unsigned long long *n_ids_out,
+                                        unsigned long long *n_text_out, std::string *report) const {
+  if (n_lines_out) *n_lines_out = 0;
+  if (n_ids_out) *n_ids_out = 0;
+  if (n_text_out) *n_text_out = 0;
+  const Status tokens = check_bos_eos(*this, bos, eos);
+  if (!tokens.ok()) return tokens;
+  const int device = device_;
+  EncoderDevice *dev = dev_;
+  const PieceFn work = [&](EncodeLane &d, unsigned long long bytes, PieceWork *w) {
+    return subword_text_on_lane(*this, *dev, d, device, d.in.bytes, bytes, bos, eos, reverse, dropout_prob, &w->n_lines, &w->n_ids, &w->n_text, &w->ms_split,
+                                nullptr, &w->ms_a);
+  };
+  return file_to_text(dev, device, TextRoute{"encode_file_subword", "seconds_format", nullptr, true}, path, out_path, piece_bytes, work, n_lines_out, n_ids_out,
+                      n_text_out, report);
+}
+
+// ... with the id printer in place of the SUBWORD formatter: the file `yttm encode --output_type id < path` prints
+Status BaseEncoder::encode_file_idtext(const std::string &path, const std::string &out_path, bool bos, bool eos, bool reverse, double dropout_prob,
+                                       unsigned long long piece_bytes, unsigned long long *n_lines_out, unsigned long long *n_ids_out,
+                                       unsigned long long *n_text_out, std::string *report) const {
+  if (n_lines_out) *n_lines_out = 0;
+  if (n_ids_out) *n_ids_out = 0;
+  if (n_text_out) *n_text_out = 0;
+  const Status tokens = check_bos_eos(*this, bos, eos);
+  if (!tokens.ok()) return tokens;
+  const int device = device_;
+  EncoderDevice *dev = dev_;
+  const PieceFn work = [&](EncodeLane &d, unsigned long long bytes, PieceWork *w) {
+    const Status s = encode_text_on_lane(*this, *dev, d, device, d.in.bytes, bytes, bos, eos, reverse, dropout_prob, &w->n_lines, &w->n_ids, &w->ms_split, nullptr);
+    if (!s.ok()) return s;
+    return idtext_on_lane(d, device, &w->n_text, &w->ms_a);
+  };
+  return file_to_text(dev, device, TextRoute{"encode_file_idtext", "seconds_format", nullptr, true}, path, out_path, piece_bytes, work, n_lines_out, n_ids_out,
+                      n_text_out, report);
+}
+
+// A file of decimal ids, one sentence per line -> the file `yttm decode < path` prints: split + parse + decode in place of split + encode + format.
+// An id that is neither ignored nor valid ends the call at its piece -- the pieces are worked on in file order, so it is the first such id of the
+// file --, with the text of the pieces before it written.
+Status BaseEncoder::decode_file(const std::string &path, const std::string &out_path, const int32_t *ignore_ids, unsigned long long n_ignore,
+                                unsigned long long piece_bytes, unsigned long long *n_lines_out, unsigned long long *n_ids_out, unsigned long long *n_text_out,
+                                std::string *report) const {
+  if (n_lines_out) *n_lines_out = 0;
+  if (n_ids_out) *n_ids_out = 0;
+  if (n_text_out) *n_text_out = 0;
+  if (n_ignore && !ignore_ids) return Status(2, "decode_file: no ignore_ids");
+  const int device = device_;
+  EncoderDevice *dev = dev_;
+  const PieceFn work = [&](EncodeLane &d, unsigned long long bytes, PieceWork *w) {
+    return decode_text_on_lane(*this, *dev, d, device, d.in.bytes, bytes, ignore_ids, n_ignore, &w->n_lines, &w->n_ids, &w->n_text, &w->ms_split, &w->ms_a,
+                               &w->ms_b);
+  };
+  return file_to_text(dev, device, TextRoute{"decode_file", "seconds_parse", "seconds_decode", false}, path, out_path, piece_bytes, work, n_lines_out, n_ids_out,
+                      n_text_out, report);
 }
 
 }  // namespace yttm

@@ -65,13 +65,17 @@ struct DecStage {
   }
 };
 
-template <bool PADDED, bool WRITE>
+// NL (ragged input only): a '\n' behind every sentence, as decode_cli writes its lines -- out_len[s] counts it, the write pass puts the newlines of
+// the sentences that END at a position (every boundary but the group's first one; empty sentences: several) in front of that position's piece,
+// and those of a boundary that no step reaches (the group ends exactly on a step's end) behind the last step.
+template <bool PADDED, bool WRITE, bool NL = false>
 __global__ __launch_bounds__(BLOCK) void k_decode(DecInput in, DecTable tb, DecIgnore ig, unsigned int group, uint32_t *__restrict__ out_len,
                                                   unsigned long long *__restrict__ bad_min, const unsigned long long *__restrict__ out_off,
                                                   uint8_t *__restrict__ out) {
   __shared__ __attribute__((aligned(16))) uint8_t s_tile[WRITE ? NWAVES : 1][WRITE ? DEC_TILE : 16];
   __shared__ uint32_t s_xs[NWAVES][65];
   __shared__ uint32_t s_flag[NWAVES][64];
+  __shared__ uint32_t s_nl[NL && WRITE ? NWAVES : 1][NL && WRITE ? 64 : 1];
   __shared__ unsigned long long s_bad[NWAVES];
   const int w = uni((int)(threadIdx.x >> 6));
   const uint32_t lane = (uint32_t)lane_id();
@@ -85,6 +89,7 @@ __global__ __launch_bounds__(BLOCK) void k_decode(DecInput in, DecTable tb, DecI
     unsigned long long rowb = g0, colb = 0;  // (PADDED) row and column of `base`
     uint32_t run = 0, open_p = 0;            // (measure) output bytes of the group before this step; ... before the start of the sentence still open
     bool carry = false;                      // the sentence that is open at `base` has a kept id already
+    uint32_t nl_left = NL ? (uint32_t)(g1 - g0) : 0u;  // (NL, write) newlines of the group not yet staged
     DecStage stg{};
     stg.tile = s_tile[WRITE ? w : 0];
     if (WRITE) {
@@ -134,6 +139,7 @@ __global__ __launch_bounds__(BLOCK) void k_decode(DecInput in, DecTable tb, DecI
       }
       // ---- sentence starts in [base, base + 64) as a lane mask
       s_flag[w][lane] = 0;
+      if (NL && WRITE) s_nl[w][lane] = 0;
       wave_sync();
       unsigned long long hits = 0;
       for (unsigned long long s2 = sc;; s2 += 64) {
@@ -142,6 +148,7 @@ __global__ __launch_bounds__(BLOCK) void k_decode(DecInput in, DecTable tb, DecI
         const unsigned long long v = have ? dec_bpos(in, s) : ~0ull;
         const bool hit = have && v < base + 64;
         if (hit && s < g1) s_flag[w][(uint32_t)(v - base)] = 1;
+        if (NL && WRITE && hit && s > g0) atomicAdd(&s_nl[w][(uint32_t)(v - base)], 1u);
         const uint32_t cnt = (uint32_t)__popcll(ballot_b(hit));
         hits += cnt;
         if (cnt < 64) break;
@@ -160,8 +167,9 @@ __global__ __launch_bounds__(BLOCK) void k_decode(DecInput in, DecTable tb, DecI
         src++;
         len--;
       }
-      const uint32_t inc = wave_incl_scan(len);
-      const uint32_t x = inc - len, total = uni(__shfl(inc, 63));
+      const uint32_t nlb = NL && WRITE ? s_nl[w][lane] : 0u;  // newlines in front of this lane's piece
+      const uint32_t inc = wave_incl_scan(len + nlb);
+      const uint32_t x = inc - len, total = uni(__shfl(inc, 63));  // (x: where the piece goes, behind its newlines)
       if (!WRITE) {
         // ---- every boundary in [base, base + 64) (the last step: every one left) closes a sentence: its length is a difference of prefixes
         s_xs[w][lane] = x;
@@ -176,8 +184,8 @@ __global__ __launch_bounds__(BLOCK) void k_decode(DecInput in, DecTable tb, DecI
           if (cnt == 0) break;
           const uint32_t pfx = res ? run + s_xs[w][(uint32_t)(v - base)] : 0u;
           const uint32_t next = __shfl_down(pfx, 1);
-          if (res && lane + 1 < cnt) out_len[s] = next - pfx;
-          if (lane == 0 && sc > g0) out_len[sc - 1] = pfx - open_p;
+          if (res && lane + 1 < cnt) out_len[s] = next - pfx + (NL ? 1u : 0u);
+          if (lane == 0 && sc > g0) out_len[sc - 1] = pfx - open_p + (NL ? 1u : 0u);
           open_p = uni(__shfl(pfx, (int)cnt - 1));
           sc += cnt;
           if (cnt < 64) break;
@@ -187,16 +195,24 @@ __global__ __launch_bounds__(BLOCK) void k_decode(DecInput in, DecTable tb, DecI
       } else {
         sc += hits;
         if (total <= (uint32_t)DEC_SEG) {
+          if (NL) for (uint32_t b = 0; b < nlb; b++) stg.tile[stg.fill + x - nlb + b] = (uint8_t)'\n';
           for (uint32_t b = 0; b < len; b++) stg.tile[stg.fill + x + b] = tb.blob[src + b];
           wave_sync();
           stg.fill += total;
           stg.flush_units();
         } else {  // pieces that do not fit the tile together (a word of thousands of chars can be one piece): one by one, the wave copies a piece
-          unsigned long long pm = ballot_b(len > 0);
+          unsigned long long pm = ballot_b(len + nlb > 0);
           while (pm) {
             const int l = __ffsll((long long)pm) - 1;
             pm &= pm - 1;
             const uint32_t plen = uni(__shfl(len, l)), psrc = uni(__shfl(src, l));
+            if (NL) {  // (at most 64 newlines a step, behind fewer than 16 staged bytes)
+              const uint32_t pnl = uni(__shfl(nlb, l));
+              if (lane < pnl) stg.tile[stg.fill + lane] = (uint8_t)'\n';
+              wave_sync();
+              stg.fill += pnl;
+              stg.flush_units();
+            }
             for (uint32_t done = 0; done < plen;) {
               const uint32_t n = plen - done < (uint32_t)DEC_SEG ? plen - done : (uint32_t)DEC_SEG;
               for (uint32_t b = lane; b < n; b += 64) stg.tile[stg.fill + b] = tb.blob[psrc + done + b];
@@ -208,6 +224,7 @@ __global__ __launch_bounds__(BLOCK) void k_decode(DecInput in, DecTable tb, DecI
           }
         }
       }
+      if (NL && WRITE) nl_left -= uni(__shfl(wave_incl_scan(nlb), 63));
       if (last) break;
       if (PADDED) {
         colb += 64;
@@ -221,6 +238,12 @@ __global__ __launch_bounds__(BLOCK) void k_decode(DecInput in, DecTable tb, DecI
           }
         }
       }
+    }
+    if (NL && WRITE && nl_left) {  // (fewer than 16 bytes are staged: every step ends with flush_units)
+      if (lane < nl_left) stg.tile[stg.fill + lane] = (uint8_t)'\n';
+      wave_sync();
+      stg.fill += nl_left;
+      stg.flush_units();
     }
     if (WRITE) stg.flush_tail();
   }
@@ -246,7 +269,7 @@ static unsigned int dec_group(const DecInput &in, unsigned long long n_flat) {
   if (grp < many) grp = many;
   return (unsigned int)(grp < 1 ? 1 : grp > 64 ? 64 : grp);
 }
-static void launch_decode_any(bool write, const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, uint32_t *out_len,
+static void launch_decode_any(bool write, bool newline, const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, uint32_t *out_len,
                               unsigned long long *bad_min, const unsigned long long *out_off, uint8_t *out, hipStream_t st) {
   if (!in.n_sent) return;
   const unsigned int group = dec_group(in, n_flat);
@@ -255,18 +278,23 @@ static void launch_decode_any(bool write, const DecInput &in, const DecTable &tb
   if (b > 256 * 8) b = 256 * 8;
   const dim3 grid((unsigned int)b), block(BLOCK);
   const bool padded = in.offsets == nullptr;
+  if (newline) {  // (ragged only: the callers' inputs are the parser's)
+    if (!write) hipLaunchKernelGGL((k_decode<false, false, true>), grid, block, 0, st, in, tb, ig, group, out_len, bad_min, out_off, out);
+    else hipLaunchKernelGGL((k_decode<false, true, true>), grid, block, 0, st, in, tb, ig, group, out_len, bad_min, out_off, out);
+    return;
+  }
   if (!write && !padded) hipLaunchKernelGGL((k_decode<false, false>), grid, block, 0, st, in, tb, ig, group, out_len, bad_min, out_off, out);
   if (!write && padded) hipLaunchKernelGGL((k_decode<true, false>), grid, block, 0, st, in, tb, ig, group, out_len, bad_min, out_off, out);
   if (write && !padded) hipLaunchKernelGGL((k_decode<false, true>), grid, block, 0, st, in, tb, ig, group, out_len, bad_min, out_off, out);
   if (write && padded) hipLaunchKernelGGL((k_decode<true, true>), grid, block, 0, st, in, tb, ig, group, out_len, bad_min, out_off, out);
 }
 void launch_decode_measure(const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, uint32_t *out_len,
-                           unsigned long long *bad_min, hipStream_t st) {
-  launch_decode_any(false, in, tb, ig, n_flat, out_len, bad_min, nullptr, nullptr, st);
+                           unsigned long long *bad_min, hipStream_t st, bool newline) {
+  launch_decode_any(false, newline, in, tb, ig, n_flat, out_len, bad_min, nullptr, nullptr, st);
 }
 void launch_decode_write(const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, const unsigned long long *out_off,
-                         uint8_t *out, hipStream_t st) {
-  launch_decode_any(true, in, tb, ig, n_flat, nullptr, nullptr, out_off, out, st);
+                         uint8_t *out, hipStream_t st, bool newline) {
+  launch_decode_any(true, newline, in, tb, ig, n_flat, nullptr, nullptr, out_off, out, st);
 }
 
 // ---- the encoder's result as a padded matrix -----------------------------------------------------------------------------------------

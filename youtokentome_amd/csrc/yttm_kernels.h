@@ -396,11 +396,12 @@ struct DecInput {  // sentence s = ids[offsets[s] .. offsets[s+1]), or (offsets 
   unsigned long long n_sent;
 };
 // n_flat: ids (ragged) or n_sent * stride (padded) -- sizes the groups of sentences.  *bad_min must hold ~0 before the launch.
+// newline (ragged input only, the same in both launches): a '\n' behind every sentence, counted in out_len.
 void launch_decode_measure(const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, uint32_t *out_len,
-                           unsigned long long *bad_min, hipStream_t st);
+                           unsigned long long *bad_min, hipStream_t st, bool newline = false);
 // out: 16-byte aligned
 void launch_decode_write(const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, const unsigned long long *out_off,
-                         uint8_t *out, hipStream_t st);
+                         uint8_t *out, hipStream_t st, bool newline = false);
 void launch_enc_longest(const unsigned long long *out_off, unsigned long long n_sent, unsigned int *longest /* holds 0 before the launch */, hipStream_t st);
 void launch_enc_pad(const int32_t *ids, const unsigned long long *out_off, unsigned long long n_sent, unsigned long long width, int32_t pad_value,
                     int32_t *matrix /* 4-byte aligned */, int32_t *lengths, hipStream_t st);
@@ -429,5 +430,19 @@ void launch_lines_count(const uint8_t *d_text, unsigned long long n_bytes, uint3
 void launch_lines_write(const uint8_t *d_text, unsigned long long n_bytes, const unsigned long long *rank, unsigned long long *off, unsigned long long n_lines,
                         hipStream_t st);
 void launch_lines_longest(const unsigned long long *off, unsigned long long n_lines, unsigned long long *longest /* holds 0 before the launch */, hipStream_t st);
+
+// ---- decimal id text (k_idtext.h, compiled with k_encode.hip): measure -> launch_exclusive_scan -> write, both ways ----
+// the parser: line i = text[loff[i] .. loff[i + 1]) with its newline (the offsets launch_lines_write left; text: any address) -> count[n_lines],
+// then the ids `while (ss >> x)` reads from each line at ids[out_off[i] ..), out_off the exclusive scan of count.  n_bytes sizes the groups of lines.
+void launch_idparse_measure(const uint8_t *text, const unsigned long long *loff, unsigned long long n_lines, unsigned long long n_bytes, uint32_t *count,
+                            hipStream_t st);
+void launch_idparse_write(const uint8_t *text, const unsigned long long *loff, unsigned long long n_lines, unsigned long long n_bytes,
+                          const unsigned long long *out_off, int32_t *ids, hipStream_t st);
+// the printer: sentence s = ids[ioff[s] .. ioff[s + 1]) -> every id in decimal + one space, then '\n'.  out: 16-byte aligned; out_off: the
+// exclusive scan of out_len, [n_sent + 1].  n_ids sizes the groups of sentences.
+void launch_idprint_measure(const int32_t *ids, const unsigned long long *ioff, unsigned long long n_sent, unsigned long long n_ids, uint32_t *out_len,
+                            hipStream_t st);
+void launch_idprint_write(const int32_t *ids, const unsigned long long *ioff, unsigned long long n_sent, unsigned long long n_ids,
+                          const unsigned long long *out_off, uint8_t *out, hipStream_t st);
 
 }  // namespace yttm

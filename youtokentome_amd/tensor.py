@@ -1,5 +1,5 @@
 """Device tensors in, device tensors out: `BPE.encode_tensor` / `BPE.encode_text_tensor` / `BPE.text_lines_tensor` / `BPE.decode_tensor` /
-`BPE.encode_subword_tensor` / `BPE.encode_text_subword_tensor` on top
+`BPE.encode_subword_tensor` / `BPE.encode_text_subword_tensor` / `BPE.decode_text_tensor` / `BPE.parse_ids_tensor` on top
 of the raw device layer of `bpe._Core` (include/yttm_mi355x.h: yttm_encode_device, yttm_encode_text_device, yttm_lines_*, yttm_encode_copy_*,
 yttm_decode_device*, yttm_decode_copy_device).  torch is imported at call
 time; the rest of the package does not need it.
@@ -232,3 +232,29 @@ def encode_text_subword_tensor(bpe, text, bos=False, eos=False, reverse=False, d
     torch.cuda.current_stream(dev).synchronize()  # the text is complete before the library's own stream reads it
     n, _, n_text, _ = core.subword_text_device_raw(d_text.data_ptr(), n_bytes, bos, eos, reverse, dropout_prob)
     return _take_text(torch, core, dev, n, n_text, as_str)
+
+
+def parse_ids_tensor(bpe, text, padded=False, width=None, pad_id=None):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    if padded and pad_id is None:
+        pad_id = bpe.subword_to_id("<PAD>")
+        if pad_id == -1 or bpe.id_to_subword(pad_id) != "<PAD>":
+            raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
+    d_text, n_bytes = _text_on(torch, text, dev)
+    torch.cuda.current_stream(dev).synchronize()  # the text is complete before the library's own stream reads it
+    n, n_ids, _ = core.ids_parse_device_raw(d_text.data_ptr(), n_bytes)
+    return _take_encoded(torch, core, dev, n, n_ids, padded, width, pad_id)
+
+
+def decode_text_tensor(bpe, text, ignore_ids=None, as_str=True):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    d_text, n_bytes = _text_on(torch, text, dev)
+    torch.cuda.current_stream(dev).synchronize()  # the text is complete before the library's own stream reads it
+    n, _, n_text, _ = core.decode_text_device_raw(d_text.data_ptr(), n_bytes, ignore_ids)
+    if as_str:
+        return [s[:-1] for s in _take_text(torch, core, dev, n, n_text, True)]
+    return _take_text(torch, core, dev, n, n_text, False)

@@ -2,6 +2,10 @@
 (youtokentome/yttm_cli.py:10-169: bpe | encode | decode | vocab), same stdout formats as the reference's native CLI
 loops (bpe.cpp:1942-2028, utils.h:92-103).  Run as `python -m youtokentome_amd.yttm_cli ...`.
 
+Two more commands work file to file through the device, with the same bytes as the streaming ones: `encode_file` (--output_type id: binary
+PREFIX.ids / PREFIX.off; subword and id_text: the text `encode --output_type subword` / `id` prints) and `decode_file` (a file of decimal ids
+-> the text `decode` prints).
+
 The loops themselves are C++ (youtokentome_amd/csrc/host_cli.cpp, behind yttm_encode_cli / yttm_decode_cli / yttm_vocab_cli):
 stdin and stdout stay bytes end to end, invalid UTF-8 included."""
 
@@ -53,9 +57,9 @@ def encode(model, output_type, n_threads, bos, eos, reverse, stream, dropout_pro
 @click.option("--model", type=click.Path(exists=True), required=True, help="Path to file with learned model.")
 @click.option("--input", "input_path", type=click.Path(exists=True, dir_okay=False), required=True, help="Text file, one sentence per line.")
 @click.option("--output", type=click.Path(), required=True,
-              help="Prefix of the output: PREFIX.ids (int32) and PREFIX.off (uint64), little-endian; with --output_type subword the text file to write.")
-@click.option("--output_type", type=click.Choice(["id", "subword"]), default="id", show_default=True,
-              help="'id': binary ids and offsets; 'subword': the text `encode --output_type subword` prints.")
+              help="Prefix of the output: PREFIX.ids (int32) and PREFIX.off (uint64), little-endian; with --output_type subword or id_text the text file to write.")
+@click.option("--output_type", type=click.Choice(["id", "subword", "id_text"]), default="id", show_default=True,
+              help="'id': binary ids and offsets; 'subword': the text `encode --output_type subword` prints; 'id_text': the text `encode --output_type id` prints.")
 @click.option("--bos", is_flag=True, help="Add tab begin of sentence.")
 @click.option("--eos", is_flag=True, help="Add tab end of sentence.")
 @click.option("--reverse", is_flag=True, help="Reverse output sequence of tokens.")
@@ -66,6 +70,9 @@ def encode_file(model, input_path, output, output_type, bos, eos, reverse, dropo
     core = _Core(model)
     if output_type == "subword":  # the same pipeline with the formatter behind the encode: yttm_encode_file_subword (host_lines.cpp)
         core.encode_file_subword(input_path, output, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob)
+        return
+    if output_type == "id_text":  # ... with the id printer behind the encode: yttm_encode_file_idtext (host_lines.cpp)
+        core.encode_file_idtext(input_path, output, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob)
         return
     core.encode_file(input_path, out=output, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob)  # the C++ pipeline: yttm_encode_file (host_lines.cpp)
 
@@ -87,6 +94,18 @@ def decode(model, ignore_ids):
     """Decode ids to text."""
     core = _Core(model)
     core.decode_cli(ignore_ids)
+
+
+@main.command(name="decode_file")
+@click.option("--model", type=click.Path(exists=True), required=True, help="Path to file with learned model.")
+@click.option("--input", "input_path", type=click.Path(exists=True, dir_okay=False), required=True, help="Text file of decimal ids, one sentence per line.")
+@click.option("--output", type=click.Path(), required=True, help="The text file to write: what `decode` prints for the input.")
+@click.option("--ignore_ids", type=click.STRING, callback=_parse_ignore_ids, required=False,
+              help="List of indices to ignore for decoding. Example: --ignore_ids=1,2,3")
+def decode_file(model, input_path, output, ignore_ids):
+    """Decode a text file of ids to a text file."""
+    core = _Core(model)
+    core.decode_file(input_path, output, ignore_ids=ignore_ids)  # the C++ pipeline: yttm_decode_file (host_lines.cpp)
 
 
 @main.command()
