@@ -178,6 +178,36 @@ int yttm_encode_file_idtext(yttm_encoder *enc, const char *path, const char *out
                             uint64_t chunk_bytes, uint64_t *n_lines, uint64_t *n_ids, uint64_t *n_text_bytes, char *report_json, int report_len,
                             char *err, int errlen);
 
+/* Byte spans on the device: for every id the bytes of its sentence it stands for, uint32 spans[n_ids][2] = (start, end), end exclusive, in bytes
+ * from the sentence's first byte, in the order of the ids.  Read as the encoder reads it (invalid bytes dropped, white space = isspace() in the C
+ * locale or U+2581), a sentence is a sequence of units: a valid non-space char of the alphabet, or a maximal run of valid chars outside the
+ * alphabet that no space and no alphabet char interrupts (invalid bytes do not end it); a unit starts at the first byte of its first char and ends
+ * behind the last byte of its last valid char.  An id covers u units: 1 for unk_id, else the code points of id_to_subword(id) other than U+2581
+ * (0 for "\u2581" alone, <PAD>, <BOS>, <EOS>).  In forward order, with a the units of the ids before it, an id with u > 0 has the span
+ * [start(unit a), end(unit a + u - 1)) -- beside its chars only invalid bytes lie inside --, one with u == 0 the empty span (p, p), p =
+ * start(unit a), or the end of the sentence's last unit where there is none (0 in a sentence without units).  With reverse the ids are stored back
+ * to front, and span k belongs to stored id k.  A sentence is below 4 GB.
+ * yttm_spans_device encodes exactly as yttm_encode_device, then computes the spans in one pass: afterwards the ids are pending as after
+ * yttm_encode_device and the spans in a slot of their own, which any later encode on the encoder empties.  kernel_ms (optional) = encode + spans.
+ * bos / eos on a model trained without them: the message and code (1) of yttm_encode_as_ids, and nothing that was pending is replaced. */
+int yttm_spans_device(yttm_encoder *enc, const void *d_bytes, const void *d_offsets, uint64_t n_sent, uint64_t total_bytes,
+                      uint64_t max_sentence_bytes, int bos, int eos, int reverse, double dropout_prob, uint64_t *n_ids, double *kernel_ms, char *err,
+                      int errlen);
+/* yttm_encode_text_device, then the spans: a sentence is a line including its newline, the spans count from the line's first byte.  Lines, ids and
+ * the lines' offsets are pending as after yttm_encode_text_device.  kernel_ms (optional) = split + encode + spans. */
+int yttm_spans_text_device(yttm_encoder *enc, const void *d_text, uint64_t n_bytes, int bos, int eos, int reverse, double dropout_prob,
+                           uint64_t *n_lines, uint64_t *n_ids, double *kernel_ms, char *err, int errlen);
+/* The pending spans (n_sent must be theirs): to a host array, to device memory the caller owns (ragged, uint32 [n_ids][2]), or as a padded
+ * matrix uint32 [n_sent, width, 2] whose row tails are (0, 0) (8-byte aligned; width < the longest row: the message and code (1) of
+ * yttm_encode_copy_padded, *longest says what is needed, nothing is written).  No pending spans -- none were made, or an encode came after them:
+ * code 1. */
+int yttm_spans_fetch(yttm_encoder *enc, uint32_t *spans, uint64_t n_sent, char *err, int errlen);
+int yttm_spans_copy_device(yttm_encoder *enc, void *d_spans, uint64_t n_sent, char *err, int errlen);
+int yttm_spans_copy_padded(yttm_encoder *enc, void *d_matrix, uint64_t n_sent, uint64_t width, uint64_t *longest, char *err, int errlen);
+/* Host to host: yttm_encode_as_ids and the spans of those ids, uint32 (*spans)[n_ids][2]; all three arrays are released with yttm_free. */
+int yttm_encode_as_ids_spans(yttm_encoder *enc, const uint8_t *bytes, const uint64_t *offsets, uint64_t n_sent, int bos, int eos, int reverse,
+                             double dropout_prob, int32_t **ids, uint64_t **out_offsets, uint32_t **spans, char *err, int errlen);
+
 /* Word-level encode cache (SURVEY.md 8f "N4"; the reference has no counterpart: bpe.cpp:1497-1632 encodes every word occurrence).
  * mode 0: every batch goes straight through the encode kernel; 1: distinct words are encoded once whenever that is possible
  * (dropout_prob == 0); 2 (default): the same for batches of at least min_bytes.  The ids are identical either way.

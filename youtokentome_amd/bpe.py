@@ -263,6 +263,53 @@ class _Core:
             return json.loads(rep.value.decode())
         return nl.value, ni.value, nt.value
 
+    # ---- byte spans on the device (include/yttm_mi355x.h): the spans stay in the encoder, beside the ids they belong to, until an encode replaces those
+    def spans_device_raw(self, d_bytes, d_offsets, n_sent, total_bytes, max_sentence_bytes, bos=False, eos=False, reverse=False, dropout_prob=0.0):
+        """-> (n_ids, kernel_ms); the ids are pending as after encode_device_raw, the spans until copy_spans_* / fetch_spans takes them"""
+        ni, ms, err = C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_spans_device(self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n_sent, total_bytes, max_sentence_bytes, int(bos),
+                                                  int(eos), int(reverse), float(dropout_prob), C.byref(ni), C.byref(ms), err, _lib.ERRLEN), err)
+        return ni.value, ms.value
+
+    def spans_text_device_raw(self, d_text, n_bytes, bos=False, eos=False, reverse=False, dropout_prob=0.0):
+        """-> (n_lines, n_ids, kernel_ms)"""
+        nl, ni, ms, err = C.c_uint64(), C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_spans_text_device(self._h, C.c_void_p(d_text), n_bytes, int(bos), int(eos), int(reverse), float(dropout_prob),
+                                                       C.byref(nl), C.byref(ni), C.byref(ms), err, _lib.ERRLEN), err)
+        return nl.value, ni.value, ms.value
+
+    def fetch_spans(self, n_sent, n_ids):
+        """the pending spans -> np.uint32 [n_ids, 2]"""
+        spans, err = np.zeros((int(n_ids), 2), np.uint32), _err()
+        self._check(_lib.load().yttm_spans_fetch(self._h, spans.ctypes.data_as(_lib.u32p), n_sent, err, _lib.ERRLEN), err)
+        return spans
+
+    def copy_spans_device(self, d_spans, n_sent):
+        err = _err()
+        self._check(_lib.load().yttm_spans_copy_device(self._h, C.c_void_p(d_spans), n_sent, err, _lib.ERRLEN), err)
+
+    def copy_spans_padded(self, d_matrix, n_sent, width):
+        """-> longest row; ValueError when width is smaller"""
+        longest, err = C.c_uint64(), _err()
+        self._check(_lib.load().yttm_spans_copy_padded(self._h, C.c_void_p(d_matrix), n_sent, width, C.byref(longest), err, _lib.ERRLEN), err)
+        return longest.value
+
+    def encode_packed_spans(self, blob: bytes, offsets, bos=False, eos=False, reverse=False, dropout_prob=0.0):
+        """host to host: -> (ids np.int32, offsets np.uint64 [n + 1], spans np.uint32 [n_ids, 2])"""
+        L = _lib.load()
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        ids, off, spans = _lib.i32p(), _lib.u64p(), _lib.u32p()
+        err = _err()
+        rc = L.yttm_encode_as_ids_spans(self._h, blob, offsets.ctypes.data_as(_lib.u64p), n, int(bos), int(eos), int(reverse), float(dropout_prob),
+                                        C.byref(ids), C.byref(off), C.byref(spans), err, _lib.ERRLEN)
+        if rc != 0:
+            raise ValueError(err.value.decode())
+        off_a = _take(off, n + 1, C.c_uint64, np.uint64)
+        ids_a = _take(ids, int(off_a[-1]), C.c_int32, np.int32)
+        spans_a = _take(spans, 2 * int(off_a[-1]), C.c_uint32, np.uint32).reshape(-1, 2)
+        return ids_a, off_a, spans_a
+
     # ---- decimal id text on the device (include/yttm_mi355x.h): the format `yttm encode --output_type id` prints and `yttm decode` reads
     def ids_parse_device_raw(self, d_text, n_bytes):
         """-> (n_lines, n_ids, kernel_ms); the ids `while (ss >> x)` reads from every line are pending as after encode_device_raw with n_sent = n_lines"""
@@ -530,6 +577,45 @@ class BPE:
         """the same for `text` as encode_text_tensor takes it, one sentence per line"""
         from . import tensor
         return tensor.encode_text_subword_tensor(self, text, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, as_str=as_str)
+
+    # ---- where in the input every token came from (include/yttm_mi355x.h "Byte spans"; the reference has no counterpart)
+    def encode_spans_tensor(self, sentences, bos: bool = False, eos: bool = False, reverse: bool = False, dropout_prob: float = 0, padded: bool = True,
+                            width: Optional[int] = None, pad_id: Optional[int] = None, device=None):
+        """encode_tensor and, for every id, the bytes of its sentence it stands for: (ids [n, width], lengths [n], spans [n, width, 2]), or with
+        padded=False (ids [n_ids], offsets [n + 1], spans [n_ids, 2]); ids, lengths and spans are int32, spans = (start, end) in bytes from the
+        sentence's first byte, (0, 0) behind a row's last id.  A token without text of its own (<BOS>, <EOS>, a lone "▁") has an empty span."""
+        from . import tensor
+        return tensor.encode_spans_tensor(self, sentences, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, padded=padded, width=width,
+                                          pad_id=pad_id, device=device)
+
+    def encode_text_spans_tensor(self, text, bos: bool = False, eos: bool = False, reverse: bool = False, dropout_prob: float = 0, padded: bool = True,
+                                 width: Optional[int] = None, pad_id: Optional[int] = None):
+        """the same for `text` as encode_text_tensor takes it, one sentence per line; the spans count from the line's first byte"""
+        from . import tensor
+        return tensor.encode_text_spans_tensor(self, text, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, padded=padded, width=width,
+                                               pad_id=pad_id)
+
+    def encode_with_spans(self, sentences: List[str], bos: bool = False, eos: bool = False, reverse: bool = False, dropout_prob: float = 0,
+                          unit: str = "char"):
+        """-> (ids per sentence, (start, end) per id): with unit="char" offsets into the str, so that s[start:end] is the token's text (an unknown
+        run's for unk_id, "" for <BOS>, <EOS> and a lone "▁"); with unit="byte" offsets into s.encode().  Needs no torch."""
+        if unit not in ("char", "byte"):
+            raise ValueError('unit must be "char" or "byte"')
+        if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
+            raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+        sentences = list(sentences)
+        blob, offs = _pack(sentences)
+        ids, off, spans = self.bpe_cython.encode_packed_spans(blob, offs, bos, eos, reverse, dropout_prob)
+        spans = spans.astype(np.int64)
+        if unit == "char" and len(blob) != sum(map(len, sentences)):
+            # code points in front of a byte = the bytes in front of it that are no continuation bytes
+            raw = np.frombuffer(blob, np.uint8)
+            lead = np.zeros(len(raw) + 1, np.int64)
+            np.cumsum((raw & 0xC0) != 0x80, out=lead[1:])
+            base = np.repeat(offs[:-1].astype(np.int64), np.diff(off.astype(np.int64)))
+            spans = lead[spans + base[:, None]] - lead[base][:, None]
+        o, ids_l, sp_l = off.tolist(), ids.tolist(), spans.tolist()
+        return ([ids_l[o[i]:o[i + 1]] for i in range(len(sentences))], [[tuple(p) for p in sp_l[o[i]:o[i + 1]]] for i in range(len(sentences))])
 
     # ---- decimal id text, one sentence per line: the format `yttm encode --output_type id` prints and `yttm decode` reads
     def decode_file(self, path, out: str, ignore_ids: Optional[Collection] = None, chunk_bytes: Optional[int] = None, report: bool = False):

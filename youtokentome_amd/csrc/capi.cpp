@@ -316,6 +316,42 @@ int yttm_encode_file_idtext(yttm_encoder *h, const char *path, const char *out_p
   return finish(s, err, errlen);
 }
 
+int yttm_spans_device(yttm_encoder *h, const void *d_bytes, const void *d_offsets, uint64_t n_sent, uint64_t total_bytes, uint64_t max_sentence_bytes, int bos,
+                      int eos, int reverse, double dropout_prob, uint64_t *n_ids, double *kernel_ms, char *err, int errlen) {
+  unsigned long long ni = 0;
+  Status s = h->enc->spans_device(d_bytes, d_offsets, n_sent, total_bytes, max_sentence_bytes, bos, eos, reverse, dropout_prob, &ni, kernel_ms);
+  if (n_ids) *n_ids = ni;
+  return finish(s, err, errlen);
+}
+int yttm_spans_text_device(yttm_encoder *h, const void *d_text, uint64_t n_bytes, int bos, int eos, int reverse, double dropout_prob, uint64_t *n_lines,
+                           uint64_t *n_ids, double *kernel_ms, char *err, int errlen) {
+  unsigned long long nl = 0, ni = 0;
+  Status s = h->enc->spans_text_device(d_text, n_bytes, bos, eos, reverse, dropout_prob, &nl, &ni, kernel_ms);
+  if (n_lines) *n_lines = nl;
+  if (n_ids) *n_ids = ni;
+  return finish(s, err, errlen);
+}
+int yttm_spans_fetch(yttm_encoder *h, uint32_t *spans, uint64_t n_sent, char *err, int errlen) {
+  return finish(h->enc->take_spans(spans, n_sent, false), err, errlen);
+}
+int yttm_spans_copy_device(yttm_encoder *h, void *d_spans, uint64_t n_sent, char *err, int errlen) {
+  return finish(h->enc->take_spans(d_spans, n_sent, true), err, errlen);
+}
+int yttm_spans_copy_padded(yttm_encoder *h, void *d_matrix, uint64_t n_sent, uint64_t width, uint64_t *longest, char *err, int errlen) {
+  unsigned long long need = 0;
+  Status s = h->enc->copy_spans_padded(d_matrix, n_sent, width, &need);
+  if (longest) *longest = need;
+  return finish(s, err, errlen);
+}
+int yttm_encode_as_ids_spans(yttm_encoder *h, const uint8_t *bytes, const uint64_t *offsets, uint64_t n_sent, int bos, int eos, int reverse,
+                             double dropout_prob, int32_t **ids, uint64_t **out_offsets, uint32_t **spans, char *err, int errlen) {
+  unsigned long long *off = nullptr;
+  Status s = h->enc->encode_as_ids_spans(bytes, (const unsigned long long *)offsets, n_sent, bos, eos, reverse, dropout_prob, ids, &off, spans);
+  if (!s.ok()) return finish(s, err, errlen);
+  *out_offsets = (uint64_t *)off;
+  return 0;
+}
+
 int yttm_encoder_set_cache(yttm_encoder *h, int mode, uint64_t min_bytes) {
   h->enc->set_cache(mode, min_bytes);
   return 0;

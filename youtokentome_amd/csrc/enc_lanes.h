@@ -74,6 +74,11 @@ struct EncodeLane {
     unsigned long long n_sent = 0, n_bytes = 0;
     bool valid = false;
   } dec;
+  struct {  // byte spans of the encode result pending beside them (host_decode.cpp, k_spans.h): uint32 [n_ids][2]; any later encode empties the slot
+    DevBuf<uint32_t> spans, misc;  // misc[0]: the kernel's "the ids do not fit the text"
+    unsigned long long n_sent = 0, n_ids = 0;
+    bool valid = false;
+  } sp;
   struct {  // line split (host_lines.cpp): newlines per tile, their scan, the lines' offsets
     DevBuf<uint32_t> cnt;
     DevBuf<unsigned long long> rank, off, misc;  // misc[0]: longest line (k_lines_longest)
@@ -87,6 +92,7 @@ struct EncodeLane {
     wc.misc.alloc(2);
     res.misc.alloc(1);
     dec.misc.alloc(1);
+    sp.misc.alloc(1);
     ln.misc.alloc(1);
   }
   ~EncodeLane() {
@@ -122,6 +128,7 @@ struct EncoderDevice {
   bool sub_ready = false;
   DevBuf<uint8_t> sub_blob;
   DevBuf<uint32_t> sub_off;
+  DevBuf<uint32_t> sub_units;  // [vocab] the units an id covers (k_spans.h), filled beside the pieces
   // a free lane, locked (falls back to waiting for the caller's turn-based choice)
   // (Lane 0 last: the device-resident pair encode_device / fetch_device_result keeps its result there, unlocked, between the two
   // calls -- a host-to-host encode from another thread in between takes another lane while one is free.)
@@ -190,6 +197,11 @@ unsigned long long scan_counts(EncodeLane &d, const uint32_t *counts, unsigned l
 // result was made from), left in the lane's text slot (dec) as a decode leaves its text: measure -> scan -> write (k_subword.h)
 Status format_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_text, const void *d_soff, bool reverse,
                       unsigned long long *n_text_bytes, double *kernel_ms);
+
+// Byte spans of the encode result pending on the lane (locked by the caller; the same d_text / d_soff as format_on_lane), left in the lane's span
+// slot (sp): one pass (k_spans.h).  Ids that do not fit their text: code 2, and no spans are pending.
+Status spans_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_text, const void *d_soff, bool reverse,
+                     double *kernel_ms);
 
 // Device decode of ids in HBM on the lane (locked by the caller), the text left in the lane's text slot: measure -> scan -> write (k_decode.h).
 // n_flat: the ids the kernels walk; newline (ragged input only): a '\n' behind every sentence.  An id that is neither ignored nor valid: the

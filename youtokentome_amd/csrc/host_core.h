@@ -164,6 +164,19 @@ class BaseEncoder {  // bpe.h:22-82
   Status encode_file_idtext(const std::string &path, const std::string &out_path, bool bos, bool eos, bool reverse, double dropout_prob,
                             unsigned long long piece_bytes, unsigned long long *n_lines, unsigned long long *n_ids, unsigned long long *n_text_bytes,
                             std::string *report) const;
+  // Byte spans on the device (host_decode.cpp, host_lines.cpp, k_spans.h): encode_device / encode_text_device, then for every id the bytes of
+  // its sentence it stands for, uint32 [n_ids][2] relative to the sentence's first byte (on the text route: the line's), in lane 0's span slot; the
+  // ids are pending as after encode_device.  The slot holds the spans of the ids pending beside it: any later encode on the lane empties it, and
+  // taking spans that are not there is code 1.
+  Status spans_device(const void *d_bytes, const void *d_offsets, unsigned long long n_sent, unsigned long long total_bytes,
+                      unsigned long long max_sentence_bytes, bool bos, bool eos, bool reverse, double dropout_prob, unsigned long long *n_ids,
+                      double *kernel_ms) const;
+  Status spans_text_device(const void *d_text, unsigned long long n_bytes, bool bos, bool eos, bool reverse, double dropout_prob,
+                           unsigned long long *n_lines, unsigned long long *n_ids, double *kernel_ms) const;
+  Status take_spans(void *spans, unsigned long long n_sent, bool to_device) const;  // ragged [n_ids][2]: to a host array or device to device
+  Status copy_spans_padded(void *d_matrix, unsigned long long n_sent, unsigned long long width, unsigned long long *longest) const;  // [n_sent, width, 2]
+  Status encode_as_ids_spans(const uint8_t *bytes, const unsigned long long *offsets, unsigned long long n_sent, bool bos, bool eos, bool reverse,
+                             double dropout_prob, int32_t **ids, unsigned long long **out_off, uint32_t **spans) const;  // host to host, free()
   // the YTTM_* hooks as they stood when THIS encoder was made: every entry point binds them to its thread (yttm_config.h CfgBind), so that a
   // later encoder or training never changes the paths of this one
   std::shared_ptr<const Config> config() const;

@@ -201,22 +201,37 @@ static void subword_table(const BaseEncoder &enc, EncoderDevice &D) {
   if (D.sub_ready) return;
   const int V = enc.vocab_size();
   std::string blob, piece;
-  std::vector<uint32_t> off((size_t)V + 1, 0);
+  std::vector<uint32_t> off((size_t)V + 1, 0), units((size_t)V, 0);
+  const SpecialTokens &sp = enc.bpe_state.special_tokens;
   for (int id = 0; id < V; id++) {
     off[(size_t)id] = (uint32_t)blob.size();
     piece.clear();
     if (enc.id_to_subword(id, &piece, false).ok()) blob += piece;
     if (blob.size() >= (size_t)DEC_INVALID) throw GpuError{"subword: the vocabulary's text does not fit 2 GB"};
+    // the units the id covers (k_spans.h): an unknown run is one; a special token none; else the piece's code points other than U+2581
+    if (id == sp.unk_id) {
+      units[(size_t)id] = 1;
+    } else if (id != sp.pad_id && id != sp.bos_id && id != sp.eos_id) {
+      uint32_t n = 0;
+      for (size_t i = 0; i < piece.size(); i++) {
+        if (((uint8_t)piece[i] & 0xC0u) == 0x80u) continue;
+        if (piece.compare(i, 3, "\xe2\x96\x81") != 0) n++;
+      }
+      units[(size_t)id] = n;
+    }
   }
   off[(size_t)V] = (uint32_t)blob.size();
   DevBuf<uint8_t> d_blob;  // (handed to the encoder once both are filled)
-  DevBuf<uint32_t> d_off;
+  DevBuf<uint32_t> d_off, d_units;
   d_blob.alloc(blob.size() + 1);
   d_off.alloc(off.size());
+  d_units.alloc(units.size());
   if (!blob.empty()) HIP_CHECK(hipMemcpy(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
   HIP_CHECK(hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+  if (!units.empty()) HIP_CHECK(hipMemcpy(d_units, units.data(), units.size() * 4, hipMemcpyHostToDevice));
   D.sub_blob = std::move(d_blob);
   D.sub_off = std::move(d_off);
+  D.sub_units = std::move(d_units);
   D.sub_ready = true;
 }
 
@@ -322,6 +337,170 @@ Status BaseEncoder::subword_device(const void *d_bytes, const void *d_offsets, u
   s = format_on_lane(*this, *dev_, d, device_, d_bytes, d_offsets, reverse, n_text_bytes, timed ? &ms_fmt : nullptr);
   if (kernel_ms) *kernel_ms = ms_enc + ms_fmt;
   return s;
+}
+
+// ---- byte spans (k_spans.h) ----------------------------------------------------------------------------------------------------------------
+// For every id K5 left the bytes of its sentence it stands for, made on the device from the ids and the batch's own text in one pass: uint32
+// [n_ids][2] in the lane's span slot, beside the ids they belong to.
+Status spans_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_text, const void *d_soff, bool reverse,
+                     double *kernel_ms) {
+  return on_device(device, [&]() -> Status {
+    d.sp.valid = false;
+    if (kernel_ms) *kernel_ms = 0;
+    const unsigned long long n_sent = d.res.n_sent;
+    if (n_sent == 0) {
+      d.sp.n_sent = d.sp.n_ids = 0;
+      d.sp.valid = true;
+      return Status();
+    }
+    subword_table(enc, D);
+    const SubInput in{(const uint8_t *)d_text, (const unsigned long long *)d_soff, d.res.ids, d.res.off, n_sent, (int32_t)enc.bpe_state.special_tokens.unk_id,
+                      reverse ? 1 : 0};
+    d.sp.spans.grow((size_t)d.res.n_ids * 2 + 2);
+    EventPair ev(d.st, kernel_ms != nullptr);
+    ev.start();
+    HIP_CHECK(hipMemsetAsync(d.sp.misc, 0, 4, d.st));
+    launch_spans(D.m, in, D.sub_units, (uint32_t)enc.vocab_size(), d.res.n_ids, d.sp.spans, d.sp.misc, d.st);
+    ev.stop();
+    uint32_t bad = 0;
+    HIP_CHECK(hipMemcpyAsync(&bad, d.sp.misc, 4, hipMemcpyDeviceToHost, d.st));
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    if (kernel_ms) *kernel_ms = ev.elapsed_ms();
+    if (bad) return Status(2, "spans: the ids of a sentence do not fit the units of its text");
+    d.sp.n_sent = n_sent;
+    d.sp.n_ids = d.res.n_ids;
+    d.sp.valid = true;
+    return Status();
+  });
+}
+
+Status BaseEncoder::spans_device(const void *d_bytes, const void *d_offsets, unsigned long long n_sent, unsigned long long total_bytes,
+                                 unsigned long long max_sentence_bytes, bool bos, bool eos, bool reverse, double dropout_prob, unsigned long long *n_ids,
+                                 double *kernel_ms) const {
+  if (n_ids) *n_ids = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work: nothing that was pending is touched)
+  if (!tokens.ok()) return tokens;
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (n_sent && !d_offsets) return Status(2, "spans_device: no offsets");
+  const CfgBind bind(dev_->cfg);
+  EncodeLane &d = dev_->lane[0];
+  std::lock_guard<std::mutex> lk(d.mu);
+  const bool timed = kernel_ms != nullptr;
+  double ms_enc = 0, ms_sp = 0;
+  Status s = encode_on_lane(*this, *dev_, d, device_, d_bytes, d_offsets, n_sent, total_bytes, max_sentence_bytes, bos, eos, reverse, dropout_prob, n_ids,
+                            timed ? &ms_enc : nullptr);
+  if (!s.ok()) return s;
+  s = spans_on_lane(*this, *dev_, d, device_, d_bytes, d_offsets, reverse, timed ? &ms_sp : nullptr);
+  if (kernel_ms) *kernel_ms = ms_enc + ms_sp;
+  return s;
+}
+
+Status BaseEncoder::take_spans(void *spans, unsigned long long n_sent, bool to_device) const {
+  const char *who = to_device ? "copy_spans: no matching result" : "fetch_spans: no matching result";
+  if (!dev_) return Status(1, who);
+  const CfgBind bind(dev_->cfg);
+  EncodeLane &d = dev_->lane[0];
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (!d.sp.valid || n_sent != d.sp.n_sent || n_sent != d.res.n_sent || d.sp.n_ids != d.res.n_ids) return Status(1, who);
+  if (!spans || !d.sp.n_ids) return Status();
+  if (to_device) return copy_out_device(device_, d, spans, d.sp.spans, (size_t)d.sp.n_ids * 8, nullptr, nullptr, n_sent);
+  return on_device(device_, [&]() -> Status {
+    copy_down(device_, spans, d.sp.spans, (size_t)d.sp.n_ids * 8, d.st);
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    return Status();
+  });
+}
+
+Status BaseEncoder::copy_spans_padded(void *d_matrix, unsigned long long n_sent, unsigned long long width, unsigned long long *longest) const {
+  if (longest) *longest = 0;
+  if (!dev_) return Status(1, "copy_spans_padded: no matching result");
+  const CfgBind bind(dev_->cfg);
+  EncodeLane &d = dev_->lane[0];
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (!d.sp.valid || n_sent != d.sp.n_sent || n_sent != d.res.n_sent || d.sp.n_ids != d.res.n_ids) return Status(1, "copy_spans_padded: no matching result");
+  if (n_sent == 0) return Status();
+  return on_device(device_, [&]() -> Status {
+    HIP_CHECK(hipMemsetAsync(d.res.misc, 0, 8, d.st));
+    launch_enc_longest(d.res.off, n_sent, (unsigned int *)d.res.misc.p, d.st);
+    unsigned long long need = 0;
+    HIP_CHECK(hipMemcpyAsync(&need, d.res.misc, 8, hipMemcpyDeviceToHost, d.st));
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    if (longest) *longest = need;
+    if (need > width)  // nothing is truncated, and nothing was written
+      return Status(1, "width is smaller than the longest row. Current value: width = " + std::to_string(width) + "; longest = " + std::to_string(need) + ";");
+    if (n_sent > (~0ull >> 4) / (width ? width : 1)) return Status(2, "copy_spans_padded: the matrix is too large");
+    if (!width) return Status();
+    if (!d_matrix) return Status(2, "copy_spans_padded: no output");
+    if (((uintptr_t)d_matrix & 7u) != 0) return Status(2, "copy_spans_padded: the matrix must be 8-byte aligned");
+    launch_spans_pad(d.sp.spans, d.res.off, n_sent, width, (uint32_t *)d_matrix, d.st);
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    return Status();
+  });
+}
+
+// host to host on one lane: upload -> K5 -> spans -> download, into arrays the caller releases with free()
+Status BaseEncoder::encode_as_ids_spans(const uint8_t *bytes, const unsigned long long *offsets, unsigned long long n_sent, bool bos, bool eos, bool reverse,
+                                        double dropout_prob, int32_t **ids, unsigned long long **out_off, uint32_t **spans) const {
+  *ids = nullptr;
+  *out_off = nullptr;
+  *spans = nullptr;
+  const CfgBind bind(config());
+  Status s = check_bos_eos(*this, bos, eos);
+  if (!s.ok()) return s;
+  if (n_sent && !dev_) return Status(2, "encoder has no device state");
+  unsigned long long *off = (unsigned long long *)result_alloc((size_t)(n_sent + 1) * 8);
+  if (!off) return Status(2, "out of memory");
+  off[0] = 0;
+  unsigned long long n_ids = 0;
+  int32_t *idp = nullptr;
+  uint32_t *spp = nullptr;
+  if (n_sent) {
+    const unsigned long long b0 = offsets[0], total_bytes = offsets[n_sent] - b0;
+    unsigned long long max_len = 0;
+    std::vector<unsigned long long> rel((size_t)n_sent + 1);  // offsets are rebased to the first byte of the batch
+    for (unsigned long long i = 0; i <= n_sent; i++) rel[i] = offsets[i] - b0;
+    for (unsigned long long i = 0; i < n_sent; i++) max_len = std::max(max_len, rel[i + 1] - rel[i]);
+    std::unique_lock<std::mutex> lk;
+    EncodeLane &d = dev_->acquire(lk);  // held until the results are back on the host
+    s = on_device(device_, [&]() -> Status {
+      d.in.bytes.grow((size_t)total_bytes + 16);
+      d.in.off.grow((size_t)n_sent + 1);
+      copy_up(device_, d.in.bytes, bytes + b0, (size_t)total_bytes, d.st);
+      copy_up(device_, d.in.off, rel.data(), ((size_t)n_sent + 1) * 8, d.st);
+      HIP_CHECK(hipStreamSynchronize(d.st));
+      return Status();
+    });
+    if (s.ok()) s = encode_on_lane(*this, *dev_, d, device_, d.in.bytes, d.in.off, n_sent, total_bytes, max_len, bos, eos, reverse, dropout_prob, &n_ids, nullptr);
+    if (s.ok()) s = spans_on_lane(*this, *dev_, d, device_, d.in.bytes, d.in.off, reverse, nullptr);
+    if (s.ok()) {
+      idp = (int32_t *)result_alloc((size_t)(n_ids ? n_ids : 1) * 4);
+      spp = (uint32_t *)result_alloc((size_t)(n_ids ? n_ids : 1) * 8);
+      if (!idp || !spp) s = Status(2, "out of memory");
+    }
+    if (s.ok())
+      s = on_device(device_, [&]() -> Status {
+        if (n_ids) copy_down(device_, idp, d.res.ids, (size_t)n_ids * 4, d.st);
+        if (n_ids) copy_down(device_, spp, d.sp.spans, (size_t)n_ids * 8, d.st);
+        copy_down(device_, off, d.res.off, (size_t)(n_sent + 1) * 8, d.st);
+        HIP_CHECK(hipStreamSynchronize(d.st));
+        return Status();
+      });
+  } else {
+    idp = (int32_t *)result_alloc(4);
+    spp = (uint32_t *)result_alloc(8);
+    if (!idp || !spp) s = Status(2, "out of memory");
+  }
+  if (!s.ok()) {
+    free(idp);
+    free(spp);
+    free(off);
+    return s;
+  }
+  *ids = idp;
+  *out_off = off;
+  *spans = spp;
+  return Status();
 }
 
 }  // namespace yttm

@@ -146,6 +146,27 @@ Status BaseEncoder::subword_text_device(const void *d_text, unsigned long long n
   return s;
 }
 
+// split, encode, then the byte spans of those ids (host_decode.cpp): a sentence is a line with its newline, the spans count from the line's start
+Status BaseEncoder::spans_text_device(const void *d_text, unsigned long long n_bytes, bool bos, bool eos, bool reverse, double dropout_prob,
+                                      unsigned long long *n_lines, unsigned long long *n_ids, double *kernel_ms) const {
+  if (n_lines) *n_lines = 0;
+  if (n_ids) *n_ids = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work: nothing that was pending is touched)
+  if (!tokens.ok()) return tokens;
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (n_bytes && !d_text) return Status(2, "spans_text_device: no text");
+  const CfgBind bind(dev_->cfg);
+  EncodeLane &d = dev_->lane[0];
+  std::lock_guard<std::mutex> lk(d.mu);
+  double ms_split = 0, ms_enc = 0, ms_sp = 0;
+  Status s = encode_text_on_lane(*this, *dev_, d, device_, d_text, n_bytes, bos, eos, reverse, dropout_prob, n_lines, n_ids, kernel_ms ? &ms_split : nullptr,
+                                 kernel_ms ? &ms_enc : nullptr);
+  if (s.ok()) s = spans_on_lane(*this, *dev_, d, device_, d_text, d.ln.off, reverse, kernel_ms ? &ms_sp : nullptr);
+  if (kernel_ms) *kernel_ms = ms_split + ms_enc + ms_sp;
+  return s;
+}
+
 // ---- decimal id text (k_idtext.h) ----------------------------------------------------------------------------------------------------------
 // The ids `while (ss >> x) ids.push_back(x)` reads from every line of the split pending on the lane (bpe.cpp:1863-1873), left in the lane's
 // encode-result buffers exactly as encode_on_lane leaves its ids, n_sent = the lines: measure -> scan -> write.
@@ -154,6 +175,7 @@ static Status parse_on_lane(EncodeLane &d, int device, const void *d_text, unsig
     const unsigned long long n_lines = d.ln.n_lines;
     d.res.n_sent = n_lines;
     d.res.n_ids = 0;
+    d.sp.valid = false;  // (spans belong to the ids they were made from)
     if (n_ids_out) *n_ids_out = 0;
     if (kernel_ms) *kernel_ms = 0;
     if (n_lines == 0) return Status();

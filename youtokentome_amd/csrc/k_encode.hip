@@ -1162,3 +1162,4 @@ void launch_encode_gather(const int32_t *scratch_ids, const unsigned long long *
 #include "k_lines.h"   // the lines of a text in HBM: kernels and launchers of this translation unit
 #include "k_subword.h"  // SUBWORD output of the ids K5 left: kernels and launchers of this translation unit
 #include "k_idtext.h"   // decimal id text, parsed and printed: kernels and launchers of this translation unit
+#include "k_spans.h"    // byte spans of the ids K5 left: kernels and launchers of this translation unit

@@ -422,6 +422,16 @@ void launch_subword_measure(const EncModel &m, const SubInput &in, const DecTabl
 void launch_subword_write(const EncModel &m, const SubInput &in, const DecTable &tb, unsigned long long n_ids, const unsigned long long *out_off,
                           uint8_t *out, hipStream_t st);
 
+// ---- byte spans (k_spans.h, compiled with k_encode.hip): one pass, 8 bytes per id ----
+// piece_units[vocab]: the units an id covers (1 for unk_id, else the code points of its piece other than U+2581).  spans: uint32 [n_ids][2],
+// 8-byte aligned, (start, end) of stored id k relative to its sentence's first byte.  *bad (holds 0 before the launch) becomes 1 where the ids
+// of a sentence do not fit its text.  n_ids sizes the groups of sentences.
+void launch_spans(const EncModel &m, const SubInput &in, const uint32_t *piece_units, uint32_t vocab, unsigned long long n_ids, uint32_t *spans, uint32_t *bad,
+                  hipStream_t st);
+// spans + ioff -> uint32 [n_sent, width][2], the tail of a row (0, 0).  matrix: 8-byte aligned; rows must fit.
+void launch_spans_pad(const uint32_t *spans, const unsigned long long *ioff, unsigned long long n_sent, unsigned long long width, uint32_t *matrix,
+                      hipStream_t st);
+
 // ---- the lines of a text in HBM (k_lines.h, compiled with k_encode.hip): count -> launch_exclusive_scan -> write, then the longest line ----
 // d_text: any address.  lines_tiles: entries of cnt (the scan's input; 0: a text of fewer than two bytes holds no newline that starts a line).
 unsigned long long lines_tiles(const void *d_text, unsigned long long n_bytes);

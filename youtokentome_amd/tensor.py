@@ -1,5 +1,5 @@
 """Device tensors in, device tensors out: `BPE.encode_tensor` / `BPE.encode_text_tensor` / `BPE.text_lines_tensor` / `BPE.decode_tensor` /
-`BPE.encode_subword_tensor` / `BPE.encode_text_subword_tensor` / `BPE.decode_text_tensor` / `BPE.parse_ids_tensor` on top
+`BPE.encode_subword_tensor` / `BPE.encode_text_subword_tensor` / `BPE.encode_spans_tensor` / `BPE.encode_text_spans_tensor` / `BPE.decode_text_tensor` / `BPE.parse_ids_tensor` on top
 of the raw device layer of `bpe._Core` (include/yttm_mi355x.h: yttm_encode_device, yttm_encode_text_device, yttm_lines_*, yttm_encode_copy_*,
 yttm_decode_device*, yttm_decode_copy_device).  torch is imported at call
 time; the rest of the package does not need it.
@@ -232,6 +232,53 @@ def encode_text_subword_tensor(bpe, text, bos=False, eos=False, reverse=False, d
     torch.cuda.current_stream(dev).synchronize()  # the text is complete before the library's own stream reads it
     n, _, n_text, _ = core.subword_text_device_raw(d_text.data_ptr(), n_bytes, bos, eos, reverse, dropout_prob)
     return _take_text(torch, core, dev, n, n_text, as_str)
+
+
+def _take_spans(torch, core, dev, n, n_ids, padded, width, pad_id):
+    """the pending encode result of n sentences and its spans as tensors that torch owns"""
+    first, second = _take_encoded(torch, core, dev, n, n_ids, padded, width, pad_id)
+    if not padded:
+        spans = torch.empty((n_ids, 2), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        core.copy_spans_device(spans.data_ptr(), n)
+        return first, second, spans
+    spans = torch.empty((n, first.shape[1], 2), dtype=torch.int32, device=dev)
+    if n:
+        torch.cuda.current_stream(dev).synchronize()
+        core.copy_spans_padded(spans.data_ptr(), n, first.shape[1])
+    return first, second, spans
+
+
+def encode_spans_tensor(bpe, sentences, bos=False, eos=False, reverse=False, dropout_prob=0, padded=True, width=None, pad_id=None, device=None):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, device)
+    if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
+        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+    if padded and pad_id is None:
+        pad_id = bpe.subword_to_id("<PAD>")
+        if pad_id == -1 or bpe.id_to_subword(pad_id) != "<PAD>":
+            raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
+    d_bytes, d_off, n, total, longest_in = _sentences_on(torch, sentences, dev)
+    torch.cuda.current_stream(dev).synchronize()  # the inputs are complete before the library's own stream reads them
+    n_ids, _ = core.spans_device_raw(d_bytes.data_ptr(), d_off.data_ptr(), n, total, longest_in, bos, eos, reverse, dropout_prob)
+    return _take_spans(torch, core, dev, n, n_ids, padded, width, pad_id)
+
+
+def encode_text_spans_tensor(bpe, text, bos=False, eos=False, reverse=False, dropout_prob=0, padded=True, width=None, pad_id=None):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
+        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+    if padded and pad_id is None:
+        pad_id = bpe.subword_to_id("<PAD>")
+        if pad_id == -1 or bpe.id_to_subword(pad_id) != "<PAD>":
+            raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
+    d_text, n_bytes = _text_on(torch, text, dev)
+    torch.cuda.current_stream(dev).synchronize()  # the text is complete before the library's own stream reads it
+    n, n_ids, _ = core.spans_text_device_raw(d_text.data_ptr(), n_bytes, bos, eos, reverse, dropout_prob)
+    return _take_spans(torch, core, dev, n, n_ids, padded, width, pad_id)
 
 
 def parse_ids_tensor(bpe, text, padded=False, width=None, pad_id=None):
