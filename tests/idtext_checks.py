@@ -165,6 +165,28 @@ def check_one(core, B, data, aligns=ALL, what=""):
     return rows
 
 
+def check_long_piece_lines(B, tmp_path, aligns=ALL):
+    """newline mode of the decode's write kernel in front of, between and behind pieces longer than the staging tile, which the wavefront copies
+    one by one: empty lines before, between and after such lines, and a last line without a newline == decode_cli, byte for byte"""
+    import youtokentome_amd as yttm
+    rng = random.Random(4)  # (the model of decode_checks.check_long_pieces, built the same way)
+    word = "".join(rng.choice("abcdefgh") for _ in range(2300))
+    corpus, model = str(tmp_path / "long.txt"), str(tmp_path / "long.model")
+    open(corpus, "w").write((word + " xy ") * 6 + "ab cd\n")
+    yttm.BPE.train(corpus, model, 4 + 11 + 2400, 1.0, 1, 0, 1, 2, 3)
+    core = yttm.BPE(model).bpe_cython
+    whole = core.subword_to_id("▁" + word)
+    assert core.id_to_subword(whole) == "▁" + word, "the long word did not become one piece"
+    data = b"\n%d\n5 %d %d 6\n\n\n%d 8" % (whole, whole, whole, whole)
+    rc, msg, want = cli_decode(core, data)
+    assert rc == 0 and want.count(word.encode()) == 4 and want.startswith(b"\n" + word.encode() + b"\n"), msg
+    for a in aligns:
+        got = dev_decode_text(core, B, data, (), a)
+        assert got[:2] == (0, ""), (a, got[1])
+        assert got[2] == want, (a, len(got[2]), len(want))
+        assert (got[4], got[5]) == (6, 7) and got[3].tolist()[-1] == len(want)
+
+
 # ---- cases 1 - 4: line structure, signs and glue, fail points, range ------------------------------------------------------------------------
 def check_line_structure(B, aligns=ALL, name="readme_small"):
     core = D.core_of(name)

@@ -241,6 +241,37 @@ def check_lengths(B, name="readme_small"):
     assert L.yttm_decode_fetch(core._h, None, off.ctypes.data_as(_lib.u64p), 0, err, _lib.ERRLEN) == 0 and off[0] == 0
 
 
+def line_of_bytes(words, target):
+    """a sentence of single-id words whose SUBWORD line holds exactly `target` bytes in front of its newline ("▁" + word + " " per word)"""
+    cost = {len(w.encode()) + 4: w for w in words}
+    best = {0: []}  # bytes -> words
+    for t in range(1, target + 1):
+        for c, w in cost.items():
+            if t - c in best:
+                best[t] = best[t - c] + [w]
+                break
+    assert target in best, (target, sorted(cost))
+    return " ".join(best[target])
+
+
+def check_full_tile(B, name="readme_small"):
+    """sentences whose pieces and spaces fill the write pass's 2048-byte staging tile to its last byte, one short of it and one past it, each alone
+    in its group and behind a first 16-byte unit shared with the sentence before: the newline behind them has no room unless the tile is flushed first"""
+    bpe, fmt = fmt_of(name)
+    core = bpe.bpe_cython
+    words = single_id_words(bpe)
+    tile, sents, cursor = 2048, [], 0
+    for delta in (0, 0, -1, 1, 0, -17, 0):
+        body = tile - cursor % 16 + delta  # (the tile holds the cursor's unit from its start)
+        sents.append(line_of_bytes(words, body))
+        cursor += body + 1
+    for b, e, r in ((0, 0, 0), (0, 0, 1)):
+        lines, rows = same(core, B, sents, b, e, r, ("full tile", b, e, r), fmt)
+        assert [len(ln) for ln in lines] == [len(host_text(core, [s])[2]) for s in sents]
+    lines, _ = same(core, B, sents, 0, 0, 0, "full tile")
+    assert len(lines[0]) == tile + 1 and len(lines[1]) == tile - 1 + 1 and all(len(r) > 256 for r in _)
+
+
 def unknown_chars(alphabet):
     u = {1: "Z", 2: "é", 3: "中", 4: "😀"}
     assert all(ord(c) not in alphabet and len(c.encode()) == n for n, c in u.items())

@@ -56,6 +56,10 @@ def test_pending_results(B):
     T.check_pending(B)
 
 
+def test_long_pieces_between_newlines(B, tmp_path):
+    T.check_long_piece_lines(B, tmp_path, FEW)
+
+
 def test_decode_file_in_pieces(tmp_path):
     T.check_decode_file(tmp_path, use_ref=True)
 

@@ -34,6 +34,10 @@ def test_groups_of_short_sentences(B):
     S.check_groups(B)
 
 
+def test_sentences_that_fill_the_tile(B):
+    S.check_full_tile(B)
+
+
 def test_errors_and_pending_results(B):
     S.check_errors(B)
 

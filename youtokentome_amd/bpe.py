@@ -26,6 +26,11 @@ def _err():
     return C.create_string_buffer(_lib.ERRLEN)
 
 
+def _check_dropout(dropout_prob):  # yttm.pyx:92-93
+    if dropout_prob < 0 or dropout_prob > 1:
+        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+
+
 def _pack(sentences):
     """list[str] -> (utf-8 blob, uint64 offsets[n+1])  (the `.encode()` per sentence of yttm.pyx:103)"""
     offs = np.zeros(len(sentences) + 1, dtype=np.uint64)
@@ -211,8 +216,7 @@ class _Core:
     def encode_file(self, path, out=None, bos=False, eos=False, reverse=False, dropout_prob=0.0, chunk_bytes=None, report=False):
         """a text file -> (int32 ids, uint64 offsets[n_lines + 1]), or with out=PREFIX the files PREFIX.ids / PREFIX.off and (n_lines, n_ids);
         report=True appends the call's report (a dict) to the result"""
-        if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
-            raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+        _check_dropout(dropout_prob)
         L = _lib.load()
         ids, off, nl, ni, err = _lib.i32p(), _lib.u64p(), C.c_uint64(), C.c_uint64(), _err()
         rep = C.create_string_buffer(1024)
@@ -245,23 +249,27 @@ class _Core:
                                                          C.byref(nl), C.byref(ni), C.byref(nt), C.byref(ms), err, _lib.ERRLEN), err)
         return nl.value, ni.value, nt.value, ms.value
 
-    def encode_file_subword(self, path, out, bos=False, eos=False, reverse=False, dropout_prob=0.0, chunk_bytes=None, report=False):
-        """a text file -> the text file `yttm encode --output_type subword` prints for it, written to `out`: (n_lines, n_ids, n_text_bytes), or with
-        report=True the call's report (a dict)"""
-        if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
-            raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
-        if out is None:
-            raise ValueError("encode_file with output_type SUBWORD needs out, the path of the text file to write")
+    def _file_to_text(self, entry, path, out, args, chunk_bytes, report):
+        """one of the library's file-to-text entries (`args`: what it takes between the two paths and the piece size) -> (n_lines, n_ids,
+        n_text_bytes), or with report=True the call's report (a dict)"""
         nl, ni, nt, err = C.c_uint64(), C.c_uint64(), C.c_uint64(), _err()
         rep = C.create_string_buffer(1024)
-        rc = _lib.load().yttm_encode_file_subword(self._h, os.fsencode(path), os.fsencode(out), int(bos), int(eos), int(reverse), float(dropout_prob),
-                                                  int(chunk_bytes or 0), C.byref(nl), C.byref(ni), C.byref(nt), rep, len(rep), err, _lib.ERRLEN)
+        rc = getattr(_lib.load(), entry)(self._h, os.fsencode(path), os.fsencode(out), *args, int(chunk_bytes or 0), C.byref(nl), C.byref(ni), C.byref(nt),
+                                         rep, len(rep), err, _lib.ERRLEN)
         if rc != 0:
             raise ValueError(err.value.decode(errors="replace"))
         if report:
             import json
             return json.loads(rep.value.decode())
         return nl.value, ni.value, nt.value
+
+    def encode_file_subword(self, path, out, bos=False, eos=False, reverse=False, dropout_prob=0.0, chunk_bytes=None, report=False):
+        """a text file -> the text file `yttm encode --output_type subword` prints for it, written to `out`: (n_lines, n_ids, n_text_bytes), or with
+        report=True the call's report (a dict)"""
+        _check_dropout(dropout_prob)
+        if out is None:
+            raise ValueError("encode_file with output_type SUBWORD needs out, the path of the text file to write")
+        return self._file_to_text("yttm_encode_file_subword", path, out, (int(bos), int(eos), int(reverse), float(dropout_prob)), chunk_bytes, report)
 
     # ---- byte spans on the device (include/yttm_mi355x.h): the spans stay in the encoder, beside the ids they belong to, until an encode replaces those
     def spans_device_raw(self, d_bytes, d_offsets, n_sent, total_bytes, max_sentence_bytes, bos=False, eos=False, reverse=False, dropout_prob=0.0):
@@ -337,38 +345,18 @@ class _Core:
         if out is None:
             raise ValueError("decode_file needs out, the path of the text file to write")
         ign, ign_p, n_ign = self._ignore(ignore_ids)
-        nl, ni, nt, err = C.c_uint64(), C.c_uint64(), C.c_uint64(), _err()
-        rep = C.create_string_buffer(1024)
-        rc = _lib.load().yttm_decode_file(self._h, os.fsencode(path), os.fsencode(out), ign_p, n_ign, int(chunk_bytes or 0), C.byref(nl), C.byref(ni),
-                                          C.byref(nt), rep, len(rep), err, _lib.ERRLEN)
-        if rc != 0:
-            raise ValueError(err.value.decode(errors="replace"))
-        if report:
-            import json
-            return json.loads(rep.value.decode())
-        return nl.value, ni.value, nt.value
+        return self._file_to_text("yttm_decode_file", path, out, (ign_p, n_ign), chunk_bytes, report)
 
     def encode_file_idtext(self, path, out, bos=False, eos=False, reverse=False, dropout_prob=0.0, chunk_bytes=None, report=False):
         """a text file -> the text file `yttm encode --output_type id` prints for it, written to `out`: (n_lines, n_ids, n_text_bytes), or with
         report=True the call's report (a dict)"""
-        if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
-            raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+        _check_dropout(dropout_prob)
         if out is None:
             raise ValueError("encode_file with id_text=True needs out, the path of the text file to write")
-        nl, ni, nt, err = C.c_uint64(), C.c_uint64(), C.c_uint64(), _err()
-        rep = C.create_string_buffer(1024)
-        rc = _lib.load().yttm_encode_file_idtext(self._h, os.fsencode(path), os.fsencode(out), int(bos), int(eos), int(reverse), float(dropout_prob),
-                                                 int(chunk_bytes or 0), C.byref(nl), C.byref(ni), C.byref(nt), rep, len(rep), err, _lib.ERRLEN)
-        if rc != 0:
-            raise ValueError(err.value.decode(errors="replace"))
-        if report:
-            import json
-            return json.loads(rep.value.decode())
-        return nl.value, ni.value, nt.value
+        return self._file_to_text("yttm_encode_file_idtext", path, out, (int(bos), int(eos), int(reverse), float(dropout_prob)), chunk_bytes, report)
 
     def encode(self, sentences, output_type, bos, eos, reverse, dropout_prob):
-        if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
-            raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+        _check_dropout(dropout_prob)
         single = isinstance(sentences, str)
         if single:
             batch = [sentences]
@@ -462,9 +450,9 @@ class _Core:
     def decode_cli(self, ignore_ids, in_fd=0, out_fd=1):
         import sys
         sys.stdout.flush()
-        ign = np.ascontiguousarray(sorted(set(int(i) for i in (ignore_ids or ()))), dtype=np.int32)
+        ign, ign_p, n_ign = self._ignore(ignore_ids)
         err = _err()
-        rc = _lib.load().yttm_decode_cli(self._h, ign.ctypes.data_as(_lib.i32p), len(ign), in_fd, out_fd, err, _lib.ERRLEN)
+        rc = _lib.load().yttm_decode_cli(self._h, ign_p, n_ign, in_fd, out_fd, err, _lib.ERRLEN)
         if rc != 0:
             raise ValueError(err.value.decode())
 
@@ -601,8 +589,7 @@ class BPE:
         run's for unk_id, "" for <BOS>, <EOS> and a lone "▁"); with unit="byte" offsets into s.encode().  Needs no torch."""
         if unit not in ("char", "byte"):
             raise ValueError('unit must be "char" or "byte"')
-        if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
-            raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+        _check_dropout(dropout_prob)
         sentences = list(sentences)
         blob, offs = _pack(sentences)
         ids, off, spans = self.bpe_cython.encode_packed_spans(blob, offs, bos, eos, reverse, dropout_prob)

@@ -173,6 +173,34 @@ struct EventPair {
   }
 };
 
+// The kernel time of an entry that runs several stages: each stage reports into its own slot (next(): null where the caller did not ask), the
+// caller's *kernel_ms is 0 from the start and the sum of the stages that ran, in their order, at the end.
+struct StageClock {
+  double *const out;
+  double slot[4] = {0, 0, 0, 0};
+  int n = 0;
+  explicit StageClock(double *kernel_ms) : out(kernel_ms) {
+    if (out) *out = 0;
+  }
+  StageClock(const StageClock &) = delete;
+  StageClock &operator=(const StageClock &) = delete;
+  double *next() { return out ? &slot[n++] : nullptr; }
+  ~StageClock() {
+    if (!out) return;
+    double sum = slot[0];
+    for (int i = 1; i < n; i++) sum += slot[i];
+    *out = sum;
+  }
+};
+
+// What every device-resident entry holds while it works: the encoder's hooks bound to the thread, and lane 0 locked.
+struct Lane0 {
+  const CfgBind bind;
+  EncodeLane &d;
+  const std::lock_guard<std::mutex> lk;
+  explicit Lane0(EncoderDevice &D) : bind(D.cfg), d(D.lane[0]), lk(d.mu) {}
+};
+
 // body() -> Status on `device`; a GpuError thrown inside it becomes the call's status
 template <class F>
 Status on_device(int device, F &&body) {
@@ -210,6 +238,30 @@ Status decode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, i
                       const int32_t *ignore_ids, unsigned long long n_ignore, unsigned long long *n_bytes, double *kernel_ms, bool newline);
 // The decimal text of the encode result pending on the lane (locked by the caller), left in the lane's text slot (k_idtext.h)
 Status idtext_on_lane(EncodeLane &d, int device, unsigned long long *n_text_bytes, double *kernel_ms);
+
+// The two-pass sequence of a kernel family that measures, then writes (k_decode.h, k_subword.h, k_idtext.h), on the lane (locked by the caller,
+// on its device): launch(false) leaves n counts, scan_counts turns them into off[n + 1] and synchronises, check() may end the call there with
+// its status (what launch(false) copied to the host is here), room(total) makes the output's room, launch(true) writes, and the stream is
+// synchronised.  *kernel_ms (may be null): from the first launch to the last.  Returns the total in *total.  Throws GpuError.
+template <class Launch, class Check, class Room>
+Status two_pass_on_lane(EncodeLane &d, unsigned long long n, DevBuf<uint32_t> &counts, DevBuf<unsigned long long> &off, double *kernel_ms,
+                        unsigned long long *total_out, Launch &&launch, Check &&check, Room &&room) {
+  counts.grow((size_t)n);
+  off.grow((size_t)n + 1);
+  EventPair ev(d.st, kernel_ms != nullptr);
+  ev.start();
+  launch(false);
+  const unsigned long long total = scan_counts(d, counts, n, off);  // (syncs)
+  const Status checked = check();
+  if (!checked.ok()) return checked;
+  room(total);
+  launch(true);
+  ev.stop();
+  HIP_CHECK(hipStreamSynchronize(d.st));
+  if (kernel_ms) *kernel_ms = ev.elapsed_ms();
+  *total_out = total;
+  return Status();
+}
 
 // Host arrays of a large batch cross the link through the trainer's pinned chunks (gpu_ctx.cpp staged_transfer; 1e7 sentences are 1.3 GB up
 // and 1.2 GB down: a plain copy from / to pageable memory moves them at a fraction of the link's rate, and the first touch of a freshly

@@ -10,111 +10,136 @@
 
 namespace yttm {
 
-// The text of every id, once per encoder: from the host's id_to_subword(id, replace_space = true), so that the device path cannot drift from
-// the host path.  An id the host function refuses is marked (DEC_INVALID) and reported by the device path the same way.
-static void decode_table(const BaseEncoder &enc, EncoderDevice &D) {
+// A piece table, once per encoder (under dec_mu; `ready` is the table's own flag): build(blob, off, per_id) fills the text of every id back to
+// back, off[V + 1] and -- where the table has a third array, dst_per_id -- a word per id, by the table's own per-id rules.  All are allocated,
+// then copied, and handed to the encoder together once every copy is there: a failure on the way leaves the encoder as it was.
+template <class Build>
+static void table_once(const BaseEncoder &enc, EncoderDevice &D, bool &ready, DevBuf<uint8_t> &dst_blob, DevBuf<uint32_t> &dst_off,
+                       DevBuf<uint32_t> *dst_per_id, Build &&build) {
   std::lock_guard<std::mutex> lk(D.dec_mu);
-  if (D.dec_ready) return;
-  const int V = enc.vocab_size();
-  std::string blob, piece;
-  std::vector<uint32_t> off((size_t)V + 1, 0);
-  for (int id = 0; id < V; id++) {
-    if (blob.size() >= (size_t)DEC_INVALID) throw GpuError{"decode: the vocabulary's text does not fit 2 GB"};
-    off[(size_t)id] = (uint32_t)blob.size();
-    piece.clear();
-    bool ok = false;
-    try {
-      ok = enc.id_to_subword(id, &piece, true).ok();
-    } catch (const std::exception &) {
-    }
-    if (ok) blob += piece;
-    else off[(size_t)id] |= DEC_INVALID;
-  }
-  if (blob.size() >= (size_t)DEC_INVALID) throw GpuError{"decode: the vocabulary's text does not fit 2 GB"};
-  off[(size_t)V] = (uint32_t)blob.size();
-  DevBuf<uint8_t> d_blob;  // (handed to the encoder once both are filled)
-  DevBuf<uint32_t> d_off;
+  if (ready) return;
+  std::string blob;
+  std::vector<uint32_t> off((size_t)enc.vocab_size() + 1, 0), per_id(dst_per_id ? (size_t)enc.vocab_size() : 0, 0);
+  build(blob, off, per_id);
+  DevBuf<uint8_t> d_blob;
+  DevBuf<uint32_t> d_off, d_per_id;
   d_blob.alloc(blob.size() + 1);
   d_off.alloc(off.size());
+  if (dst_per_id) d_per_id.alloc(per_id.size());
   if (!blob.empty()) HIP_CHECK(hipMemcpy(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
   HIP_CHECK(hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-  D.piece_blob = std::move(d_blob);
-  D.piece_off = std::move(d_off);
-  D.dec_vocab = (uint32_t)V;
-  D.dec_ready = true;
+  if (!per_id.empty()) HIP_CHECK(hipMemcpy(d_per_id, per_id.data(), per_id.size() * 4, hipMemcpyHostToDevice));
+  dst_blob = std::move(d_blob);
+  dst_off = std::move(d_off);
+  if (dst_per_id) *dst_per_id = std::move(d_per_id);
+  ready = true;
 }
 
-// measure -> scan -> write on the lane (locked by the caller).  n_flat: the ids the kernels walk (ragged: n_ids; padded: n_sent * stride).
-// newline (ragged input only): a '\n' behind every sentence, as decode_cli writes its lines.
-Status decode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, DecInput in, unsigned long long n_flat,
-                      const int32_t *ignore_ids, unsigned long long n_ignore, unsigned long long *n_bytes, double *kernel_ms, bool newline) {
+// The text of every id: from the host's id_to_subword(id, replace_space = true), so that the device path cannot drift from the host path.  An
+// id the host function refuses is marked (DEC_INVALID) and reported by the device path the same way.
+static void decode_table(const BaseEncoder &enc, EncoderDevice &D) {
+  table_once(enc, D, D.dec_ready, D.piece_blob, D.piece_off, nullptr, [&](std::string &blob, std::vector<uint32_t> &off, std::vector<uint32_t> &) {
+    const int V = enc.vocab_size();
+    std::string piece;
+    for (int id = 0; id < V; id++) {
+      if (blob.size() >= (size_t)DEC_INVALID) throw GpuError{"decode: the vocabulary's text does not fit 2 GB"};
+      off[(size_t)id] = (uint32_t)blob.size();
+      piece.clear();
+      bool ok = false;
+      try {
+        ok = enc.id_to_subword(id, &piece, true).ok();
+      } catch (const std::exception &) {
+      }
+      if (ok) blob += piece;
+      else off[(size_t)id] |= DEC_INVALID;
+    }
+    if (blob.size() >= (size_t)DEC_INVALID) throw GpuError{"decode: the vocabulary's text does not fit 2 GB"};
+    off[(size_t)V] = (uint32_t)blob.size();
+    D.dec_vocab = (uint32_t)V;
+  });
+}
+
+// A text for n_sent sentences into the lane's text slot (dec; the lane locked by the caller): the slot is invalid from the first step on and
+// valid again only with the new text in it.  No sentence: an empty text, nothing is launched.  Else prepare() (tables, inputs), then the two
+// passes over dec.len / dec.off (two_pass_on_lane: launch, check) into dec.bytes, which has 16 bytes more than the text -- the writer's last
+// 16-byte store may reach past the end -- and must be 16-byte aligned.  `who` names the route in that message.
+template <class Prepare, class Launch, class Check>
+static Status text_on_lane(EncodeLane &d, int device, const char *who, unsigned long long n_sent, unsigned long long *n_bytes, double *kernel_ms,
+                           Prepare &&prepare, Launch &&launch, Check &&check) {
   return on_device(device, [&]() -> Status {
     d.dec.valid = false;
     if (n_bytes) *n_bytes = 0;
     if (kernel_ms) *kernel_ms = 0;
-    if (in.n_sent == 0) {
-      d.dec.n_sent = d.dec.n_bytes = 0;
-      d.dec.valid = true;
-      return Status();
+    unsigned long long total = 0;
+    if (n_sent) {
+      prepare();
+      const Status s = two_pass_on_lane(d, n_sent, d.dec.len, d.dec.off, kernel_ms, &total, launch, check, [&](unsigned long long need) {
+        d.dec.bytes.grow((size_t)need + 16);
+        if (((uintptr_t)d.dec.bytes.p & 15u) != 0) throw GpuError{std::string(who) + ": the output blob is not 16-byte aligned"};
+      });
+      if (!s.ok()) return s;
     }
-    decode_table(enc, D);
-    const DecTable tb{D.piece_blob, D.piece_off, D.dec_vocab};
-    DecIgnore ig{nullptr, nullptr, 0, 0};
-    if (n_ignore) {
-      const size_t words = ((size_t)D.dec_vocab + 31) / 32 + 1;
-      std::vector<uint32_t> host(words, 0);
-      std::vector<int32_t> extra;
-      for (unsigned long long i = 0; i < n_ignore; i++) {
-        const int32_t id = ignore_ids[i];
-        if ((uint32_t)id < D.dec_vocab) host[(uint32_t)id >> 5] |= 1u << ((uint32_t)id & 31u);
-        else extra.push_back(id);
-      }
-      std::sort(extra.begin(), extra.end());
-      extra.erase(std::unique(extra.begin(), extra.end()), extra.end());
-      for (int32_t id : extra) host.push_back((uint32_t)id);
-      d.dec.ign.grow(host.size());
-      HIP_CHECK(hipMemcpy(d.dec.ign, host.data(), host.size() * 4, hipMemcpyHostToDevice));  // (the lane's stream is idle; the vector ends with this call)
-      ig = DecIgnore{d.dec.ign, (const int32_t *)(d.dec.ign + words), (uint32_t)extra.size(), 1u};
-    }
-    d.dec.len.grow((size_t)in.n_sent);
-    d.dec.off.grow((size_t)in.n_sent + 1);
-    EventPair ev(d.st, kernel_ms != nullptr);
-    ev.start();
-    HIP_CHECK(hipMemsetAsync(d.dec.misc, 0xff, 8, d.st));
-    launch_decode_measure(in, tb, ig, n_flat, d.dec.len, d.dec.misc, d.st, newline);
-    unsigned long long bad = ~0ull;
-    HIP_CHECK(hipMemcpyAsync(&bad, d.dec.misc, 8, hipMemcpyDeviceToHost, d.st));
-    const unsigned long long total = scan_counts(d, d.dec.len, in.n_sent, d.dec.off);  // (syncs: `bad` is here)
-    if (bad != ~0ull) {  // the first id, in sentence order then position order, that is neither ignored nor valid: the host path's message
-      int32_t id = 0;
-      HIP_CHECK(hipMemcpyAsync(&id, in.ids + bad, 4, hipMemcpyDeviceToHost, d.st));
-      HIP_CHECK(hipStreamSynchronize(d.st));
-      std::string piece;
-      Status st = enc.id_to_subword(id, &piece, true);
-      return st.ok() ? Status(1, "decode: no text for id " + std::to_string(id)) : st;
-    }
-    d.dec.bytes.grow((size_t)total + 16);
-    if (((uintptr_t)d.dec.bytes.p & 15u) != 0) throw GpuError{"decode: the output blob is not 16-byte aligned"};
-    launch_decode_write(in, tb, ig, n_flat, d.dec.off, d.dec.bytes, d.st, newline);
-    ev.stop();
-    HIP_CHECK(hipStreamSynchronize(d.st));
-    if (kernel_ms) *kernel_ms = ev.elapsed_ms();
-    d.dec.n_sent = in.n_sent;
+    d.dec.n_sent = n_sent;
     d.dec.n_bytes = total;
     d.dec.valid = true;
     if (n_bytes) *n_bytes = total;
     return Status();
   });
 }
+static Status no_check() { return Status(); }
+
+// measure -> scan -> write on the lane (locked by the caller).  n_flat: the ids the kernels walk (ragged: n_ids; padded: n_sent * stride).
+// newline (ragged input only): a '\n' behind every sentence, as decode_cli writes its lines.
+Status decode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, DecInput in, unsigned long long n_flat,
+                      const int32_t *ignore_ids, unsigned long long n_ignore, unsigned long long *n_bytes, double *kernel_ms, bool newline) {
+  DecTable tb{};
+  DecIgnore ig{nullptr, nullptr, 0, 0};
+  unsigned long long bad = ~0ull;  // the measure pass's smallest flat index of an invalid id
+  return text_on_lane(
+      d, device, "decode", in.n_sent, n_bytes, kernel_ms,
+      [&] {
+        decode_table(enc, D);
+        tb = DecTable{D.piece_blob, D.piece_off, D.dec_vocab};
+        if (!n_ignore) return;
+        const size_t words = ((size_t)D.dec_vocab + 31) / 32 + 1;
+        std::vector<uint32_t> host(words, 0);
+        std::vector<int32_t> extra;
+        for (unsigned long long i = 0; i < n_ignore; i++) {
+          const int32_t id = ignore_ids[i];
+          if ((uint32_t)id < D.dec_vocab) host[(uint32_t)id >> 5] |= 1u << ((uint32_t)id & 31u);
+          else extra.push_back(id);
+        }
+        std::sort(extra.begin(), extra.end());
+        extra.erase(std::unique(extra.begin(), extra.end()), extra.end());
+        for (int32_t id : extra) host.push_back((uint32_t)id);
+        d.dec.ign.grow(host.size());
+        HIP_CHECK(hipMemcpy(d.dec.ign, host.data(), host.size() * 4, hipMemcpyHostToDevice));  // (the lane's stream is idle; the vector ends with this call)
+        ig = DecIgnore{d.dec.ign, (const int32_t *)(d.dec.ign + words), (uint32_t)extra.size(), 1u};
+      },
+      [&](bool write) {
+        if (!write) HIP_CHECK(hipMemsetAsync(d.dec.misc, 0xff, 8, d.st));
+        launch_decode(write, newline, in, tb, ig, n_flat, d.dec.len, d.dec.misc, d.dec.off, d.dec.bytes, d.st);
+        if (!write) HIP_CHECK(hipMemcpyAsync(&bad, d.dec.misc, 8, hipMemcpyDeviceToHost, d.st));  // (here once the scan has synchronised)
+      },
+      [&]() -> Status {
+        if (bad == ~0ull) return Status();
+        // the first id, in sentence order then position order, that is neither ignored nor valid: the host path's message
+        int32_t id = 0;
+        HIP_CHECK(hipMemcpyAsync(&id, in.ids + bad, 4, hipMemcpyDeviceToHost, d.st));
+        HIP_CHECK(hipStreamSynchronize(d.st));
+        std::string piece;
+        const Status st = enc.id_to_subword(id, &piece, true);
+        return st.ok() ? Status(1, "decode: no text for id " + std::to_string(id)) : st;
+      });
+}
 
 Status BaseEncoder::decode_device(const void *d_ids, const void *d_offsets, unsigned long long n_sent, unsigned long long n_ids, const int32_t *ignore_ids,
                                   unsigned long long n_ignore, unsigned long long *n_bytes, double *kernel_ms) const {
   if (!dev_) return Status(2, "encoder has no device state");
   if (n_sent && !d_offsets) return Status(2, "decode_device: no offsets");
-  const CfgBind bind(dev_->cfg);
-  std::lock_guard<std::mutex> lk(dev_->lane[0].mu);
+  const Lane0 l(*dev_);
   const DecInput in{(const int32_t *)d_ids, (const unsigned long long *)d_offsets, nullptr, 0, 0, n_sent};
-  return decode_on_lane(*this, *dev_, dev_->lane[0], device_, in, n_ids, ignore_ids, n_ignore, n_bytes, kernel_ms, false);
+  return decode_on_lane(*this, *dev_, l.d, device_, in, n_ids, ignore_ids, n_ignore, n_bytes, kernel_ms, false);
 }
 
 Status BaseEncoder::decode_device_padded(const void *d_ids, unsigned long long n_sent, unsigned long long width, unsigned long long row_stride,
@@ -124,17 +149,15 @@ Status BaseEncoder::decode_device_padded(const void *d_ids, unsigned long long n
   if (row_stride < width) return Status(2, "decode_device_padded: row_stride is smaller than width");
   if (row_stride == 0) row_stride = 1;  // (width 0: rows without ids)
   if (n_sent > (~0ull >> 1) / row_stride) return Status(2, "decode_device_padded: the matrix is too large");
-  const CfgBind bind(dev_->cfg);
-  std::lock_guard<std::mutex> lk(dev_->lane[0].mu);
+  const Lane0 l(*dev_);
   const DecInput in{(const int32_t *)d_ids, nullptr, (const int32_t *)d_lengths, width, row_stride, n_sent};
-  return decode_on_lane(*this, *dev_, dev_->lane[0], device_, in, n_sent * row_stride, ignore_ids, n_ignore, n_bytes, kernel_ms, false);
+  return decode_on_lane(*this, *dev_, l.d, device_, in, n_sent * row_stride, ignore_ids, n_ignore, n_bytes, kernel_ms, false);
 }
 
 Status BaseEncoder::fetch_decode_result(char *bytes, unsigned long long *out_off, unsigned long long n_sent) const {
   if (!dev_) return Status(2, "fetch_decode_result: no matching result");
-  const CfgBind bind(dev_->cfg);
-  EncodeLane &d = dev_->lane[0];
-  std::lock_guard<std::mutex> lk(d.mu);
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
   if (!d.dec.valid || n_sent != d.dec.n_sent) return Status(2, "fetch_decode_result: no matching result");
   return on_device(device_, [&]() -> Status {
     if (n_sent == 0) { if (out_off) out_off[0] = 0; return Status(); }
@@ -147,40 +170,45 @@ Status BaseEncoder::fetch_decode_result(char *bytes, unsigned long long *out_off
 
 Status BaseEncoder::copy_decode_result(void *d_bytes, void *d_out_off, unsigned long long n_sent) const {
   if (!dev_) return Status(2, "copy_decode_result: no matching result");
-  const CfgBind bind(dev_->cfg);
-  EncodeLane &d = dev_->lane[0];
-  std::lock_guard<std::mutex> lk(d.mu);
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
   if (!d.dec.valid || n_sent != d.dec.n_sent) return Status(2, "copy_decode_result: no matching result");
   return copy_out_device(device_, d, d_bytes, d.dec.bytes, (size_t)d.dec.n_bytes, d_out_off, d.dec.off, n_sent);
 }
 
 Status BaseEncoder::copy_encode_result(void *d_ids, void *d_out_off, unsigned long long n_sent) const {
   if (!dev_) return Status(2, "copy_encode_result: no matching result");
-  const CfgBind bind(dev_->cfg);
-  EncodeLane &d = dev_->lane[0];
-  std::lock_guard<std::mutex> lk(d.mu);
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
   if (n_sent != d.res.n_sent) return Status(2, "copy_encode_result: no matching result");
   return copy_out_device(device_, d, d_ids, d.res.ids, (size_t)d.res.n_ids * 4, d_out_off, d.res.off, n_sent);
+}
+
+// The longest row of the encode result pending on the lane (k_enc_longest; synchronises), checked against the width of a padded copy: a row
+// that does not fit is the reference's message, code 1 -- nothing is truncated, and nothing was written.
+static Status longest_row_fits(EncodeLane &d, unsigned long long n_sent, unsigned long long width, unsigned long long *need, unsigned long long *longest) {
+  HIP_CHECK(hipMemsetAsync(d.res.misc, 0, 8, d.st));
+  launch_enc_longest(d.res.off, n_sent, (unsigned int *)d.res.misc.p, d.st);
+  HIP_CHECK(hipMemcpyAsync(need, d.res.misc, 8, hipMemcpyDeviceToHost, d.st));
+  HIP_CHECK(hipStreamSynchronize(d.st));
+  if (longest) *longest = *need;
+  if (*need > width)
+    return Status(1, "width is smaller than the longest row. Current value: width = " + std::to_string(width) + "; longest = " + std::to_string(*need) + ";");
+  return Status();
 }
 
 Status BaseEncoder::copy_encode_padded(void *d_matrix, void *d_lengths, unsigned long long n_sent, unsigned long long width, int32_t pad_value,
                                        unsigned long long *longest) const {
   if (longest) *longest = 0;
   if (!dev_) return Status(2, "copy_encode_padded: no matching result");
-  const CfgBind bind(dev_->cfg);
-  EncodeLane &d = dev_->lane[0];
-  std::lock_guard<std::mutex> lk(d.mu);
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
   if (n_sent != d.res.n_sent) return Status(2, "copy_encode_padded: no matching result");
   if (n_sent == 0) return Status();
   return on_device(device_, [&]() -> Status {
-    HIP_CHECK(hipMemsetAsync(d.res.misc, 0, 8, d.st));
-    launch_enc_longest(d.res.off, n_sent, (unsigned int *)d.res.misc.p, d.st);
     unsigned long long need = 0;
-    HIP_CHECK(hipMemcpyAsync(&need, d.res.misc, 8, hipMemcpyDeviceToHost, d.st));
-    HIP_CHECK(hipStreamSynchronize(d.st));
-    if (longest) *longest = need;
-    if (need > width)  // nothing is truncated, and nothing was written
-      return Status(1, "width is smaller than the longest row. Current value: width = " + std::to_string(width) + "; longest = " + std::to_string(need) + ";");
+    const Status fit = longest_row_fits(d, n_sent, width, &need, longest);
+    if (!fit.ok()) return fit;
     if (need > 0x7fffffffull) return Status(2, "copy_encode_padded: a row is too long for int32 lengths");
     if (!d_matrix || !d_lengths) return Status(2, "copy_encode_padded: no output");
     if (((uintptr_t)d_matrix & 3u) != 0) return Status(2, "copy_encode_padded: the matrix must be 4-byte aligned");
@@ -197,123 +225,65 @@ Status BaseEncoder::copy_encode_padded(void *d_matrix, void *d_lengths, unsigned
 // The text of every id, once per encoder: from the host's id_to_subword(id, replace_space = false), so that the device path cannot drift from
 // the host path ("▁" stays, the special ids give their names, a hole of the id space is "").
 static void subword_table(const BaseEncoder &enc, EncoderDevice &D) {
-  std::lock_guard<std::mutex> lk(D.dec_mu);
-  if (D.sub_ready) return;
-  const int V = enc.vocab_size();
-  std::string blob, piece;
-  std::vector<uint32_t> off((size_t)V + 1, 0), units((size_t)V, 0);
-  const SpecialTokens &sp = enc.bpe_state.special_tokens;
-  for (int id = 0; id < V; id++) {
-    off[(size_t)id] = (uint32_t)blob.size();
-    piece.clear();
-    if (enc.id_to_subword(id, &piece, false).ok()) blob += piece;
-    if (blob.size() >= (size_t)DEC_INVALID) throw GpuError{"subword: the vocabulary's text does not fit 2 GB"};
-    // the units the id covers (k_spans.h): an unknown run is one; a special token none; else the piece's code points other than U+2581
-    if (id == sp.unk_id) {
-      units[(size_t)id] = 1;
-    } else if (id != sp.pad_id && id != sp.bos_id && id != sp.eos_id) {
-      uint32_t n = 0;
-      for (size_t i = 0; i < piece.size(); i++) {
-        if (((uint8_t)piece[i] & 0xC0u) == 0x80u) continue;
-        if (piece.compare(i, 3, "\xe2\x96\x81") != 0) n++;
+  // units: the units an id covers (k_spans.h), counted beside the pieces
+  table_once(enc, D, D.sub_ready, D.sub_blob, D.sub_off, &D.sub_units, [&](std::string &blob, std::vector<uint32_t> &off, std::vector<uint32_t> &units) {
+    const int V = enc.vocab_size();
+    std::string piece;
+    const SpecialTokens &sp = enc.bpe_state.special_tokens;
+    for (int id = 0; id < V; id++) {
+      off[(size_t)id] = (uint32_t)blob.size();
+      piece.clear();
+      if (enc.id_to_subword(id, &piece, false).ok()) blob += piece;
+      if (blob.size() >= (size_t)DEC_INVALID) throw GpuError{"subword: the vocabulary's text does not fit 2 GB"};
+      // an unknown run is one unit; a special token none; else the piece's code points other than U+2581
+      if (id == sp.unk_id) {
+        units[(size_t)id] = 1;
+      } else if (id != sp.pad_id && id != sp.bos_id && id != sp.eos_id) {
+        uint32_t n = 0;
+        for (size_t i = 0; i < piece.size(); i++) {
+          if (((uint8_t)piece[i] & 0xC0u) == 0x80u) continue;
+          if (piece.compare(i, 3, "\xe2\x96\x81") != 0) n++;
+        }
+        units[(size_t)id] = n;
       }
-      units[(size_t)id] = n;
     }
-  }
-  off[(size_t)V] = (uint32_t)blob.size();
-  DevBuf<uint8_t> d_blob;  // (handed to the encoder once both are filled)
-  DevBuf<uint32_t> d_off, d_units;
-  d_blob.alloc(blob.size() + 1);
-  d_off.alloc(off.size());
-  d_units.alloc(units.size());
-  if (!blob.empty()) HIP_CHECK(hipMemcpy(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-  if (!units.empty()) HIP_CHECK(hipMemcpy(d_units, units.data(), units.size() * 4, hipMemcpyHostToDevice));
-  D.sub_blob = std::move(d_blob);
-  D.sub_off = std::move(d_off);
-  D.sub_units = std::move(d_units);
-  D.sub_ready = true;
+    off[(size_t)V] = (uint32_t)blob.size();
+  });
+}
+
+static SubInput pending_input(const BaseEncoder &enc, const EncodeLane &d, const void *d_text, const void *d_soff, bool reverse) {
+  return SubInput{(const uint8_t *)d_text, (const unsigned long long *)d_soff, d.res.ids, d.res.off, d.res.n_sent, (int32_t)enc.bpe_state.special_tokens.unk_id,
+                  reverse ? 1 : 0};
 }
 
 Status format_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_text, const void *d_soff, bool reverse,
                       unsigned long long *n_text_bytes, double *kernel_ms) {
-  return on_device(device, [&]() -> Status {
-    d.dec.valid = false;
-    if (n_text_bytes) *n_text_bytes = 0;
-    if (kernel_ms) *kernel_ms = 0;
-    const unsigned long long n_sent = d.res.n_sent;
-    if (n_sent == 0) {
-      d.dec.n_sent = d.dec.n_bytes = 0;
-      d.dec.valid = true;
-      return Status();
-    }
-    subword_table(enc, D);
-    const DecTable tb{D.sub_blob, D.sub_off, (uint32_t)enc.vocab_size()};
-    const SubInput in{(const uint8_t *)d_text, (const unsigned long long *)d_soff, d.res.ids, d.res.off, n_sent, (int32_t)enc.bpe_state.special_tokens.unk_id,
-                      reverse ? 1 : 0};
-    d.dec.len.grow((size_t)n_sent);
-    d.dec.off.grow((size_t)n_sent + 1);
-    EventPair ev(d.st, kernel_ms != nullptr);
-    ev.start();
-    launch_subword_measure(D.m, in, tb, d.res.n_ids, d.dec.len, d.st);
-    const unsigned long long total = scan_counts(d, d.dec.len, n_sent, d.dec.off);  // (syncs)
-    d.dec.bytes.grow((size_t)total + 16);
-    if (((uintptr_t)d.dec.bytes.p & 15u) != 0) throw GpuError{"subword: the output blob is not 16-byte aligned"};
-    launch_subword_write(D.m, in, tb, d.res.n_ids, d.dec.off, d.dec.bytes, d.st);
-    ev.stop();
-    HIP_CHECK(hipStreamSynchronize(d.st));
-    if (kernel_ms) *kernel_ms = ev.elapsed_ms();
-    d.dec.n_sent = n_sent;
-    d.dec.n_bytes = total;
-    d.dec.valid = true;
-    if (n_text_bytes) *n_text_bytes = total;
-    return Status();
-  });
+  const SubInput in = pending_input(enc, d, d_text, d_soff, reverse);
+  return text_on_lane(
+      d, device, "subword", in.n_sent, n_text_bytes, kernel_ms, [&] { subword_table(enc, D); },
+      [&](bool write) {
+        launch_subword(write, D.m, in, DecTable{D.sub_blob, D.sub_off, (uint32_t)enc.vocab_size()}, d.res.n_ids, d.dec.len, d.dec.off, d.dec.bytes, d.st);
+      },
+      no_check);
 }
 
 // ---- id text (k_idtext.h) ------------------------------------------------------------------------------------------------------------------
 // The text `yttm encode --output_type id` prints for the encode result pending on the lane (utils.h:92-103: every id and a space, a newline per
 // sentence), left in the lane's text slot like the SUBWORD text; the ids stay pending.  Needs no input text and no table.
 Status idtext_on_lane(EncodeLane &d, int device, unsigned long long *n_text_bytes, double *kernel_ms) {
-  return on_device(device, [&]() -> Status {
-    d.dec.valid = false;
-    if (n_text_bytes) *n_text_bytes = 0;
-    if (kernel_ms) *kernel_ms = 0;
-    const unsigned long long n_sent = d.res.n_sent;
-    if (n_sent == 0) {
-      d.dec.n_sent = d.dec.n_bytes = 0;
-      d.dec.valid = true;
-      return Status();
-    }
-    d.dec.len.grow((size_t)n_sent);
-    d.dec.off.grow((size_t)n_sent + 1);
-    EventPair ev(d.st, kernel_ms != nullptr);
-    ev.start();
-    launch_idprint_measure(d.res.ids, d.res.off, n_sent, d.res.n_ids, d.dec.len, d.st);
-    const unsigned long long total = scan_counts(d, d.dec.len, n_sent, d.dec.off);  // (syncs)
-    d.dec.bytes.grow((size_t)total + 16);
-    if (((uintptr_t)d.dec.bytes.p & 15u) != 0) throw GpuError{"idtext: the output blob is not 16-byte aligned"};
-    launch_idprint_write(d.res.ids, d.res.off, n_sent, d.res.n_ids, d.dec.off, d.dec.bytes, d.st);
-    ev.stop();
-    HIP_CHECK(hipStreamSynchronize(d.st));
-    if (kernel_ms) *kernel_ms = ev.elapsed_ms();
-    d.dec.n_sent = n_sent;
-    d.dec.n_bytes = total;
-    d.dec.valid = true;
-    if (n_text_bytes) *n_text_bytes = total;
-    return Status();
-  });
+  return text_on_lane(
+      d, device, "idtext", d.res.n_sent, n_text_bytes, kernel_ms, [] {},
+      [&](bool write) { launch_idprint(write, d.res.ids, d.res.off, d.res.n_sent, d.res.n_ids, d.dec.len, d.dec.off, d.dec.bytes, d.st); }, no_check);
 }
 
 Status BaseEncoder::idtext_device(unsigned long long n_sent, unsigned long long *n_text_bytes, double *kernel_ms) const {
   if (n_text_bytes) *n_text_bytes = 0;
-  if (kernel_ms) *kernel_ms = 0;
+  StageClock ms(kernel_ms);
   if (!dev_) return Status(1, "idtext_device: no matching encode result");
-  const CfgBind bind(dev_->cfg);
-  EncodeLane &d = dev_->lane[0];
-  std::lock_guard<std::mutex> lk(d.mu);
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
   if (n_sent != d.res.n_sent) return Status(1, "idtext_device: no matching encode result");  // (before any work: a pending text stays)
-  return idtext_on_lane(d, device_, n_text_bytes, kernel_ms);
+  return idtext_on_lane(d, device_, n_text_bytes, ms.next());
 }
 
 Status BaseEncoder::subword_device(const void *d_bytes, const void *d_offsets, unsigned long long n_sent, unsigned long long total_bytes,
@@ -321,21 +291,16 @@ Status BaseEncoder::subword_device(const void *d_bytes, const void *d_offsets, u
                                    unsigned long long *n_ids, unsigned long long *n_text_bytes, double *kernel_ms) const {
   if (n_ids) *n_ids = 0;
   if (n_text_bytes) *n_text_bytes = 0;
-  if (kernel_ms) *kernel_ms = 0;
-  const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work: nothing that was pending is touched)
+  StageClock ms(kernel_ms);
+  const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work, and before the device check: nothing that was pending is touched)
   if (!tokens.ok()) return tokens;
   if (!dev_) return Status(2, "encoder has no device state");
   if (n_sent && !d_offsets) return Status(2, "subword_device: no offsets");
-  const CfgBind bind(dev_->cfg);
-  EncodeLane &d = dev_->lane[0];
-  std::lock_guard<std::mutex> lk(d.mu);
-  const bool timed = kernel_ms != nullptr;
-  double ms_enc = 0, ms_fmt = 0;
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
   Status s = encode_on_lane(*this, *dev_, d, device_, d_bytes, d_offsets, n_sent, total_bytes, max_sentence_bytes, bos, eos, reverse, dropout_prob, n_ids,
-                            timed ? &ms_enc : nullptr);
-  if (!s.ok()) return s;
-  s = format_on_lane(*this, *dev_, d, device_, d_bytes, d_offsets, reverse, n_text_bytes, timed ? &ms_fmt : nullptr);
-  if (kernel_ms) *kernel_ms = ms_enc + ms_fmt;
+                            ms.next());
+  if (s.ok()) s = format_on_lane(*this, *dev_, d, device_, d_bytes, d_offsets, reverse, n_text_bytes, ms.next());
   return s;
 }
 
@@ -354,8 +319,7 @@ Status spans_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, in
       return Status();
     }
     subword_table(enc, D);
-    const SubInput in{(const uint8_t *)d_text, (const unsigned long long *)d_soff, d.res.ids, d.res.off, n_sent, (int32_t)enc.bpe_state.special_tokens.unk_id,
-                      reverse ? 1 : 0};
+    const SubInput in = pending_input(enc, d, d_text, d_soff, reverse);
     d.sp.spans.grow((size_t)d.res.n_ids * 2 + 2);
     EventPair ev(d.st, kernel_ms != nullptr);
     ev.start();
@@ -378,30 +342,24 @@ Status BaseEncoder::spans_device(const void *d_bytes, const void *d_offsets, uns
                                  unsigned long long max_sentence_bytes, bool bos, bool eos, bool reverse, double dropout_prob, unsigned long long *n_ids,
                                  double *kernel_ms) const {
   if (n_ids) *n_ids = 0;
-  if (kernel_ms) *kernel_ms = 0;
-  const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work: nothing that was pending is touched)
+  StageClock ms(kernel_ms);
+  const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work, and before the device check: nothing that was pending is touched)
   if (!tokens.ok()) return tokens;
   if (!dev_) return Status(2, "encoder has no device state");
   if (n_sent && !d_offsets) return Status(2, "spans_device: no offsets");
-  const CfgBind bind(dev_->cfg);
-  EncodeLane &d = dev_->lane[0];
-  std::lock_guard<std::mutex> lk(d.mu);
-  const bool timed = kernel_ms != nullptr;
-  double ms_enc = 0, ms_sp = 0;
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
   Status s = encode_on_lane(*this, *dev_, d, device_, d_bytes, d_offsets, n_sent, total_bytes, max_sentence_bytes, bos, eos, reverse, dropout_prob, n_ids,
-                            timed ? &ms_enc : nullptr);
-  if (!s.ok()) return s;
-  s = spans_on_lane(*this, *dev_, d, device_, d_bytes, d_offsets, reverse, timed ? &ms_sp : nullptr);
-  if (kernel_ms) *kernel_ms = ms_enc + ms_sp;
+                            ms.next());
+  if (s.ok()) s = spans_on_lane(*this, *dev_, d, device_, d_bytes, d_offsets, reverse, ms.next());
   return s;
 }
 
 Status BaseEncoder::take_spans(void *spans, unsigned long long n_sent, bool to_device) const {
   const char *who = to_device ? "copy_spans: no matching result" : "fetch_spans: no matching result";
   if (!dev_) return Status(1, who);
-  const CfgBind bind(dev_->cfg);
-  EncodeLane &d = dev_->lane[0];
-  std::lock_guard<std::mutex> lk(d.mu);
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
   if (!d.sp.valid || n_sent != d.sp.n_sent || n_sent != d.res.n_sent || d.sp.n_ids != d.res.n_ids) return Status(1, who);
   if (!spans || !d.sp.n_ids) return Status();
   if (to_device) return copy_out_device(device_, d, spans, d.sp.spans, (size_t)d.sp.n_ids * 8, nullptr, nullptr, n_sent);
@@ -415,20 +373,14 @@ Status BaseEncoder::take_spans(void *spans, unsigned long long n_sent, bool to_d
 Status BaseEncoder::copy_spans_padded(void *d_matrix, unsigned long long n_sent, unsigned long long width, unsigned long long *longest) const {
   if (longest) *longest = 0;
   if (!dev_) return Status(1, "copy_spans_padded: no matching result");
-  const CfgBind bind(dev_->cfg);
-  EncodeLane &d = dev_->lane[0];
-  std::lock_guard<std::mutex> lk(d.mu);
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
   if (!d.sp.valid || n_sent != d.sp.n_sent || n_sent != d.res.n_sent || d.sp.n_ids != d.res.n_ids) return Status(1, "copy_spans_padded: no matching result");
   if (n_sent == 0) return Status();
   return on_device(device_, [&]() -> Status {
-    HIP_CHECK(hipMemsetAsync(d.res.misc, 0, 8, d.st));
-    launch_enc_longest(d.res.off, n_sent, (unsigned int *)d.res.misc.p, d.st);
     unsigned long long need = 0;
-    HIP_CHECK(hipMemcpyAsync(&need, d.res.misc, 8, hipMemcpyDeviceToHost, d.st));
-    HIP_CHECK(hipStreamSynchronize(d.st));
-    if (longest) *longest = need;
-    if (need > width)  // nothing is truncated, and nothing was written
-      return Status(1, "width is smaller than the longest row. Current value: width = " + std::to_string(width) + "; longest = " + std::to_string(need) + ";");
+    const Status fit = longest_row_fits(d, n_sent, width, &need, longest);
+    if (!fit.ok()) return fit;
     if (n_sent > (~0ull >> 4) / (width ? width : 1)) return Status(2, "copy_spans_padded: the matrix is too large");
     if (!width) return Status();
     if (!d_matrix) return Status(2, "copy_spans_padded: no output");

@@ -59,9 +59,8 @@ Status BaseEncoder::lines_device(const void *d_text, unsigned long long n_bytes,
   if (longest) *longest = 0;
   if (!dev_) return Status(2, "encoder has no device state");
   if (n_bytes && !d_text) return Status(2, "lines_device: no text");
-  const CfgBind bind(dev_->cfg);
-  EncodeLane &d = dev_->lane[0];
-  std::lock_guard<std::mutex> lk(d.mu);
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
   return on_device(device_, [&]() -> Status {
     split_on_lane(d, d_text, n_bytes, n_lines, longest, kernel_ms);
     return Status();
@@ -72,9 +71,8 @@ Status BaseEncoder::lines_device(const void *d_text, unsigned long long n_bytes,
 Status BaseEncoder::take_lines(void *offsets, unsigned long long n_lines, bool to_device) const {
   const char *who = to_device ? "copy_lines: no matching result" : "fetch_lines: no matching result";
   if (!dev_) return Status(2, who);
-  const CfgBind bind(dev_->cfg);
-  EncodeLane &d = dev_->lane[0];
-  std::lock_guard<std::mutex> lk(d.mu);
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
   if (!d.ln.valid || n_lines != d.ln.n_lines) return Status(2, who);
   if (!offsets) return Status();
   if (to_device) return copy_out_device(device_, d, nullptr, nullptr, 0, offsets, d.ln.off, n_lines);
@@ -106,16 +104,12 @@ Status BaseEncoder::encode_text_device(const void *d_text, unsigned long long n_
                                        unsigned long long *n_lines, unsigned long long *n_ids, double *kernel_ms) const {
   if (n_lines) *n_lines = 0;
   if (n_ids) *n_ids = 0;
-  if (kernel_ms) *kernel_ms = 0;
-  if (!dev_) return Status(2, "encoder has no device state");
+  StageClock ms(kernel_ms);
+  if (!dev_) return Status(2, "encoder has no device state");  // (this entry alone asks for the device first: bos / eos are checked on the lane)
   if (n_bytes && !d_text) return Status(2, "encode_text_device: no text");
-  const CfgBind bind(dev_->cfg);
-  std::lock_guard<std::mutex> lk(dev_->lane[0].mu);
-  double ms_split = 0, ms_enc = 0;
-  Status s = encode_text_on_lane(*this, *dev_, dev_->lane[0], device_, d_text, n_bytes, bos, eos, reverse, dropout_prob, n_lines, n_ids,
-                                 kernel_ms ? &ms_split : nullptr, kernel_ms ? &ms_enc : nullptr);
-  if (kernel_ms) *kernel_ms = ms_split + ms_enc;
-  return s;
+  const Lane0 l(*dev_);
+  double *const ms_split = ms.next(), *const ms_enc = ms.next();
+  return encode_text_on_lane(*this, *dev_, l.d, device_, d_text, n_bytes, bos, eos, reverse, dropout_prob, n_lines, n_ids, ms_split, ms_enc);
 }
 
 // split, encode, then the SUBWORD text of those ids (host_decode.cpp): the lines' offsets are the formatter's sentence offsets
@@ -132,18 +126,15 @@ Status BaseEncoder::subword_text_device(const void *d_text, unsigned long long n
   if (n_lines) *n_lines = 0;
   if (n_ids) *n_ids = 0;
   if (n_text_bytes) *n_text_bytes = 0;
-  if (kernel_ms) *kernel_ms = 0;
-  const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work: nothing that was pending is touched)
+  StageClock ms(kernel_ms);
+  const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work, and before the device check: nothing that was pending is touched)
   if (!tokens.ok()) return tokens;
   if (!dev_) return Status(2, "encoder has no device state");
   if (n_bytes && !d_text) return Status(2, "subword_text_device: no text");
-  const CfgBind bind(dev_->cfg);
-  std::lock_guard<std::mutex> lk(dev_->lane[0].mu);
-  double ms_split = 0, ms_enc = 0, ms_fmt = 0;
-  Status s = subword_text_on_lane(*this, *dev_, dev_->lane[0], device_, d_text, n_bytes, bos, eos, reverse, dropout_prob, n_lines, n_ids, n_text_bytes,
-                                  kernel_ms ? &ms_split : nullptr, kernel_ms ? &ms_enc : nullptr, kernel_ms ? &ms_fmt : nullptr);
-  if (kernel_ms) *kernel_ms = ms_split + ms_enc + ms_fmt;
-  return s;
+  const Lane0 l(*dev_);
+  double *const ms_split = ms.next(), *const ms_enc = ms.next(), *const ms_fmt = ms.next();
+  return subword_text_on_lane(*this, *dev_, l.d, device_, d_text, n_bytes, bos, eos, reverse, dropout_prob, n_lines, n_ids, n_text_bytes, ms_split, ms_enc,
+                              ms_fmt);
 }
 
 // split, encode, then the byte spans of those ids (host_decode.cpp): a sentence is a line with its newline, the spans count from the line's start
@@ -151,19 +142,16 @@ Status BaseEncoder::spans_text_device(const void *d_text, unsigned long long n_b
                                       unsigned long long *n_lines, unsigned long long *n_ids, double *kernel_ms) const {
   if (n_lines) *n_lines = 0;
   if (n_ids) *n_ids = 0;
-  if (kernel_ms) *kernel_ms = 0;
-  const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work: nothing that was pending is touched)
+  StageClock ms(kernel_ms);
+  const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work, and before the device check: nothing that was pending is touched)
   if (!tokens.ok()) return tokens;
   if (!dev_) return Status(2, "encoder has no device state");
   if (n_bytes && !d_text) return Status(2, "spans_text_device: no text");
-  const CfgBind bind(dev_->cfg);
-  EncodeLane &d = dev_->lane[0];
-  std::lock_guard<std::mutex> lk(d.mu);
-  double ms_split = 0, ms_enc = 0, ms_sp = 0;
-  Status s = encode_text_on_lane(*this, *dev_, d, device_, d_text, n_bytes, bos, eos, reverse, dropout_prob, n_lines, n_ids, kernel_ms ? &ms_split : nullptr,
-                                 kernel_ms ? &ms_enc : nullptr);
-  if (s.ok()) s = spans_on_lane(*this, *dev_, d, device_, d_text, d.ln.off, reverse, kernel_ms ? &ms_sp : nullptr);
-  if (kernel_ms) *kernel_ms = ms_split + ms_enc + ms_sp;
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
+  double *const ms_split = ms.next(), *const ms_enc = ms.next();
+  Status s = encode_text_on_lane(*this, *dev_, d, device_, d_text, n_bytes, bos, eos, reverse, dropout_prob, n_lines, n_ids, ms_split, ms_enc);
+  if (s.ok()) s = spans_on_lane(*this, *dev_, d, device_, d_text, d.ln.off, reverse, ms.next());
   return s;
 }
 
@@ -179,17 +167,12 @@ static Status parse_on_lane(EncodeLane &d, int device, const void *d_text, unsig
     if (n_ids_out) *n_ids_out = 0;
     if (kernel_ms) *kernel_ms = 0;
     if (n_lines == 0) return Status();
-    d.k5.counts.grow((size_t)n_lines);
-    d.res.off.grow((size_t)n_lines + 1);
-    EventPair ev(d.st, kernel_ms != nullptr);
-    ev.start();
-    launch_idparse_measure((const uint8_t *)d_text, d.ln.off, n_lines, n_bytes, d.k5.counts, d.st);
-    const unsigned long long total = scan_counts(d, d.k5.counts, n_lines, d.res.off);  // (syncs)
-    d.res.ids.grow((size_t)total + 1);
-    launch_idparse_write((const uint8_t *)d_text, d.ln.off, n_lines, n_bytes, d.res.off, d.res.ids, d.st);
-    ev.stop();
-    HIP_CHECK(hipStreamSynchronize(d.st));
-    if (kernel_ms) *kernel_ms = ev.elapsed_ms();
+    unsigned long long total = 0;
+    const Status s = two_pass_on_lane(
+        d, n_lines, d.k5.counts, d.res.off, kernel_ms, &total,
+        [&](bool write) { launch_idparse(write, (const uint8_t *)d_text, d.ln.off, n_lines, n_bytes, d.k5.counts, d.res.off, d.res.ids, d.st); },
+        [] { return Status(); }, [&](unsigned long long need) { d.res.ids.grow((size_t)need + 1); });
+    if (!s.ok()) return s;
     d.res.n_ids = total;
     if (n_ids_out) *n_ids_out = total;
     return Status();
@@ -226,15 +209,12 @@ Status BaseEncoder::ids_parse_device(const void *d_text, unsigned long long n_by
                                      double *kernel_ms) const {
   if (n_lines) *n_lines = 0;
   if (n_ids) *n_ids = 0;
-  if (kernel_ms) *kernel_ms = 0;
+  StageClock ms(kernel_ms);
   if (!dev_) return Status(2, "encoder has no device state");
   if (n_bytes && !d_text) return Status(2, "ids_parse_device: no text");
-  const CfgBind bind(dev_->cfg);
-  std::lock_guard<std::mutex> lk(dev_->lane[0].mu);
-  double ms_split = 0, ms_parse = 0;
-  const Status s = parse_text_on_lane(dev_->lane[0], device_, d_text, n_bytes, n_lines, n_ids, kernel_ms ? &ms_split : nullptr, kernel_ms ? &ms_parse : nullptr);
-  if (kernel_ms) *kernel_ms = ms_split + ms_parse;
-  return s;
+  const Lane0 l(*dev_);
+  double *const ms_split = ms.next(), *const ms_parse = ms.next();
+  return parse_text_on_lane(l.d, device_, d_text, n_bytes, n_lines, n_ids, ms_split, ms_parse);
 }
 
 Status BaseEncoder::decode_text_device(const void *d_text, unsigned long long n_bytes, const int32_t *ignore_ids, unsigned long long n_ignore,
@@ -242,17 +222,13 @@ Status BaseEncoder::decode_text_device(const void *d_text, unsigned long long n_
   if (n_lines) *n_lines = 0;
   if (n_ids) *n_ids = 0;
   if (n_text_bytes) *n_text_bytes = 0;
-  if (kernel_ms) *kernel_ms = 0;
+  StageClock ms(kernel_ms);
   if (!dev_) return Status(2, "encoder has no device state");
   if (n_bytes && !d_text) return Status(2, "decode_text_device: no text");
   if (n_ignore && !ignore_ids) return Status(2, "decode_text_device: no ignore_ids");
-  const CfgBind bind(dev_->cfg);
-  std::lock_guard<std::mutex> lk(dev_->lane[0].mu);
-  double ms_split = 0, ms_parse = 0, ms_dec = 0;
-  const Status s = decode_text_on_lane(*this, *dev_, dev_->lane[0], device_, d_text, n_bytes, ignore_ids, n_ignore, n_lines, n_ids, n_text_bytes,
-                                       kernel_ms ? &ms_split : nullptr, kernel_ms ? &ms_parse : nullptr, kernel_ms ? &ms_dec : nullptr);
-  if (kernel_ms) *kernel_ms = ms_split + ms_parse + ms_dec;
-  return s;
+  const Lane0 l(*dev_);
+  double *const ms_split = ms.next(), *const ms_parse = ms.next(), *const ms_dec = ms.next();
+  return decode_text_on_lane(*this, *dev_, l.d, device_, d_text, n_bytes, ignore_ids, n_ignore, n_lines, n_ids, n_text_bytes, ms_split, ms_parse, ms_dec);
 }
 
 // ---- a file of any size ------------------------------------------------------------------------------------------------------------------
@@ -354,6 +330,70 @@ struct Growing {
   }
   ~Growing() { free(p); }
 };
+
+double secs_since(std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); }
+
+// What the file entries share: the input, the upload leg of run_two_lanes and the record of the piece in flight on each lane -- upload(i) fills
+// it, the entry's work(i) adds the counts (and kernel times in milliseconds: the split, two more named by the route), its download(i) reads it.
+struct FilePieces {
+  struct Piece {
+    unsigned long long pos = 0, bytes = 0, n_lines = 0, n_ids = 0, n_text = 0;
+    double ms_split = 0, ms_a = 0, ms_b = 0;
+  } piece[2];
+  const std::string &path;
+  EncoderDevice *const dev;
+  const int device;
+  const unsigned long long piece_bytes;
+  const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+  Fd in;
+  struct stat sb;
+  unsigned long long size = 0, next_pos = 0;
+  double s_up = 0;
+  FilePieces(const std::string &input, EncoderDevice *D, int dev_id, unsigned long long want)
+      : path(input), dev(D), device(dev_id), piece_bytes(want ? want : FILE_PIECE_DEFAULT) {}
+  Status open_input() {
+    in.fd = open(path.c_str(), O_RDONLY | O_CLOEXEC);
+    if (in.fd < 0 || fstat(in.fd, &sb) != 0) return Status(1, "Failed to open file: " + path + " (" + strerror(errno) + ")");
+    if (!S_ISREG(sb.st_mode)) return Status(1, "Failed to read file: " + path + " is not a regular file");
+    size = (unsigned long long)sb.st_size;
+    return Status();
+  }
+  Status upload(size_t i, bool *exhausted) {
+    const unsigned long long pos = next_pos;
+    if (pos >= size) { *exhausted = true; return Status(); }
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned long long end = size;
+    const Status st = upload_piece(in.fd, path, device, dev->lane[i & 1], pos, piece_bytes, size, &end);
+    if (!st.ok()) return st;
+    s_up += secs_since(t0);
+    piece[i & 1] = Piece{};
+    piece[i & 1].pos = pos;
+    piece[i & 1].bytes = end - pos;
+    next_pos = end;
+    return Status();
+  }
+  // the report of a finished call: text_bytes only for the text routes, `stages` the route's own kernel seconds behind the encode's
+  std::string report(size_t n_pieces, unsigned long long lines, unsigned long long ids, const unsigned long long *text_bytes, double s_split, double s_enc,
+                     std::initializer_list<std::pair<const char *, double>> stages, double s_down) const {
+    char tmp[512];
+    snprintf(tmp, sizeof tmp, "{\"pieces\": %zu, \"piece_bytes\": %llu, \"bytes\": %llu, \"lines\": %llu, \"ids\": %llu, ", n_pieces, piece_bytes, size, lines, ids);
+    std::string r = tmp;
+    if (text_bytes) {
+      snprintf(tmp, sizeof tmp, "\"text_bytes\": %llu, ", *text_bytes);
+      r += tmp;
+    }
+    snprintf(tmp, sizeof tmp, "\"seconds_total\": %.6f, \"seconds_read_upload\": %.6f, \"seconds_split\": %.6f, \"seconds_encode\": %.6f", secs_since(t_begin), s_up,
+             s_split, s_enc);
+    r += tmp;
+    for (const auto &st : stages) {
+      if (!st.first) continue;
+      snprintf(tmp, sizeof tmp, ", \"%s\": %.6f", st.first, st.second);
+      r += tmp;
+    }
+    snprintf(tmp, sizeof tmp, ", \"seconds_download_write\": %.6f}", s_down);
+    return r + tmp;
+  }
+};
 }  // namespace
 
 Status BaseEncoder::encode_file(const std::string &path, const char *out_prefix, bool bos, bool eos, bool reverse, double dropout_prob,
@@ -367,15 +407,11 @@ Status BaseEncoder::encode_file(const std::string &path, const char *out_prefix,
   if (!tokens.ok()) return tokens;
   if (!dev_) return Status(2, "encoder has no device state");
   if (!out_prefix && (!ids_out || !off_out)) return Status(2, "encode_file: no output");
-  if (!piece_bytes) piece_bytes = FILE_PIECE_DEFAULT;
-  const auto t_begin = std::chrono::steady_clock::now();
-  auto secs = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
-  Fd in, out_ids, out_off;
-  in.fd = open(path.c_str(), O_RDONLY | O_CLOEXEC);
-  struct stat sb;
-  if (in.fd < 0 || fstat(in.fd, &sb) != 0) return Status(1, "Failed to open file: " + path + " (" + strerror(errno) + ")");
-  if (!S_ISREG(sb.st_mode)) return Status(1, "Failed to read file: " + path + " is not a regular file");
-  const unsigned long long size = (unsigned long long)sb.st_size;
+  FilePieces fp(path, dev_, device_, piece_bytes);
+  const Status opened = fp.open_input();
+  if (!opened.ok()) return opened;
+  const unsigned long long size = fp.size;
+  Fd out_ids, out_off;
   std::string ids_path, off_path;
   if (out_prefix) {
     ids_path = std::string(out_prefix) + ".ids";
@@ -391,38 +427,23 @@ Status BaseEncoder::encode_file(const std::string &path, const char *out_prefix,
   EncoderDevice *dev = dev_;
   std::lock_guard<std::mutex> lk0(dev->lane[0].mu), lk1(dev->lane[1].mu);  // (lane 0 first, always: nobody else waits for two lanes)
 
-  struct Piece {
-    unsigned long long pos = 0, bytes = 0, n_lines = 0, n_ids = 0;
-  } piece[2];  // of the item in flight on each lane: upload(i) fills it, work(i) adds the counts, download(i) reads it
-  double s_up = 0, s_split = 0, s_enc = 0, s_down = 0;
+  double s_split = 0, s_enc = 0, s_down = 0;
   Growing<int32_t> ids;
   Growing<unsigned long long> off;
-  unsigned long long next_pos = 0, lines_total = 0, ids_total = 0;  // (the upload leg's; the download leg's two)
+  unsigned long long lines_total = 0, ids_total = 0;  // (the download leg's)
 
-  auto upload = [&](size_t i, bool *exhausted) {
-    const unsigned long long pos = next_pos;
-    if (pos >= size) { *exhausted = true; return Status(); }
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned long long end = size;
-    const Status st = upload_piece(in.fd, path, device, dev->lane[i & 1], pos, piece_bytes, size, &end);
-    if (!st.ok()) return st;
-    s_up += secs(t0);
-    piece[i & 1] = Piece{pos, end - pos, 0, 0};
-    next_pos = end;
-    return Status();
-  };
+  auto upload = [&](size_t i, bool *exhausted) { return fp.upload(i, exhausted); };
   auto work = [&](size_t i) {
-    Piece &p = piece[i & 1];
+    FilePieces::Piece &p = fp.piece[i & 1];
     EncodeLane &d = dev->lane[i & 1];
-    double ms_split = 0;
     const auto t0 = std::chrono::steady_clock::now();
-    const Status st = encode_text_on_lane(*this, *dev, d, device, d.in.bytes, p.bytes, bos, eos, reverse, dropout_prob, &p.n_lines, &p.n_ids, &ms_split, nullptr);
-    s_split += ms_split * 1e-3;
-    s_enc += secs(t0) - ms_split * 1e-3;
+    const Status st = encode_text_on_lane(*this, *dev, d, device, d.in.bytes, p.bytes, bos, eos, reverse, dropout_prob, &p.n_lines, &p.n_ids, &p.ms_split, nullptr);
+    s_split += p.ms_split * 1e-3;
+    s_enc += secs_since(t0) - p.ms_split * 1e-3;
     return st;
   };
   auto download = [&](size_t i) {
-    const Piece p = piece[i & 1];
+    const FilePieces::Piece p = fp.piece[i & 1];
     const auto t0 = std::chrono::steady_clock::now();
     EncodeLane &d = dev->lane[i & 1];
     const unsigned long long ids_base = ids_total, lines_base = lines_total;
@@ -461,7 +482,7 @@ Status BaseEncoder::encode_file(const std::string &path, const char *out_prefix,
     }
     ids_total += p.n_ids;
     lines_total += p.n_lines;
-    s_down += secs(t0);
+    s_down += secs_since(t0);
     return Status();
   };
   size_t n_pieces = 0;
@@ -489,14 +510,7 @@ Status BaseEncoder::encode_file(const std::string &path, const char *out_prefix,
   }
   if (n_lines_out) *n_lines_out = lines_total;
   if (n_ids_out) *n_ids_out = ids_total;
-  if (report) {
-    char tmp[512];
-    snprintf(tmp, sizeof tmp,
-             "{\"pieces\": %zu, \"piece_bytes\": %llu, \"bytes\": %llu, \"lines\": %llu, \"ids\": %llu, \"seconds_total\": %.6f, \"seconds_read_upload\": %.6f, "
-             "\"seconds_split\": %.6f, \"seconds_encode\": %.6f, \"seconds_download_write\": %.6f}",
-             n_pieces, piece_bytes, size, lines_total, ids_total, secs(t_begin), s_up, s_split, s_enc, s_down);
-    *report = tmp;
-  }
+  if (report) *report = fp.report(n_pieces, lines_total, ids_total, nullptr, s_split, s_enc, {}, s_down);
   return Status();
 }
 
@@ -505,15 +519,12 @@ Status BaseEncoder::encode_file(const std::string &path, const char *out_prefix,
 // behind the text of the pieces before it.  Three routes share it: the SUBWORD formatter and the id printer behind the encode, and the decode
 // of a file of decimal ids.
 namespace {
-struct PieceWork {  // what `work` reports for one piece: counts, and kernel times in milliseconds (split; two more, named by the route)
-  unsigned long long n_lines = 0, n_ids = 0, n_text = 0;
-  double ms_split = 0, ms_a = 0, ms_b = 0;
-};
 struct TextRoute {
   const char *who;           // for run_two_lanes' messages
-  const char *key_a, *key_b;  // report keys of ms_a, ms_b ("seconds_...")
+  const char *key_a, *key_b;  // report keys of a piece's ms_a, ms_b ("seconds_..."; key_b may be null)
   bool has_encode;            // the wall time of `work` beyond the three kernel times is the encode's ("seconds_encode"; else it is 0)
 };
+using PieceWork = FilePieces::Piece;
 using PieceFn = std::function<Status(EncodeLane &d, unsigned long long bytes, PieceWork *w)>;
 
 Status file_to_text(EncoderDevice *dev, int device, const TextRoute &route, const std::string &path, const std::string &out_path, unsigned long long piece_bytes,
@@ -521,15 +532,11 @@ Status file_to_text(EncoderDevice *dev, int device, const TextRoute &route, cons
                     std::string *report) {
   if (!dev) return Status(2, "encoder has no device state");
   if (out_path.empty()) return Status(1, "Failed to open file for writing: no output path");
-  if (!piece_bytes) piece_bytes = FILE_PIECE_DEFAULT;
-  const auto t_begin = std::chrono::steady_clock::now();
-  auto secs = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
-  Fd in, out;
-  in.fd = open(path.c_str(), O_RDONLY | O_CLOEXEC);
-  struct stat sb;
-  if (in.fd < 0 || fstat(in.fd, &sb) != 0) return Status(1, "Failed to open file: " + path + " (" + strerror(errno) + ")");
-  if (!S_ISREG(sb.st_mode)) return Status(1, "Failed to read file: " + path + " is not a regular file");
-  const unsigned long long size = (unsigned long long)sb.st_size;
+  FilePieces fp(path, dev, device, piece_bytes);
+  const Status opened = fp.open_input();
+  if (!opened.ok()) return opened;
+  const struct stat &sb = fp.sb;
+  Fd out;
   // (opened without O_TRUNC, emptied only once it is known not to be the input itself: the output may be longer than the input it would overwrite)
   out.fd = open(out_path.c_str(), O_WRONLY | O_CREAT | O_CLOEXEC, 0644);
   struct stat ob;
@@ -540,44 +547,29 @@ Status file_to_text(EncoderDevice *dev, int device, const TextRoute &route, cons
   const CfgBind bind(C);
   std::lock_guard<std::mutex> lk0(dev->lane[0].mu), lk1(dev->lane[1].mu);  // (lane 0 first, always: nobody else waits for two lanes)
 
-  struct Piece {
-    unsigned long long pos = 0, bytes = 0;
-    PieceWork w;
-  } piece[2];  // of the item in flight on each lane: upload(i) fills it, work(i) adds the counts, download(i) reads it
-  double s_up = 0, s_split = 0, s_enc = 0, s_a = 0, s_b = 0, s_down = 0;
-  unsigned long long next_pos = 0, lines_total = 0, ids_total = 0, text_total = 0;  // (the upload leg's; the download leg's three)
+  double s_split = 0, s_enc = 0, s_a = 0, s_b = 0, s_down = 0;
+  unsigned long long lines_total = 0, ids_total = 0, text_total = 0;  // (the download leg's)
 
-  auto upload = [&](size_t i, bool *exhausted) {
-    const unsigned long long pos = next_pos;
-    if (pos >= size) { *exhausted = true; return Status(); }
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned long long end = size;
-    const Status st = upload_piece(in.fd, path, device, dev->lane[i & 1], pos, piece_bytes, size, &end);
-    if (!st.ok()) return st;
-    s_up += secs(t0);
-    piece[i & 1] = Piece{pos, end - pos, PieceWork{}};
-    next_pos = end;
-    return Status();
-  };
+  auto upload = [&](size_t i, bool *exhausted) { return fp.upload(i, exhausted); };
   auto work = [&](size_t i) {
-    Piece &p = piece[i & 1];
+    PieceWork &p = fp.piece[i & 1];
     const auto t0 = std::chrono::steady_clock::now();
-    const Status st = work_piece(dev->lane[i & 1], p.bytes, &p.w);
-    s_split += p.w.ms_split * 1e-3;
-    s_a += p.w.ms_a * 1e-3;
-    s_b += p.w.ms_b * 1e-3;
-    if (route.has_encode) s_enc += secs(t0) - (p.w.ms_split + p.w.ms_a + p.w.ms_b) * 1e-3;
+    const Status st = work_piece(dev->lane[i & 1], p.bytes, &p);
+    s_split += p.ms_split * 1e-3;
+    s_a += p.ms_a * 1e-3;
+    s_b += p.ms_b * 1e-3;
+    if (route.has_encode) s_enc += secs_since(t0) - (p.ms_split + p.ms_a + p.ms_b) * 1e-3;
     return st;
   };
   auto download = [&](size_t i) {
-    const Piece p = piece[i & 1];
+    const PieceWork p = fp.piece[i & 1];
     const auto t0 = std::chrono::steady_clock::now();
     EncodeLane &d = dev->lane[i & 1];
     const unsigned long long text_base = text_total;
     std::atomic<bool> write_ok{true};
     try {
-      if (p.w.n_text)
-        staged_transfer(device, d.dec.bytes.p, p.w.n_text, false, [&](void *chunk, unsigned long long o, size_t len) {
+      if (p.n_text)
+        staged_transfer(device, d.dec.bytes.p, p.n_text, false, [&](void *chunk, unsigned long long o, size_t len) {
           if (!pwrite_all(out.fd, chunk, len, text_base + o)) { write_ok.store(false); return false; }
           return true;
         }, nullptr, ENC_CHUNK);
@@ -585,10 +577,10 @@ Status file_to_text(EncoderDevice *dev, int device, const TextRoute &route, cons
       if (!write_ok.load()) return Status(1, "Failed to write file: " + out_path);
       throw;
     }
-    text_total += p.w.n_text;
-    ids_total += p.w.n_ids;
-    lines_total += p.w.n_lines;
-    s_down += secs(t0);
+    text_total += p.n_text;
+    ids_total += p.n_ids;
+    lines_total += p.n_lines;
+    s_down += secs_since(t0);
     return Status();
   };
   size_t n_pieces = 0;
@@ -600,20 +592,7 @@ Status file_to_text(EncoderDevice *dev, int device, const TextRoute &route, cons
   if (n_lines_out) *n_lines_out = lines_total;
   if (n_ids_out) *n_ids_out = ids_total;
   if (n_text_out) *n_text_out = text_total;
-  if (report) {
-    char tmp[768];
-    snprintf(tmp, sizeof tmp,
-             "{\"pieces\": %zu, \"piece_bytes\": %llu, \"bytes\": %llu, \"lines\": %llu, \"ids\": %llu, \"text_bytes\": %llu, \"seconds_total\": %.6f, "
-             "\"seconds_read_upload\": %.6f, \"seconds_split\": %.6f, \"seconds_encode\": %.6f, \"%s\": %.6f",
-             n_pieces, piece_bytes, size, lines_total, ids_total, text_total, secs(t_begin), s_up, s_split, s_enc, route.key_a, s_a);
-    *report = tmp;
-    if (route.key_b) {
-      snprintf(tmp, sizeof tmp, ", \"%s\": %.6f", route.key_b, s_b);
-      *report += tmp;
-    }
-    snprintf(tmp, sizeof tmp, ", \"seconds_download_write\": %.6f}", s_down);
-    *report += tmp;
-  }
+  if (report) *report = fp.report(n_pieces, lines_total, ids_total, &text_total, s_split, s_enc, {{route.key_a, s_a}, {route.key_b, s_b}}, s_down);
   return Status();
 }
 }  // namespace

@@ -20,50 +20,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "yttm_device.h"
+#include "k_textout.h"
 #include "yttm_kernels.h"
 
 namespace yttm {
 
-constexpr int DEC_TILE = 2048;          // bytes of LDS staging per wavefront
-constexpr int DEC_SEG = DEC_TILE - 16;  // most bytes staged at once: up to 15 bytes of an unfinished 16-byte unit stay in front of them
-
 __device__ inline unsigned long long dec_bpos(const DecInput &in, unsigned long long s) { return in.offsets ? in.offsets[s] : s * in.stride; }
-
-// The staged bytes mirror out[base .. base + fill): base is a multiple of 16; the first `head` bytes of the tile belong to the group before
-// this one (another wavefront writes them) and are never stored.
-struct DecStage {
-  uint8_t *tile;
-  uint8_t *out;
-  unsigned long long base;
-  uint32_t fill, head;
-  // stores every complete 16-byte unit; the rest (< 16 bytes) moves to the front of the tile
-  __device__ void flush_units() {
-    const uint32_t full = fill >> 4;
-    if (!full) return;
-    const uint32_t lane = (uint32_t)lane_id();
-    uint32_t u0 = 0;
-    if (head) {  // the group's first unit is shared with the group before: bytes
-      if (lane >= head && lane < 16u) out[base + lane] = tile[lane];
-      u0 = 1;
-      head = 0;
-    }
-    for (uint32_t u = u0 + lane; u < full; u += 64) *reinterpret_cast<uint4 *>(out + base + 16ull * u) = *reinterpret_cast<const uint4 *>(tile + 16u * u);
-    const uint32_t rem = fill & 15u;
-    const uint8_t v = lane < rem ? tile[16u * full + lane] : (uint8_t)0;
-    wave_sync();
-    if (lane < rem) tile[lane] = v;
-    wave_sync();
-    base += 16ull * full;
-    fill = rem;
-  }
-  // end of a group: the unfinished unit is shared with the next group: bytes
-  __device__ void flush_tail() {
-    const uint32_t lane = (uint32_t)lane_id();
-    if (lane >= head && lane < fill) out[base + lane] = tile[lane];
-    wave_sync();
-  }
-};
 
 // NL (ragged input only): a '\n' behind every sentence, as decode_cli writes its lines -- out_len[s] counts it, the write pass puts the newlines of
 // the sentences that END at a position (every boundary but the group's first one; empty sentences: several) in front of that position's piece,
@@ -79,25 +41,17 @@ __global__ __launch_bounds__(BLOCK) void k_decode(DecInput in, DecTable tb, DecI
   __shared__ unsigned long long s_bad[NWAVES];
   const int w = uni((int)(threadIdx.x >> 6));
   const uint32_t lane = (uint32_t)lane_id();
-  const unsigned long long n_groups = (in.n_sent + group - 1) / group;
-  const unsigned long long n_waves = (unsigned long long)gridDim.x * NWAVES;
   unsigned long long bad = ~0ull;
-  for (unsigned long long g = (unsigned long long)blockIdx.x * NWAVES + (unsigned long long)w; g < n_groups; g += n_waves) {
-    const unsigned long long g0 = g * group, g1 = g0 + group < in.n_sent ? g0 + group : in.n_sent;
+  for (WaveGroups wg(in.n_sent, group, w); wg.more(); wg.next()) {
+    const unsigned long long g0 = wg.g0(), g1 = wg.g1();
     const unsigned long long k0 = uni64(dec_bpos(in, g0)), k1 = uni64(dec_bpos(in, g1));
     unsigned long long sc = g0;              // the first boundary (start of sentence sc) that lies at or behind `base`
     unsigned long long rowb = g0, colb = 0;  // (PADDED) row and column of `base`
     uint32_t run = 0, open_p = 0;            // (measure) output bytes of the group before this step; ... before the start of the sentence still open
     bool carry = false;                      // the sentence that is open at `base` has a kept id already
     uint32_t nl_left = NL ? (uint32_t)(g1 - g0) : 0u;  // (NL, write) newlines of the group not yet staged
-    DecStage stg{};
-    stg.tile = s_tile[WRITE ? w : 0];
-    if (WRITE) {
-      const unsigned long long cursor = uni64(out_off[g0]);
-      stg.out = out;
-      stg.base = cursor & ~15ull;
-      stg.head = stg.fill = (uint32_t)(cursor & 15ull);
-    }
+    TileWriter stg(s_tile[WRITE ? w : 0], lane);
+    if (WRITE) stg.open(out, uni64(out_off[g0]));
     for (unsigned long long base = k0;; base += 64) {
       const bool last = base + 64 >= k1;
       // ---- this lane's id
@@ -195,10 +149,10 @@ __global__ __launch_bounds__(BLOCK) void k_decode(DecInput in, DecTable tb, DecI
       } else {
         sc += hits;
         if (total <= (uint32_t)DEC_SEG) {
-          if (NL) for (uint32_t b = 0; b < nlb; b++) stg.tile[stg.fill + x - nlb + b] = (uint8_t)'\n';
-          for (uint32_t b = 0; b < len; b++) stg.tile[stg.fill + x + b] = tb.blob[src + b];
-          wave_sync();
-          stg.fill += total;
+          uint8_t *const nlp = stg.at(x - nlb), *const p = nlp + nlb;  // (every step ends with flush_units: DEC_SEG more bytes fit)
+          if (NL) for (uint32_t b = 0; b < nlb; b++) nlp[b] = (uint8_t)'\n';
+          for (uint32_t b = 0; b < len; b++) p[b] = tb.blob[src + b];
+          stg.commit(total);
           stg.flush_units();
         } else {  // pieces that do not fit the tile together (a word of thousands of chars can be one piece): one by one, the wave copies a piece
           unsigned long long pm = ballot_b(len + nlb > 0);
@@ -206,21 +160,8 @@ __global__ __launch_bounds__(BLOCK) void k_decode(DecInput in, DecTable tb, DecI
             const int l = __ffsll((long long)pm) - 1;
             pm &= pm - 1;
             const uint32_t plen = uni(__shfl(len, l)), psrc = uni(__shfl(src, l));
-            if (NL) {  // (at most 64 newlines a step, behind fewer than 16 staged bytes)
-              const uint32_t pnl = uni(__shfl(nlb, l));
-              if (lane < pnl) stg.tile[stg.fill + lane] = (uint8_t)'\n';
-              wave_sync();
-              stg.fill += pnl;
-              stg.flush_units();
-            }
-            for (uint32_t done = 0; done < plen;) {
-              const uint32_t n = plen - done < (uint32_t)DEC_SEG ? plen - done : (uint32_t)DEC_SEG;
-              for (uint32_t b = lane; b < n; b += 64) stg.tile[stg.fill + b] = tb.blob[psrc + done + b];
-              wave_sync();
-              stg.fill += n;
-              stg.flush_units();
-              done += n;
-            }
+            if (NL) stg.append_run((uint8_t)'\n', uni(__shfl(nlb, l)));  // (at most 64 newlines a step)
+            stg.copy_piece(tb.blob + psrc, plen);
           }
         }
       }
@@ -239,13 +180,8 @@ __global__ __launch_bounds__(BLOCK) void k_decode(DecInput in, DecTable tb, DecI
         }
       }
     }
-    if (NL && WRITE && nl_left) {  // (fewer than 16 bytes are staged: every step ends with flush_units)
-      if (lane < nl_left) stg.tile[stg.fill + lane] = (uint8_t)'\n';
-      wave_sync();
-      stg.fill += nl_left;
-      stg.flush_units();
-    }
-    if (WRITE) stg.flush_tail();
+    if (NL && WRITE && nl_left) stg.append_run((uint8_t)'\n', nl_left);
+    if (WRITE) stg.close();
   }
   if (!WRITE) {
     for (int o = 32; o > 0; o >>= 1) {
@@ -262,22 +198,15 @@ __global__ __launch_bounds__(BLOCK) void k_decode(DecInput in, DecTable tb, DecI
   }
 }
 
-// sentences per group: about 256 ids, and in a large batch enough that a wavefront has a few groups, not thousands
-static unsigned int dec_group(const DecInput &in, unsigned long long n_flat) {
-  unsigned long long avg = n_flat / in.n_sent, grp = 256 / (avg ? avg : 1);
-  const unsigned long long many = in.n_sent / (256ull * 8 * NWAVES * 4);
-  if (grp < many) grp = many;
-  return (unsigned int)(grp < 1 ? 1 : grp > 64 ? 64 : grp);
-}
-static void launch_decode_any(bool write, bool newline, const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, uint32_t *out_len,
-                              unsigned long long *bad_min, const unsigned long long *out_off, uint8_t *out, hipStream_t st) {
+// *bad_min must hold ~0 before the measure pass; each pass is given what it uses
+void launch_decode(bool write, bool newline, const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, uint32_t *out_len,
+                   unsigned long long *bad_min, const unsigned long long *out_off, uint8_t *out, hipStream_t st) {
   if (!in.n_sent) return;
-  const unsigned int group = dec_group(in, n_flat);
-  const unsigned long long n_groups = (in.n_sent + group - 1) / group;
-  unsigned long long b = (n_groups + NWAVES - 1) / NWAVES;
-  if (b > 256 * 8) b = 256 * 8;
-  const dim3 grid((unsigned int)b), block(BLOCK);
+  const unsigned int group = group_size(in.n_sent, n_flat, 256, 64);  // (a group may hold any number of sentences: the boundaries are read 64 at a time)
+  const dim3 grid = grid_for_groups(in.n_sent, group), block(BLOCK);
   const bool padded = in.offsets == nullptr;
+  if (write) out_len = nullptr, bad_min = nullptr;
+  else out_off = nullptr, out = nullptr;
   if (newline) {  // (ragged only: the callers' inputs are the parser's)
     if (!write) hipLaunchKernelGGL((k_decode<false, false, true>), grid, block, 0, st, in, tb, ig, group, out_len, bad_min, out_off, out);
     else hipLaunchKernelGGL((k_decode<false, true, true>), grid, block, 0, st, in, tb, ig, group, out_len, bad_min, out_off, out);
@@ -287,14 +216,6 @@ static void launch_decode_any(bool write, bool newline, const DecInput &in, cons
   if (!write && padded) hipLaunchKernelGGL((k_decode<true, false>), grid, block, 0, st, in, tb, ig, group, out_len, bad_min, out_off, out);
   if (write && !padded) hipLaunchKernelGGL((k_decode<false, true>), grid, block, 0, st, in, tb, ig, group, out_len, bad_min, out_off, out);
   if (write && padded) hipLaunchKernelGGL((k_decode<true, true>), grid, block, 0, st, in, tb, ig, group, out_len, bad_min, out_off, out);
-}
-void launch_decode_measure(const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, uint32_t *out_len,
-                           unsigned long long *bad_min, hipStream_t st, bool newline) {
-  launch_decode_any(false, newline, in, tb, ig, n_flat, out_len, bad_min, nullptr, nullptr, st);
-}
-void launch_decode_write(const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, const unsigned long long *out_off,
-                         uint8_t *out, hipStream_t st, bool newline) {
-  launch_decode_any(true, newline, in, tb, ig, n_flat, nullptr, nullptr, out_off, out, st);
 }
 
 // ---- the encoder's result as a padded matrix -----------------------------------------------------------------------------------------
@@ -356,9 +277,7 @@ __global__ __launch_bounds__(BLOCK) void k_enc_pad(const int32_t *__restrict__ i
 
 void launch_enc_longest(const unsigned long long *out_off, unsigned long long n_sent, unsigned int *longest, hipStream_t st) {
   if (!n_sent) return;
-  unsigned long long b = (n_sent + BLOCK - 1) / BLOCK;
-  if (b > 256 * 8) b = 256 * 8;
-  hipLaunchKernelGGL(k_enc_longest, dim3((unsigned int)b), dim3(BLOCK), 0, st, out_off, n_sent, longest);
+  hipLaunchKernelGGL(k_enc_longest, grid_for(n_sent, BLOCK), dim3(BLOCK), 0, st, out_off, n_sent, longest);
 }
 // matrix: 4-byte aligned (the caller checks)
 void launch_enc_pad(const int32_t *ids, const unsigned long long *out_off, unsigned long long n_sent, unsigned long long width, int32_t pad_value,

@@ -1,6 +1,6 @@
 // k_idtext.h -- decimal id text on the device, both ways: the lines of a text -> the ids `while (ss >> x)` reads from each (k_idparse), and the
 // pending encode result -> the text `yttm encode --output_type id` prints (k_idprint).  Included at the end of k_encode.hip (behind k_subword.h:
-// the staging tile is DecStage, the groups of the printer are sub_group's).
+// the groups of the printer are its lane_group's).
 //
 // replaces: the parse of BaseEncoder::decode(const vector<string>&, ...) bpe.cpp:1863-1873 (`while (ss >> x) ids.push_back(x)` per line, restated
 // in decode_cli, host_cli.cpp) and the id formatting of encode_cli bpe.cpp:1942-2014 (utils.h:92-103: every id followed by one space, then
@@ -28,8 +28,8 @@
 // Limits: a line below 4 G numbers; a single line is walked by one wavefront.
 //
 // ---- the printer.  Per sentence every id in decimal ('-' for a negative one, -2147483648 included) followed by one space, then '\n'.
-// measure -> scan -> write as k_subword.h, a lane per id of one sentence at a time; the digits go to the 2 KB LDS tile (DecStage), the tile to
-// the output in aligned 16-byte stores.  Algorithmic bytes: read 4 K + 8 (S + 1), written B_out + 8 (S + 1).
+// measure -> scan -> write as k_subword.h, a lane per id of one sentence at a time; the digits go through the tile writer
+// (k_textout.h).  Algorithmic bytes: read 4 K + 8 (S + 1), written B_out + 8 (S + 1).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -47,10 +47,8 @@ __global__ __launch_bounds__(BLOCK) void k_idparse(const uint8_t *__restrict__ t
   const int w = uni((int)(threadIdx.x >> 6));
   const uint32_t lane = (uint32_t)lane_id();
   const unsigned long long lt = lanemask_lt(), le = lt | (1ull << lane);
-  const unsigned long long n_groups = (n_lines + group - 1) / group;
-  const unsigned long long n_waves = (unsigned long long)gridDim.x * NWAVES;
-  for (unsigned long long g = (unsigned long long)blockIdx.x * NWAVES + (unsigned long long)w; g < n_groups; g += n_waves) {
-    const unsigned long long g0 = g * group, g1 = g0 + group < n_lines ? g0 + group : n_lines;
+  for (WaveGroups wg(n_lines, group, w); wg.more(); wg.next()) {
+    const unsigned long long g0 = wg.g0(), g1 = wg.g1();
     const unsigned long long k0 = uni64(loff[g0]), k1 = uni64(loff[g1]);
     // what crosses a step; a group starts behind a newline (or at the text's start): all clear
     bool c_digit = false, c_neg = false, c_fail = false;
@@ -128,31 +126,14 @@ __global__ __launch_bounds__(BLOCK) void k_idparse(const uint8_t *__restrict__ t
   }
 }
 
-static unsigned int idparse_group(unsigned long long n_lines, unsigned long long n_bytes) {
-  // lines per group: about 4 KB of text, in a large text enough that a wavefront has a few groups, not thousands
-  unsigned long long avg = n_bytes / n_lines, grp = 4096 / (avg ? avg : 1);
-  const unsigned long long many = n_lines / (256ull * 8 * NWAVES * 4);
-  if (grp < many) grp = many;
-  return (unsigned int)(grp < 1 ? 1 : grp > (1u << 20) ? (1u << 20) : grp);
-}
-static void launch_idparse_any(bool write, const uint8_t *text, const unsigned long long *loff, unsigned long long n_lines, unsigned long long n_bytes,
-                               uint32_t *count, const unsigned long long *out_off, int32_t *ids, hipStream_t st) {
+// each pass is given what it uses
+void launch_idparse(bool write, const uint8_t *text, const unsigned long long *loff, unsigned long long n_lines, unsigned long long n_bytes, uint32_t *count,
+                    const unsigned long long *out_off, int32_t *ids, hipStream_t st) {
   if (!n_lines) return;
-  const unsigned int group = idparse_group(n_lines, n_bytes);
-  const unsigned long long n_groups = (n_lines + group - 1) / group;
-  unsigned long long b = (n_groups + NWAVES - 1) / NWAVES;
-  if (b > 256 * 8) b = 256 * 8;
-  const dim3 grid((unsigned int)b), block(BLOCK);
-  if (write) hipLaunchKernelGGL((k_idparse<true>), grid, block, 0, st, text, loff, n_lines, group, count, out_off, ids);
-  else hipLaunchKernelGGL((k_idparse<false>), grid, block, 0, st, text, loff, n_lines, group, count, out_off, ids);
-}
-void launch_idparse_measure(const uint8_t *text, const unsigned long long *loff, unsigned long long n_lines, unsigned long long n_bytes, uint32_t *count,
-                            hipStream_t st) {
-  launch_idparse_any(false, text, loff, n_lines, n_bytes, count, nullptr, nullptr, st);
-}
-void launch_idparse_write(const uint8_t *text, const unsigned long long *loff, unsigned long long n_lines, unsigned long long n_bytes,
-                          const unsigned long long *out_off, int32_t *ids, hipStream_t st) {
-  launch_idparse_any(true, text, loff, n_lines, n_bytes, nullptr, out_off, ids, st);
+  const unsigned int group = group_size(n_lines, n_bytes, 4096, 1u << 20);  // lines per group: about 4 KB of text
+  const dim3 grid = grid_for_groups(n_lines, group), block(BLOCK);
+  if (write) hipLaunchKernelGGL((k_idparse<true>), grid, block, 0, st, text, loff, n_lines, group, (uint32_t *)nullptr, out_off, ids);
+  else hipLaunchKernelGGL((k_idparse<false>), grid, block, 0, st, text, loff, n_lines, group, count, (const unsigned long long *)nullptr, (int32_t *)nullptr);
 }
 
 // ---- the printer -------------------------------------------------------------------------------------------------------------------------
@@ -171,24 +152,15 @@ __global__ __launch_bounds__(BLOCK) void k_idprint(const int32_t *__restrict__ i
   __shared__ __attribute__((aligned(16))) uint8_t s_tile[WRITE ? NWAVES : 1][WRITE ? DEC_TILE : 16];
   const int w = uni((int)(threadIdx.x >> 6));
   const uint32_t lane = (uint32_t)lane_id();
-  const unsigned long long n_groups = (n_sent + group - 1) / group;
-  const unsigned long long n_waves = (unsigned long long)gridDim.x * NWAVES;
-  for (unsigned long long g = (unsigned long long)blockIdx.x * NWAVES + (unsigned long long)w; g < n_groups; g += n_waves) {
-    const unsigned long long g0 = g * group, g1 = g0 + group < n_sent ? g0 + group : n_sent;
-    // the group's boundaries, a lane each (group < 64)
-    const unsigned long long my_i = g0 + lane <= g1 ? ioff[g0 + lane] : 0ull;
+  for (WaveGroups wg(n_sent, group, w); wg.more(); wg.next()) {
+    const unsigned long long g0 = wg.g0(), g1 = wg.g1();
+    const LaneBounds ib(ioff, g0, g1, lane);
     uint32_t my_len = 0;  // (measure) lane j: the output bytes of sentence g0 + j
-    DecStage stg{};
-    stg.tile = s_tile[WRITE ? w : 0];
-    if (WRITE) {
-      const unsigned long long cursor = uni64(out_off[g0]);
-      stg.out = out;
-      stg.base = cursor & ~15ull;
-      stg.head = stg.fill = (uint32_t)(cursor & 15ull);
-    }
+    TileWriter stg(s_tile[WRITE ? w : 0], lane);
+    if (WRITE) stg.open(out, uni64(out_off[g0]));
     for (unsigned long long sidx = g0; sidx < g1; sidx++) {
       const int j = (int)(sidx - g0);
-      const unsigned long long i0 = uni64(__shfl(my_i, j)), i1 = uni64(__shfl(my_i, j + 1));
+      const unsigned long long i0 = ib.at(j), i1 = ib.at(j + 1);
       uint32_t acc = 0;
       for (unsigned long long base = i0; base < i1; base += 64) {
         const unsigned long long k = base + lane;
@@ -204,59 +176,43 @@ __global__ __launch_bounds__(BLOCK) void k_idprint(const int32_t *__restrict__ i
         }
         const uint32_t inc = wave_incl_scan(olen);
         const uint32_t x = inc - olen, total = uni(__shfl(inc, 63));
-        if (stg.fill + total > (uint32_t)DEC_TILE) stg.flush_units();
+        if (!stg.fits(total)) stg.flush_units();
         if (inside) {
-          uint32_t p = stg.fill + x;
-          if (neg) stg.tile[p++] = (uint8_t)'-';
-          uint32_t q = p + nd;
-          stg.tile[q] = (uint8_t)' ';
+          uint8_t *p = stg.at(x);
+          if (neg) *p++ = (uint8_t)'-';
+          uint8_t *q = p + nd;
+          *q = (uint8_t)' ';
           do {
-            stg.tile[--q] = (uint8_t)('0' + v % 10u);
+            *--q = (uint8_t)('0' + v % 10u);
             v /= 10u;
           } while (q > p);
         }
-        wave_sync();
-        stg.fill += total;
-        if (stg.fill >= SUB_FLUSH) stg.flush_units();
+        stg.commit(total);
+        stg.flush_if_due();
       }
       if (!WRITE) {
         const uint32_t total = uni(__shfl(wave_incl_scan(acc), 63)) + 1u;  // + the newline
         if (lane == (uint32_t)j) my_len = total;
         continue;
       }
-      if (stg.fill + 1u > (uint32_t)DEC_TILE) stg.flush_units();
-      if (lane == 0) stg.tile[stg.fill] = (uint8_t)'\n';
-      wave_sync();
-      stg.fill += 1;
-      if (stg.fill >= SUB_FLUSH) stg.flush_units();
+      stg.append_byte((uint8_t)'\n');
     }
     if (WRITE) {
-      stg.flush_units();
-      stg.flush_tail();
+      stg.close();
     } else if (g0 + lane < g1) {
       out_len[g0 + lane] = my_len;
     }
   }
 }
 
-static void launch_idprint_any(bool write, const int32_t *ids, const unsigned long long *ioff, unsigned long long n_sent, unsigned long long n_ids,
-                               uint32_t *out_len, const unsigned long long *out_off, uint8_t *out, hipStream_t st) {
+// each pass is given what it uses
+void launch_idprint(bool write, const int32_t *ids, const unsigned long long *ioff, unsigned long long n_sent, unsigned long long n_ids, uint32_t *out_len,
+                    const unsigned long long *out_off, uint8_t *out, hipStream_t st) {
   if (!n_sent) return;
-  const unsigned int group = sub_group(n_sent, n_ids);
-  const unsigned long long n_groups = (n_sent + group - 1) / group;
-  unsigned long long b = (n_groups + NWAVES - 1) / NWAVES;
-  if (b > 256 * 8) b = 256 * 8;
-  const dim3 grid((unsigned int)b), block(BLOCK);
-  if (write) hipLaunchKernelGGL((k_idprint<true>), grid, block, 0, st, ids, ioff, n_sent, group, out_len, out_off, out);
-  else hipLaunchKernelGGL((k_idprint<false>), grid, block, 0, st, ids, ioff, n_sent, group, out_len, out_off, out);
-}
-void launch_idprint_measure(const int32_t *ids, const unsigned long long *ioff, unsigned long long n_sent, unsigned long long n_ids, uint32_t *out_len,
-                            hipStream_t st) {
-  launch_idprint_any(false, ids, ioff, n_sent, n_ids, out_len, nullptr, nullptr, st);
-}
-void launch_idprint_write(const int32_t *ids, const unsigned long long *ioff, unsigned long long n_sent, unsigned long long n_ids,
-                          const unsigned long long *out_off, uint8_t *out, hipStream_t st) {
-  launch_idprint_any(true, ids, ioff, n_sent, n_ids, nullptr, out_off, out, st);
+  const unsigned int group = lane_group(n_sent, n_ids);
+  const dim3 grid = grid_for_groups(n_sent, group), block(BLOCK);
+  if (write) hipLaunchKernelGGL((k_idprint<true>), grid, block, 0, st, ids, ioff, n_sent, group, (uint32_t *)nullptr, out_off, out);
+  else hipLaunchKernelGGL((k_idprint<false>), grid, block, 0, st, ids, ioff, n_sent, group, out_len, (const unsigned long long *)nullptr, (uint8_t *)nullptr);
 }
 
 }  // namespace yttm

@@ -1,5 +1,5 @@
 // k_spans.h -- byte spans on the device: the ids K5 left + the sentences' text -> for every id the bytes of the sentence it stands for.
-// Included at the end of k_encode.hip (behind k_subword.h: the groups of sentences are sub_group's, the classification of a byte is enc_classify).
+// Included at the end of k_encode.hip (behind k_subword.h: the groups of sentences are its lane_group's, the classification of a byte is enc_classify).
 //
 // The rule.  Read through enc_classify, a sentence is a sequence of UNITS: a valid non-space char of the alphabet is one, and so is a maximal run
 // of valid chars outside the alphabet that no space and no alphabet char interrupts (invalid bytes do not end a run: SURVEY.md A.7).  A unit
@@ -13,7 +13,7 @@
 // One pass, no global atomic: the output is 8 bytes per id at the id's own index.
 // Algorithmic bytes (N text bytes, K ids, S sentences): read N + 4 K + 16 (S + 1), written 8 K.  (Not counted: piece_units, which stays in L2.)
 //
-// Mapping: a wavefront takes a GROUP of consecutive sentences (sub_group) and walks one after the other as a merge of two monotone sequences:
+// Mapping: a wavefront takes a GROUP of consecutive sentences (lane_group) and walks one after the other as a merge of two monotone sequences:
 //   the id tiles    64 ids at a time, a lane per id: u, then A = a_k (wave scan + the tiles before) and E = A + u - 1;
 //   the text steps  64 bytes at a time, a lane per byte: ST = the lanes where a unit starts, LAST = the lanes of the last char in the step of
 //                   each unit that has a char in it -- bit j of ST is unit ub + j, bit j of LAST unit ub - cont + j (cont: the step opens inside
@@ -58,17 +58,13 @@ __global__ __launch_bounds__(BLOCK) void k_spans(EncModel m, SubInput in, const 
   const int w = uni((int)(threadIdx.x >> 6));
   const uint32_t lane = (uint32_t)lane_id();
   const unsigned long long lt = lanemask_lt();
-  const unsigned long long n_groups = (in.n_sent + group - 1) / group;
-  const unsigned long long n_waves = (unsigned long long)gridDim.x * NWAVES;
-  for (unsigned long long g = (unsigned long long)blockIdx.x * NWAVES + (unsigned long long)w; g < n_groups; g += n_waves) {
-    const unsigned long long g0 = g * group, g1 = g0 + group < in.n_sent ? g0 + group : in.n_sent;
-    // the group's boundaries, a lane each (group < 64)
-    const bool have = g0 + lane <= g1;
-    const unsigned long long my_i = have ? in.ioff[g0 + lane] : 0ull, my_s = have ? in.soff[g0 + lane] : 0ull;
+  for (WaveGroups wg(in.n_sent, group, w); wg.more(); wg.next()) {
+    const unsigned long long g0 = wg.g0(), g1 = wg.g1();
+    const LaneBounds ib(in.ioff, g0, g1, lane), sb(in.soff, g0, g1, lane);
     for (unsigned long long sidx = g0; sidx < g1; sidx++) {
       const int j = (int)(sidx - g0);
-      const unsigned long long i0 = uni64(__shfl(my_i, j)), i1 = uni64(__shfl(my_i, j + 1));
-      const unsigned long long t0 = uni64(__shfl(my_s, j)), nbytes = uni64(__shfl(my_s, j + 1)) - t0;
+      const unsigned long long i0 = ib.at(j), i1 = ib.at(j + 1);
+      const unsigned long long t0 = sb.at(j), nbytes = sb.at(j + 1) - t0;
       const uint8_t *s = in.text + t0;
       // ---- the text side: the step at hand and what the steps so far carry
       unsigned long long next_b0 = 0;      // first byte of the step to read next
@@ -172,11 +168,8 @@ __global__ __launch_bounds__(BLOCK) void k_spans_pad(const unsigned long long *_
 void launch_spans(const EncModel &m, const SubInput &in, const uint32_t *piece_units, uint32_t vocab, unsigned long long n_ids, uint32_t *spans, uint32_t *bad,
                   hipStream_t st) {
   if (!in.n_sent) return;
-  const unsigned int group = sub_group(in.n_sent, n_ids);
-  const unsigned long long n_groups = (in.n_sent + group - 1) / group;
-  unsigned long long b = (n_groups + NWAVES - 1) / NWAVES;
-  if (b > 256 * 8) b = 256 * 8;
-  hipLaunchKernelGGL(k_spans, dim3((unsigned int)b), dim3(BLOCK), 0, st, m, in, piece_units, vocab, group, (unsigned long long *)spans, bad);
+  const unsigned int group = lane_group(in.n_sent, n_ids);
+  hipLaunchKernelGGL(k_spans, grid_for_groups(in.n_sent, group), dim3(BLOCK), 0, st, m, in, piece_units, vocab, group, (unsigned long long *)spans, bad);
 }
 void launch_spans_pad(const uint32_t *spans, const unsigned long long *ioff, unsigned long long n_sent, unsigned long long width, uint32_t *matrix,
                       hipStream_t st) {

@@ -1,5 +1,5 @@
 // k_subword.h -- SUBWORD output on the device: the ids K5 left + the sentences' text -> the text `yttm encode --output_type subword` prints.
-// Included at the end of k_encode.hip (behind k_decode.h: the staging tile is DecStage, the classification of a byte is enc_classify).
+// Included at the end of k_encode.hip (behind k_decode.h; the output goes through k_textout.h's TileWriter, the classification of a byte is enc_classify).
 //
 // replaces: BaseEncoder::encode_as_subwords bpe.h:41-46, bpe.cpp:1757 (pieces by id_to_subword(id, false) bpe.cpp:1774-1807, unknown runs
 // bpe.cpp:1597-1613) + the formatting of encode_cli bpe.cpp:1942-2014 (utils.h:92-103: every piece followed by one space, then '\n'), for a batch.
@@ -12,7 +12,7 @@
 // Three steps on the lane's stream, none waits for another's progress, no global atomic:
 //   measure  k_subword<false>: out_len[s] = sum over the sentence's ids of (piece bytes + 1) + 1
 //   scan     launch_exclusive_scan(out_len) -> line_off[S + 1]                                                       (k_frontend.hip)
-//   write    k_subword<true>: pieces, runs, spaces and newlines -> LDS staging tile -> the output blob in aligned 16-byte stores
+//   write    k_subword<true>: pieces, runs, spaces and newlines -> the tile writer -> the output blob
 // Algorithmic bytes (K ids, S sentences, B_out output bytes): read 4 K + 8 (S + 1) + the text of the sentences that hold an unk_id, written
 // B_out + 8 (S + 1).  (Not counted: the sentences' byte offsets, another 8 (S + 1); the write pass reads ids, offsets and that text a second
 // time; the table, which stays in L2.)
@@ -33,9 +33,6 @@ namespace yttm {
 
 constexpr int SUB_DIR = 128;        // runs of a sentence the write pass holds at a time
 constexpr uint32_t SUB_LANE_RUN = 64;  // a run of more valid bytes than this is copied by the whole wave, not by its lane
-constexpr uint32_t SUB_FLUSH = DEC_TILE / 2;  // the wide path flushes once the tile holds this much; every append to the tile checks its own room:
-static_assert(SUB_FLUSH + 64 + 1 <= (uint32_t)DEC_TILE, "a 64-byte step of a run and a space fit behind SUB_FLUSH - 1 staged bytes");
-static_assert(15 + DEC_SEG <= DEC_TILE, "a segment of a piece fits behind an unfinished unit");
 
 // Is byte i of the sentence kept by the reference's decode (utf8.cpp:111-128)?  A byte inside a valid char, which is every byte except the start
 // of an invalid one.  (Between the first and the last byte of an unknown run every valid char belongs to the run.)
@@ -77,27 +74,17 @@ __global__ __launch_bounds__(BLOCK) void k_subword(EncModel m, SubInput in, DecT
   const int w = uni((int)(threadIdx.x >> 6));
   const uint32_t lane = (uint32_t)lane_id();
   const unsigned long long lt = lanemask_lt();
-  const unsigned long long n_groups = (in.n_sent + group - 1) / group;
-  const unsigned long long n_waves = (unsigned long long)gridDim.x * NWAVES;
   uint32_t *const beg = s_beg[WRITE ? w : 0], *const end = s_end[WRITE ? w : 0], *const vlen = s_vlen[WRITE ? w : 0];
-  for (unsigned long long g = (unsigned long long)blockIdx.x * NWAVES + (unsigned long long)w; g < n_groups; g += n_waves) {
-    const unsigned long long g0 = g * group, g1 = g0 + group < in.n_sent ? g0 + group : in.n_sent;
-    // the group's boundaries, a lane each (group < 64)
-    const bool have = g0 + lane <= g1;
-    const unsigned long long my_i = have ? in.ioff[g0 + lane] : 0ull, my_s = have ? in.soff[g0 + lane] : 0ull;
+  for (WaveGroups wg(in.n_sent, group, w); wg.more(); wg.next()) {
+    const unsigned long long g0 = wg.g0(), g1 = wg.g1();
+    const LaneBounds ib(in.ioff, g0, g1, lane), sb(in.soff, g0, g1, lane);
     uint32_t my_len = 0;  // (measure) lane j: the output bytes of sentence g0 + j
-    DecStage stg{};
-    stg.tile = s_tile[WRITE ? w : 0];
-    if (WRITE) {
-      const unsigned long long cursor = uni64(out_off[g0]);
-      stg.out = out;
-      stg.base = cursor & ~15ull;
-      stg.head = stg.fill = (uint32_t)(cursor & 15ull);
-    }
+    TileWriter stg(s_tile[WRITE ? w : 0], lane);
+    if (WRITE) stg.open(out, uni64(out_off[g0]));
     for (unsigned long long sidx = g0; sidx < g1; sidx++) {
       const int j = (int)(sidx - g0);
-      const unsigned long long i0 = uni64(__shfl(my_i, j)), i1 = uni64(__shfl(my_i, j + 1));
-      const unsigned long long b0 = uni64(__shfl(my_s, j)), nbytes = uni64(__shfl(my_s, j + 1)) - b0;
+      const unsigned long long i0 = ib.at(j), i1 = ib.at(j + 1);
+      const unsigned long long b0 = sb.at(j), nbytes = sb.at(j + 1) - b0;
       const uint8_t *s = in.text + b0;
       if (!WRITE) {
         uint32_t acc = 0, n_unk = 0;
@@ -172,20 +159,20 @@ __global__ __launch_bounds__(BLOCK) void k_subword(EncModel m, SubInput in, DecT
         const uint32_t inc = wave_incl_scan(olen);
         const uint32_t x = inc - olen, total = uni(__shfl(inc, 63));
         const bool wide = total > (uint32_t)DEC_SEG || ballot_b(is_unk && len > SUB_LANE_RUN) != 0ull;
-        if (wide || stg.fill + total > (uint32_t)DEC_TILE) stg.flush_units();
+        if (wide || !stg.fits(total)) stg.flush_units();
         if (!wide) {
           if (inside) {
-            uint32_t p = stg.fill + x;
+            uint8_t *const p = stg.at(x);
             if (is_unk) {
+              uint32_t n = 0;
               for (uint32_t i = rb; i < re; i++)
-                if (sub_keep(s, i, nbytes)) stg.tile[p++] = s[i];
+                if (sub_keep(s, i, nbytes)) p[n++] = s[i];
             } else {
-              for (uint32_t b = 0; b < len; b++) stg.tile[p + b] = tb.blob[src + b];
+              for (uint32_t b = 0; b < len; b++) p[b] = tb.blob[src + b];
             }
-            stg.tile[stg.fill + x + len] = (uint8_t)' ';
+            p[len] = (uint8_t)' ';
           }
-          wave_sync();
-          stg.fill += total;
+          stg.commit(total);
         } else {  // pieces that do not fit the tile together, or a long run: one by one, the wave copies a piece
           unsigned long long pm = ballot_b(inside);
           while (pm) {
@@ -195,71 +182,37 @@ __global__ __launch_bounds__(BLOCK) void k_subword(EncModel m, SubInput in, DecT
             if ((UK >> l) & 1ull) {  // a run streams through the tile 64 bytes of text a step, its invalid bytes filtered out
               for (uint32_t c0 = prb; c0 < pre; c0 += 64) {
                 const uint32_t i = c0 + lane;
-                const bool keep = i < pre && sub_keep(s, i, nbytes);
-                const unsigned long long K = ballot_b(keep);
-                if (keep) stg.tile[stg.fill + (uint32_t)__popcll(K & lt)] = s[i];
-                wave_sync();
-                stg.fill += (uint32_t)__popcll(K);
-                if (stg.fill >= SUB_FLUSH) stg.flush_units();
+                stg.append_kept(i < pre && sub_keep(s, i, nbytes), [&]() { return s[i]; });
               }
             } else {
-              for (uint32_t done = 0; done < plen;) {
-                const uint32_t n = plen - done < (uint32_t)DEC_SEG ? plen - done : (uint32_t)DEC_SEG;
-                if (stg.fill + n > (uint32_t)DEC_TILE) stg.flush_units();  // (a run or a space in front left up to SUB_FLUSH bytes; now fill < 16)
-                for (uint32_t b = lane; b < n; b += 64) stg.tile[stg.fill + b] = tb.blob[psrc + done + b];
-                wave_sync();
-                stg.fill += n;
-                stg.flush_units();
-                done += n;
-              }
+              stg.copy_piece(tb.blob + psrc, plen);
             }
-            if (lane == 0) stg.tile[stg.fill] = (uint8_t)' ';
-            wave_sync();
-            stg.fill += 1;
-            if (stg.fill >= SUB_FLUSH) stg.flush_units();
+            stg.append_byte((uint8_t)' ');
           }
           stg.flush_units();
         }
       }
-      if (stg.fill + 1u > (uint32_t)DEC_TILE) stg.flush_units();
-      if (lane == 0) stg.tile[stg.fill] = (uint8_t)'\n';
-      wave_sync();
-      stg.fill += 1;
-      if (stg.fill >= SUB_FLUSH) stg.flush_units();
+      stg.append_byte((uint8_t)'\n');
     }
     if (WRITE) {
-      stg.flush_units();
-      stg.flush_tail();
+      stg.close();
     } else if (g0 + lane < g1) {
       out_len[g0 + lane] = my_len;
     }
   }
 }
 
-// sentences per group: about 256 ids, in a large batch enough that a wavefront has a few groups, not thousands; below 64 (a lane per boundary)
-static unsigned int sub_group(unsigned long long n_sent, unsigned long long n_ids) {
-  unsigned long long avg = n_ids / n_sent, grp = 256 / (avg ? avg : 1);
-  const unsigned long long many = n_sent / (256ull * 8 * NWAVES * 4);
-  if (grp < many) grp = many;
-  return (unsigned int)(grp < 1 ? 1 : grp > 63 ? 63 : grp);
-}
-static void launch_subword_any(bool write, const EncModel &m, const SubInput &in, const DecTable &tb, unsigned long long n_ids, uint32_t *out_len,
-                               const unsigned long long *out_off, uint8_t *out, hipStream_t st) {
+// sentences per group of the kernels that hold a group's boundaries a lane each (k_subword, k_idprint, k_spans): about 256 ids
+static unsigned int lane_group(unsigned long long n_sent, unsigned long long n_ids) { return group_size(n_sent, n_ids, 256, LANE_GROUP_MAX); }
+
+// each pass is given what it uses
+void launch_subword(bool write, const EncModel &m, const SubInput &in, const DecTable &tb, unsigned long long n_ids, uint32_t *out_len,
+                    const unsigned long long *out_off, uint8_t *out, hipStream_t st) {
   if (!in.n_sent) return;
-  const unsigned int group = sub_group(in.n_sent, n_ids);
-  const unsigned long long n_groups = (in.n_sent + group - 1) / group;
-  unsigned long long b = (n_groups + NWAVES - 1) / NWAVES;
-  if (b > 256 * 8) b = 256 * 8;
-  const dim3 grid((unsigned int)b), block(BLOCK);
-  if (write) hipLaunchKernelGGL((k_subword<true>), grid, block, 0, st, m, in, tb, group, out_len, out_off, out);
-  else hipLaunchKernelGGL((k_subword<false>), grid, block, 0, st, m, in, tb, group, out_len, out_off, out);
-}
-void launch_subword_measure(const EncModel &m, const SubInput &in, const DecTable &tb, unsigned long long n_ids, uint32_t *out_len, hipStream_t st) {
-  launch_subword_any(false, m, in, tb, n_ids, out_len, nullptr, nullptr, st);
-}
-void launch_subword_write(const EncModel &m, const SubInput &in, const DecTable &tb, unsigned long long n_ids, const unsigned long long *out_off,
-                          uint8_t *out, hipStream_t st) {
-  launch_subword_any(true, m, in, tb, n_ids, nullptr, out_off, out, st);
+  const unsigned int group = lane_group(in.n_sent, n_ids);
+  const dim3 grid = grid_for_groups(in.n_sent, group), block(BLOCK);
+  if (write) hipLaunchKernelGGL((k_subword<true>), grid, block, 0, st, m, in, tb, group, (uint32_t *)nullptr, out_off, out);
+  else hipLaunchKernelGGL((k_subword<false>), grid, block, 0, st, m, in, tb, group, out_len, (const unsigned long long *)nullptr, (uint8_t *)nullptr);
 }
 
 }  // namespace yttm

@@ -395,13 +395,12 @@ struct DecInput {  // sentence s = ids[offsets[s] .. offsets[s+1]), or (offsets 
   unsigned long long width, stride;  // padded only; 1 <= stride, width <= stride
   unsigned long long n_sent;
 };
-// n_flat: ids (ragged) or n_sent * stride (padded) -- sizes the groups of sentences.  *bad_min must hold ~0 before the launch.
-// newline (ragged input only, the same in both launches): a '\n' behind every sentence, counted in out_len.
-void launch_decode_measure(const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, uint32_t *out_len,
-                           unsigned long long *bad_min, hipStream_t st, bool newline = false);
-// out: 16-byte aligned
-void launch_decode_write(const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, const unsigned long long *out_off,
-                         uint8_t *out, hipStream_t st, bool newline = false);
+// The two-pass kernels below take both passes' arguments: write == false is the measure pass (out_len / count, and decode's bad_min), write == true
+// the write pass (out_off, the exclusive scan of the measure's counts, and out, 16-byte aligned); a pass's kernel is handed null for the other's.
+// n_flat: ids (ragged) or n_sent * stride (padded) -- sizes the groups of sentences.  *bad_min must hold ~0 before the measure pass.
+// newline (ragged input only, the same in both passes): a '\n' behind every sentence, counted in out_len.
+void launch_decode(bool write, bool newline, const DecInput &in, const DecTable &tb, const DecIgnore &ig, unsigned long long n_flat, uint32_t *out_len,
+                   unsigned long long *bad_min, const unsigned long long *out_off, uint8_t *out, hipStream_t st);
 void launch_enc_longest(const unsigned long long *out_off, unsigned long long n_sent, unsigned int *longest /* holds 0 before the launch */, hipStream_t st);
 void launch_enc_pad(const int32_t *ids, const unsigned long long *out_off, unsigned long long n_sent, unsigned long long width, int32_t pad_value,
                     int32_t *matrix /* 4-byte aligned */, int32_t *lengths, hipStream_t st);
@@ -417,10 +416,8 @@ struct SubInput {  // sentence s = text[soff[s] .. soff[s+1]) and the ids K5 lef
   int reverse;  // the ids are stored back to front
 };
 // tb: the pieces as id_to_subword(id, replace_space = false) gives them (no DEC_INVALID marks).  n_ids sizes the groups of sentences.
-void launch_subword_measure(const EncModel &m, const SubInput &in, const DecTable &tb, unsigned long long n_ids, uint32_t *out_len, hipStream_t st);
-// out: 16-byte aligned; out_off: the exclusive scan of out_len, [n_sent + 1]
-void launch_subword_write(const EncModel &m, const SubInput &in, const DecTable &tb, unsigned long long n_ids, const unsigned long long *out_off,
-                          uint8_t *out, hipStream_t st);
+void launch_subword(bool write, const EncModel &m, const SubInput &in, const DecTable &tb, unsigned long long n_ids, uint32_t *out_len,
+                    const unsigned long long *out_off /* [n_sent + 1] */, uint8_t *out, hipStream_t st);
 
 // ---- byte spans (k_spans.h, compiled with k_encode.hip): one pass, 8 bytes per id ----
 // piece_units[vocab]: the units an id covers (1 for unk_id, else the code points of its piece other than U+2581).  spans: uint32 [n_ids][2],
@@ -444,15 +441,11 @@ void launch_lines_longest(const unsigned long long *off, unsigned long long n_li
 // ---- decimal id text (k_idtext.h, compiled with k_encode.hip): measure -> launch_exclusive_scan -> write, both ways ----
 // the parser: line i = text[loff[i] .. loff[i + 1]) with its newline (the offsets launch_lines_write left; text: any address) -> count[n_lines],
 // then the ids `while (ss >> x)` reads from each line at ids[out_off[i] ..), out_off the exclusive scan of count.  n_bytes sizes the groups of lines.
-void launch_idparse_measure(const uint8_t *text, const unsigned long long *loff, unsigned long long n_lines, unsigned long long n_bytes, uint32_t *count,
-                            hipStream_t st);
-void launch_idparse_write(const uint8_t *text, const unsigned long long *loff, unsigned long long n_lines, unsigned long long n_bytes,
-                          const unsigned long long *out_off, int32_t *ids, hipStream_t st);
+void launch_idparse(bool write, const uint8_t *text, const unsigned long long *loff, unsigned long long n_lines, unsigned long long n_bytes, uint32_t *count,
+                    const unsigned long long *out_off, int32_t *ids, hipStream_t st);
 // the printer: sentence s = ids[ioff[s] .. ioff[s + 1]) -> every id in decimal + one space, then '\n'.  out: 16-byte aligned; out_off: the
 // exclusive scan of out_len, [n_sent + 1].  n_ids sizes the groups of sentences.
-void launch_idprint_measure(const int32_t *ids, const unsigned long long *ioff, unsigned long long n_sent, unsigned long long n_ids, uint32_t *out_len,
-                            hipStream_t st);
-void launch_idprint_write(const int32_t *ids, const unsigned long long *ioff, unsigned long long n_sent, unsigned long long n_ids,
-                          const unsigned long long *out_off, uint8_t *out, hipStream_t st);
+void launch_idprint(bool write, const int32_t *ids, const unsigned long long *ioff, unsigned long long n_sent, unsigned long long n_ids, uint32_t *out_len,
+                    const unsigned long long *out_off, uint8_t *out, hipStream_t st);
 
 }  // namespace yttm

@@ -9,6 +9,8 @@ torch's current stream (whatever produced the input tensors is done), call the l
 allocated -- torch owns all memory it sees."""
 import numpy as np
 
+from .bpe import _check_dropout
+
 
 def _torch():
     import torch
@@ -23,6 +25,21 @@ def _device_of(bpe, device):
         if want.type != "cuda" or (want.index is not None and want.index != own.index):
             raise ValueError("device %s is not the encoder's (%s)" % (want, own))
     return own
+
+
+def _pad_id(bpe, padded, pad_id):
+    """the value behind a row's last id: the caller's, else the model's <PAD>"""
+    if padded and pad_id is None:
+        pad_id = bpe.subword_to_id("<PAD>")
+        if pad_id == -1 or bpe.id_to_subword(pad_id) != "<PAD>":
+            raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
+    return pad_id
+
+
+def _synced(torch, dev, call, *args):
+    """call(*args) once torch's current stream is done: the tensors the library is about to read are complete, those it fills are allocated"""
+    torch.cuda.current_stream(dev).synchronize()
+    return call(*args)
 
 
 def _check_on(t, dev, what):
@@ -71,15 +88,10 @@ def encode_tensor(bpe, sentences, bos=False, eos=False, reverse=False, dropout_p
     torch = _torch()
     core = bpe.bpe_cython
     dev = _device_of(bpe, device)
-    if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
-        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
-    if padded and pad_id is None:
-        pad_id = bpe.subword_to_id("<PAD>")
-        if pad_id == -1 or bpe.id_to_subword(pad_id) != "<PAD>":
-            raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
+    _check_dropout(dropout_prob)
+    pad_id = _pad_id(bpe, padded, pad_id)
     d_bytes, d_off, n, total, longest_in = _sentences_on(torch, sentences, dev)
-    torch.cuda.current_stream(dev).synchronize()  # the inputs are complete before the library's own stream reads them
-    n_ids, _ = core.encode_device_raw(d_bytes.data_ptr(), d_off.data_ptr(), n, total, longest_in, bos, eos, reverse, dropout_prob)
+    n_ids, _ = _synced(torch, dev, core.encode_device_raw, d_bytes.data_ptr(), d_off.data_ptr(), n, total, longest_in, bos, eos, reverse, dropout_prob)
     return _take_encoded(torch, core, dev, n, n_ids, padded, width, pad_id)
 
 
@@ -88,8 +100,7 @@ def _take_encoded(torch, core, dev, n, n_ids, padded, width, pad_id):
     if not padded:
         ids = torch.empty(n_ids, dtype=torch.int32, device=dev)
         out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        core.copy_encode_device(ids.data_ptr(), out_off.data_ptr(), n)
+        _synced(torch, dev, core.copy_encode_device, ids.data_ptr(), out_off.data_ptr(), n)
         return ids, out_off
     longest = core.encode_longest(n) if n else 0
     if width is None:
@@ -99,8 +110,7 @@ def _take_encoded(torch, core, dev, n, n_ids, padded, width, pad_id):
     matrix = torch.empty((n, width), dtype=torch.int32, device=dev)
     lengths = torch.empty(n, dtype=torch.int32, device=dev)
     if n:
-        torch.cuda.current_stream(dev).synchronize()
-        core.copy_encode_padded(matrix.data_ptr(), lengths.data_ptr(), n, width, pad_id)
+        _synced(torch, dev, core.copy_encode_padded, matrix.data_ptr(), lengths.data_ptr(), n, width, pad_id)
     return matrix, lengths
 
 
@@ -120,15 +130,10 @@ def encode_text_tensor(bpe, text, bos=False, eos=False, reverse=False, dropout_p
     torch = _torch()
     core = bpe.bpe_cython
     dev = _device_of(bpe, None)
-    if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
-        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
-    if padded and pad_id is None:
-        pad_id = bpe.subword_to_id("<PAD>")
-        if pad_id == -1 or bpe.id_to_subword(pad_id) != "<PAD>":
-            raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
+    _check_dropout(dropout_prob)
+    pad_id = _pad_id(bpe, padded, pad_id)
     d_text, n_bytes = _text_on(torch, text, dev)
-    torch.cuda.current_stream(dev).synchronize()  # the text is complete before the library's own stream reads it
-    n, n_ids, _ = core.encode_text_device_raw(d_text.data_ptr(), n_bytes, bos, eos, reverse, dropout_prob)
+    n, n_ids, _ = _synced(torch, dev, core.encode_text_device_raw, d_text.data_ptr(), n_bytes, bos, eos, reverse, dropout_prob)
     return _take_encoded(torch, core, dev, n, n_ids, padded, width, pad_id)
 
 
@@ -137,11 +142,9 @@ def text_lines_tensor(bpe, text):
     core = bpe.bpe_cython
     dev = _device_of(bpe, None)
     d_text, n_bytes = _text_on(torch, text, dev)
-    torch.cuda.current_stream(dev).synchronize()
-    n, _, _ = core.lines_device_raw(d_text.data_ptr(), n_bytes)
+    n, _, _ = _synced(torch, dev, core.lines_device_raw, d_text.data_ptr(), n_bytes)
     off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    torch.cuda.current_stream(dev).synchronize()
-    core.copy_lines_device(off.data_ptr(), n)
+    _synced(torch, dev, core.copy_lines_device, off.data_ptr(), n)
     return off
 
 
@@ -170,8 +173,7 @@ def decode_tensor(bpe, ids, lengths=None, offsets=None, ignore_ids=None, as_str=
                 raise ValueError("lengths must have one entry per row")
             lengths = lengths.to(torch.int32).contiguous()
             d_len = lengths.data_ptr()
-        torch.cuda.current_stream(dev).synchronize()
-        n_bytes, _ = core.decode_device_padded_raw(ids.data_ptr(), n, width, stride, d_len or None, ignore_ids)
+        n_bytes, _ = _synced(torch, dev, core.decode_device_padded_raw, ids.data_ptr(), n, width, stride, d_len or None, ignore_ids)
     elif ids.dim() == 1:
         if offsets is None or lengths is not None:
             raise ValueError("1-D ids take offsets [n + 1] (and no lengths)")
@@ -182,31 +184,22 @@ def decode_tensor(bpe, ids, lengths=None, offsets=None, ignore_ids=None, as_str=
             raise ValueError("offsets must have at least one entry")
         if n and (int(offsets[-1]) > ids.numel() or int(offsets[0]) < 0 or bool((offsets[1:] < offsets[:-1]).any())):
             raise ValueError("offsets must be non-decreasing and end inside ids")
-        torch.cuda.current_stream(dev).synchronize()
-        n_bytes, _ = core.decode_device_raw(ids.data_ptr(), offsets.data_ptr(), n, ids.numel(), ignore_ids)
+        n_bytes, _ = _synced(torch, dev, core.decode_device_raw, ids.data_ptr(), offsets.data_ptr(), n, ids.numel(), ignore_ids)
     else:
         raise ValueError("ids must be 1-D (with offsets) or 2-D (padded)")
+    return _take_text(torch, core, dev, n, n_bytes, as_str, errors="strict")
+
+
+def _take_text(torch, core, dev, n, n_bytes, as_str, errors="replace"):
+    """the pending text of n lines: list[str], or (uint8 text, int64 line_off [n + 1]) tensors that torch owns.  errors: a formatter's text may cut
+    a sentence's invalid UTF-8 as it stood ("replace"); a decode's is the vocabulary's own ("strict")"""
     if as_str:
         raw, off = core.fetch_decode(n, n_bytes)
         raw, o = raw.tobytes(), off.tolist()
-        return [raw[o[i]:o[i + 1]].decode() for i in range(n)]
+        return [raw[o[i]:o[i + 1]].decode(errors=errors) for i in range(n)]
     text = torch.empty(n_bytes, dtype=torch.uint8, device=dev)
     out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    torch.cuda.current_stream(dev).synchronize()
-    core.copy_decode_device(text.data_ptr(), out_off.data_ptr(), n)
-    return text, out_off
-
-
-def _take_text(torch, core, dev, n, n_bytes, as_str):
-    """the pending text of n lines: list[str], or (uint8 text, int64 line_off [n + 1]) tensors that torch owns"""
-    if as_str:
-        raw, off = core.fetch_decode(n, n_bytes)
-        raw, o = raw.tobytes(), off.tolist()
-        return [raw[o[i]:o[i + 1]].decode(errors="replace") for i in range(n)]
-    text = torch.empty(n_bytes, dtype=torch.uint8, device=dev)
-    out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    torch.cuda.current_stream(dev).synchronize()
-    core.copy_decode_device(text.data_ptr(), out_off.data_ptr(), n)
+    _synced(torch, dev, core.copy_decode_device, text.data_ptr(), out_off.data_ptr(), n)
     return text, out_off
 
 
@@ -214,11 +207,9 @@ def encode_subword_tensor(bpe, sentences, bos=False, eos=False, reverse=False, d
     torch = _torch()
     core = bpe.bpe_cython
     dev = _device_of(bpe, device)
-    if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
-        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+    _check_dropout(dropout_prob)
     d_bytes, d_off, n, total, longest_in = _sentences_on(torch, sentences, dev)
-    torch.cuda.current_stream(dev).synchronize()  # the inputs are complete before the library's own stream reads them
-    _, n_text, _ = core.subword_device_raw(d_bytes.data_ptr(), d_off.data_ptr(), n, total, longest_in, bos, eos, reverse, dropout_prob)
+    _, n_text, _ = _synced(torch, dev, core.subword_device_raw, d_bytes.data_ptr(), d_off.data_ptr(), n, total, longest_in, bos, eos, reverse, dropout_prob)
     return _take_text(torch, core, dev, n, n_text, as_str)
 
 
@@ -226,11 +217,9 @@ def encode_text_subword_tensor(bpe, text, bos=False, eos=False, reverse=False, d
     torch = _torch()
     core = bpe.bpe_cython
     dev = _device_of(bpe, None)
-    if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
-        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
+    _check_dropout(dropout_prob)
     d_text, n_bytes = _text_on(torch, text, dev)
-    torch.cuda.current_stream(dev).synchronize()  # the text is complete before the library's own stream reads it
-    n, _, n_text, _ = core.subword_text_device_raw(d_text.data_ptr(), n_bytes, bos, eos, reverse, dropout_prob)
+    n, _, n_text, _ = _synced(torch, dev, core.subword_text_device_raw, d_text.data_ptr(), n_bytes, bos, eos, reverse, dropout_prob)
     return _take_text(torch, core, dev, n, n_text, as_str)
 
 
@@ -239,13 +228,11 @@ def _take_spans(torch, core, dev, n, n_ids, padded, width, pad_id):
     first, second = _take_encoded(torch, core, dev, n, n_ids, padded, width, pad_id)
     if not padded:
         spans = torch.empty((n_ids, 2), dtype=torch.int32, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        core.copy_spans_device(spans.data_ptr(), n)
+        _synced(torch, dev, core.copy_spans_device, spans.data_ptr(), n)
         return first, second, spans
     spans = torch.empty((n, first.shape[1], 2), dtype=torch.int32, device=dev)
     if n:
-        torch.cuda.current_stream(dev).synchronize()
-        core.copy_spans_padded(spans.data_ptr(), n, first.shape[1])
+        _synced(torch, dev, core.copy_spans_padded, spans.data_ptr(), n, first.shape[1])
     return first, second, spans
 
 
@@ -253,15 +240,10 @@ def encode_spans_tensor(bpe, sentences, bos=False, eos=False, reverse=False, dro
     torch = _torch()
     core = bpe.bpe_cython
     dev = _device_of(bpe, device)
-    if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
-        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
-    if padded and pad_id is None:
-        pad_id = bpe.subword_to_id("<PAD>")
-        if pad_id == -1 or bpe.id_to_subword(pad_id) != "<PAD>":
-            raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
+    _check_dropout(dropout_prob)
+    pad_id = _pad_id(bpe, padded, pad_id)
     d_bytes, d_off, n, total, longest_in = _sentences_on(torch, sentences, dev)
-    torch.cuda.current_stream(dev).synchronize()  # the inputs are complete before the library's own stream reads them
-    n_ids, _ = core.spans_device_raw(d_bytes.data_ptr(), d_off.data_ptr(), n, total, longest_in, bos, eos, reverse, dropout_prob)
+    n_ids, _ = _synced(torch, dev, core.spans_device_raw, d_bytes.data_ptr(), d_off.data_ptr(), n, total, longest_in, bos, eos, reverse, dropout_prob)
     return _take_spans(torch, core, dev, n, n_ids, padded, width, pad_id)
 
 
@@ -269,15 +251,10 @@ def encode_text_spans_tensor(bpe, text, bos=False, eos=False, reverse=False, dro
     torch = _torch()
     core = bpe.bpe_cython
     dev = _device_of(bpe, None)
-    if dropout_prob < 0 or dropout_prob > 1:  # yttm.pyx:92-93
-        raise ValueError("dropout_prob value must be in the range [0, 1]. Current value of dropout_prob = " + str(dropout_prob))
-    if padded and pad_id is None:
-        pad_id = bpe.subword_to_id("<PAD>")
-        if pad_id == -1 or bpe.id_to_subword(pad_id) != "<PAD>":
-            raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
+    _check_dropout(dropout_prob)
+    pad_id = _pad_id(bpe, padded, pad_id)
     d_text, n_bytes = _text_on(torch, text, dev)
-    torch.cuda.current_stream(dev).synchronize()  # the text is complete before the library's own stream reads it
-    n, n_ids, _ = core.spans_text_device_raw(d_text.data_ptr(), n_bytes, bos, eos, reverse, dropout_prob)
+    n, n_ids, _ = _synced(torch, dev, core.spans_text_device_raw, d_text.data_ptr(), n_bytes, bos, eos, reverse, dropout_prob)
     return _take_spans(torch, core, dev, n, n_ids, padded, width, pad_id)
 
 
@@ -285,13 +262,9 @@ def parse_ids_tensor(bpe, text, padded=False, width=None, pad_id=None):
     torch = _torch()
     core = bpe.bpe_cython
     dev = _device_of(bpe, None)
-    if padded and pad_id is None:
-        pad_id = bpe.subword_to_id("<PAD>")
-        if pad_id == -1 or bpe.id_to_subword(pad_id) != "<PAD>":
-            raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
+    pad_id = _pad_id(bpe, padded, pad_id)
     d_text, n_bytes = _text_on(torch, text, dev)
-    torch.cuda.current_stream(dev).synchronize()  # the text is complete before the library's own stream reads it
-    n, n_ids, _ = core.ids_parse_device_raw(d_text.data_ptr(), n_bytes)
+    n, n_ids, _ = _synced(torch, dev, core.ids_parse_device_raw, d_text.data_ptr(), n_bytes)
     return _take_encoded(torch, core, dev, n, n_ids, padded, width, pad_id)
 
 
@@ -300,8 +273,7 @@ def decode_text_tensor(bpe, text, ignore_ids=None, as_str=True):
     core = bpe.bpe_cython
     dev = _device_of(bpe, None)
     d_text, n_bytes = _text_on(torch, text, dev)
-    torch.cuda.current_stream(dev).synchronize()  # the text is complete before the library's own stream reads it
-    n, _, n_text, _ = core.decode_text_device_raw(d_text.data_ptr(), n_bytes, ignore_ids)
+    n, _, n_text, _ = _synced(torch, dev, core.decode_text_device_raw, d_text.data_ptr(), n_bytes, ignore_ids)
     if as_str:
         return [s[:-1] for s in _take_text(torch, core, dev, n, n_text, True)]
     return _take_text(torch, core, dev, n, n_text, False)
