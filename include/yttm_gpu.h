@@ -54,6 +54,12 @@ int yttm_gpu_download_word_table(yttm_ctx *ctx, uint32_t *tok, uint64_t *off, ui
 int yttm_gpu_pair_count(yttm_ctx *ctx, uint64_t *n_pairs);
 /* all pairs with count > 0 (unsorted); *n_inout: capacity in, count out */
 int yttm_gpu_download_pairs(yttm_ctx *ctx, uint64_t *pairs /* x<<32|y */, uint64_t *counts, uint64_t *n_inout);
+/* debug: the pair index of word mode as the rounds read it.  Key i is pairs[i] (unsorted), its postings -- class-A word rows, in no order,
+ * duplicates allowed -- are post[run_lo[i] .. run_hi[i]).  *n_keys_inout, *n_post_inout: capacities in, counts out (also when the call fails
+ * for lack of room, so that it can be repeated); both 0: no valid index.  Between rounds only, and like yttm_gpu_download_pairs it fails
+ * while the scan of a yttm_gpu_merge_apply_scan is pending. */
+int yttm_gpu_download_index(yttm_ctx *ctx, uint64_t *pairs, uint64_t *run_lo, uint64_t *run_hi, uint64_t *n_keys_inout, uint32_t *post,
+                            uint64_t *n_post_inout);
 
 /* K4 -- worker_doing_merge (bpe.cpp:491-812) for a batch of k mutually non-intersecting rules xyz[3k]
  * (rule_intersection, bpe.cpp:145-147; at most one x==y rule, last): applies them to every word and updates the
@@ -73,8 +79,9 @@ int yttm_gpu_merge_apply_scan(yttm_ctx *ctx, const uint32_t *xyz, uint32_t k, co
 /* Which paths the context's merge rounds and candidate scans took so far -- the counters of the training report, in this order:
  * [0] merge_rounds, [1] word_rounds, [2] word_all_rounds, [3] word_fused_rounds, [4] index_builds, [5] classb_word_rounds,
  * [6] fused_rounds, [7] fused_overflows, [8] hot_rebuilds, [9] top_refills, [10] word_switch_round, [11] exchange_retries (multi-GPU: rounds
- * whose exchange was repeated with wider blocks), [12] k3_radix (1: K3 counted class A by radix partition).  The first min(n, 13) go to out. */
-#define YTTM_ROUND_STATS 13
+ * whose exchange was repeated with wider blocks), [12] k3_radix (1: K3 counted class A by radix partition), [13] index_radix_builds (of
+ * index_builds: filled by radix partition of the postings).  The first min(n, 14) go to out. */
+#define YTTM_ROUND_STATS 14
 int yttm_gpu_round_stats(yttm_ctx *ctx, uint64_t *out, uint32_t n);
 /* Measurement mode of K4 (bench.py's untimed pass behind roofline.algorithmic_bytes_8d): on != 0 makes the following
  * yttm_gpu_merge_apply calls also count the WORDS that hold a merge site and their tokens (W_touched, T_touched).

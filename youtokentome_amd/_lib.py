@@ -33,7 +33,7 @@ EXPORTS = [
     "yttm_gpu_ctx_create", "yttm_gpu_ctx_destroy", "yttm_gpu_ctx_set_comm", "yttm_gpu_last_error", "yttm_release_device_memory", "yttm_config_table",
     "yttm_gpu_upload_corpus",
     "yttm_gpu_attach_corpus", "yttm_gpu_char_hist", "yttm_gpu_build_word_table", "yttm_gpu_download_word_table",
-    "yttm_gpu_pair_count", "yttm_gpu_download_pairs", "yttm_gpu_merge_apply", "yttm_gpu_pair_query",
+    "yttm_gpu_pair_count", "yttm_gpu_download_pairs", "yttm_gpu_download_index", "yttm_gpu_merge_apply", "yttm_gpu_pair_query",
     "yttm_gpu_candidates", "yttm_gpu_k4_measure", "yttm_gpu_merge_apply_scan", "yttm_gpu_round_stats",
 ]
 
@@ -130,6 +130,7 @@ def load():
     L.yttm_gpu_download_word_table.argtypes = [cvp, u32p, u64p, u32p, u64p]
     L.yttm_gpu_pair_count.argtypes = [cvp, u64p]
     L.yttm_gpu_download_pairs.argtypes = [cvp, u64p, u64p, u64p]
+    L.yttm_gpu_download_index.argtypes = [cvp, u64p, u64p, u64p, u64p, u32p, u64p]
     L.yttm_gpu_merge_apply.argtypes = [cvp, u32p, C.c_uint32]
     L.yttm_gpu_merge_apply_scan.argtypes = [cvp, u32p, C.c_uint32, u64p, C.c_uint64, C.c_uint32, C.c_uint32]
     L.yttm_gpu_round_stats.argtypes = [cvp, u64p, C.c_uint32]

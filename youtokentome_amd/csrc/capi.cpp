@@ -35,15 +35,15 @@ void yttm_report_to_json(const TrainReport &r, char *buf, int len) {
   if (!buf || len <= 0) return;
   static const char *names[8] = {"char_hist", "segments", "dedup", "build", "pair_count", "merge_apply", "cand_scan", "exchange"};
   std::string s = "{";
-  char tmp[1024];
+  char tmp[1280];
   snprintf(tmp, sizeof tmp, "\"seconds_total\": %.6f, \"seconds_upload\": %.6f, \"seconds_frontend\": %.6f, \"seconds_merge\": %.6f, \"seconds_io\": %.6f, ", r.seconds_total,
            r.seconds_upload, r.seconds_frontend, r.seconds_merge, r.seconds_io);
   s += tmp;
   snprintf(tmp, sizeof tmp, "\"corpus_bytes\": %llu, \"n_unique\": %llu, \"n_tokens\": %llu, \"rounds\": %llu, \"rules\": %llu, \"cand_rescans\": %llu, \"hot_rebuilds\": %llu, \"repacks\": %llu, \"merge_sites\": %llu, ",
            r.corpus_bytes, r.n_unique, r.n_tokens, r.rounds, r.rules, r.cand_rescans, r.hot_rebuilds, r.repacks, r.merge_sites);
   s += tmp;
-  snprintf(tmp, sizeof tmp, "\"fused_rounds\": %llu, \"fused_overflows\": %llu, \"exchange_retries\": %llu, \"word_table_retries\": %llu, \"front_end_overlapped\": %llu, \"top_refills\": %llu, \"index_builds\": %llu, \"word_rounds\": %llu, \"word_switch_round\": %llu, \"word_all_rounds\": %llu, \"word_fused_rounds\": %llu, \"rounds_exhausted\": %llu, \"batch_extensions\": %llu, \"batch_splits\": %llu, \"replicated_merge_loop\": %llu, \"front_end_chunks\": %llu, \"peak_device_bytes\": %llu, \"classb_word_rounds\": %llu, \"k3_radix\": %llu, ",
-           r.fused_rounds, r.fused_overflows, r.exchange_retries, r.word_table_retries, r.front_end_overlapped, r.top_refills, r.index_builds, r.word_rounds, r.word_switch_round, r.word_all_rounds, r.word_fused_rounds, r.rounds_exhausted, r.batch_extensions, r.batch_splits, r.replicated_merge_loop, r.front_end_chunks, r.peak_device_bytes, r.classb_word_rounds, r.k3_radix);
+  snprintf(tmp, sizeof tmp, "\"fused_rounds\": %llu, \"fused_overflows\": %llu, \"exchange_retries\": %llu, \"word_table_retries\": %llu, \"front_end_overlapped\": %llu, \"top_refills\": %llu, \"index_builds\": %llu, \"index_radix_builds\": %llu, \"word_rounds\": %llu, \"word_switch_round\": %llu, \"word_all_rounds\": %llu, \"word_fused_rounds\": %llu, \"rounds_exhausted\": %llu, \"batch_extensions\": %llu, \"batch_splits\": %llu, \"replicated_merge_loop\": %llu, \"front_end_chunks\": %llu, \"peak_device_bytes\": %llu, \"classb_word_rounds\": %llu, \"k3_radix\": %llu, ",
+           r.fused_rounds, r.fused_overflows, r.exchange_retries, r.word_table_retries, r.front_end_overlapped, r.top_refills, r.index_builds, r.index_radix_builds, r.word_rounds, r.word_switch_round, r.word_all_rounds, r.word_fused_rounds, r.rounds_exhausted, r.batch_extensions, r.batch_splits, r.replicated_merge_loop, r.front_end_chunks, r.peak_device_bytes, r.classb_word_rounds, r.k3_radix);
   s += tmp;
   snprintf(tmp, sizeof tmp, "\"touched_tiles\": %llu, \"touched_tile_tokens\": %llu, \"touched_words\": %llu, \"touched_word_tokens\": %llu, ",
            r.touched_tiles, r.touched_tile_tokens, r.touched_words, r.touched_word_tokens);
@@ -511,6 +511,19 @@ int yttm_gpu_download_pairs(yttm_ctx *c, uint64_t *pairs, uint64_t *counts, uint
     *n_inout = k.size();
   })
 }
+int yttm_gpu_download_index(yttm_ctx *c, uint64_t *pairs, uint64_t *run_lo, uint64_t *run_hi, uint64_t *n_keys_inout, uint32_t *post, uint64_t *n_post_inout) {
+  GUARD_CTX({
+    std::vector<unsigned long long> k, lo, hi;
+    std::vector<uint32_t> p;
+    c->g->download_index(k, lo, hi, p);
+    const bool fits = k.size() <= *n_keys_inout && p.size() <= *n_post_inout;
+    *n_keys_inout = k.size();
+    *n_post_inout = p.size();
+    if (!fits) throw GpuError{"download_index: output capacity too small"};
+    for (size_t i = 0; i < k.size(); i++) { pairs[i] = k[i]; run_lo[i] = lo[i]; run_hi[i] = hi[i]; }
+    if (!p.empty()) memcpy(post, p.data(), p.size() * 4);
+  })
+}
 int yttm_gpu_merge_apply(yttm_ctx *c, const uint32_t *xyz, uint32_t k) { GUARD_CTX(c->g->merge_apply(xyz, k, nullptr)) }
 int yttm_gpu_merge_apply_scan(yttm_ctx *c, const uint32_t *xyz, uint32_t k, const uint64_t *rule_counts, uint64_t next_tau_cnt, uint32_t next_tau_mx,
                               uint32_t next_want) {
@@ -523,7 +536,8 @@ int yttm_gpu_round_stats(yttm_ctx *c, uint64_t *out, uint32_t n) {
   GUARD_CTX({
     const GpuCtx &g = *c->g;
     const unsigned long long v[YTTM_ROUND_STATS] = {g.merge_rounds, g.word_rounds, g.word_all_rounds, g.word_fused_rounds, g.index_builds, g.classb_word_rounds,
-                                                    g.fused_rounds, g.fused_overflows, g.hot_rebuilds, g.top_refills, g.word_switch_round, g.exchange_retries, g.k3_radix};
+                                                    g.fused_rounds, g.fused_overflows, g.hot_rebuilds, g.top_refills, g.word_switch_round, g.exchange_retries, g.k3_radix,
+                                                    g.index_radix_builds};
     for (uint32_t i = 0; i < std::min<uint32_t>(n, YTTM_ROUND_STATS); i++) out[i] = v[i];
   })
 }

@@ -27,6 +27,7 @@ GpuCtx::GpuCtx(int device) : device_(device) {
   hot_min_ = (unsigned int)C.hot_min.u;
   fuse_enabled_ = C.no_fuse.u == 0;
   idx_enabled_ = C.no_index.u == 0;  // (no pair index: no word mode either)
+  idx_radix_min_ = C.index_radix_min.u;  // (class-A live tokens from which the index is built by radix partition; tests: 0 / huge)
   idx_agg_min_ = C.index_agg_min.u;  // (fill pass of an index build: postings from which on a workgroup sums them per key in LDS first; tests: 0)
   hot_target_words_ = (unsigned int)C.hot_target_words.u;  // (measured at 1 GB, word mode: 8192 -> 6 rebuilds, candidate family 21.0 ms; 32768 -> 3, 16.9 ms; round 4: 32768 -> 3, 14.6 ms; 65536 -> 2, 12.5; 131072 -> 2, 15.0)
   // rounds of at most this many words (by the hint) whose batch travels in the kernel arguments are ONE launch, k_words<FUSED>; 0: never.

@@ -85,6 +85,9 @@ class GpuCtx {
   // ---- K3
   void pair_count();
   void download_pairs(std::vector<unsigned long long> &keys, std::vector<unsigned long long> &cnts);
+  // debug: the pair index as the rounds read it -- its keys, each key's run [lo, hi) of `post`, and the postings (class-A word rows).  Between
+  // rounds only, with no scan pending; an index that is not valid comes back empty.
+  void download_index(std::vector<unsigned long long> &keys, std::vector<unsigned long long> &lo, std::vector<unsigned long long> &hi, std::vector<uint32_t> &post);
   // ---- K4: apply a batch of mutually non-intersecting rules (x,y,z)*k
   // next_tau_cnt / next_tau_mx (optional): the threshold of the candidate scan that will follow this round.  When the round is
   // one launch (single GPU, class-A tiles only, hot list active) that scan runs inside it (k_merge_shared.h scan_top) and the
@@ -109,6 +112,7 @@ class GpuCtx {
   unsigned long long index_builds = 0, word_rounds = 0, word_switch_round = 0, word_all_rounds = 0, word_fused_rounds = 0;  // K4 rounds whose worklist came from the pair index
   unsigned long long classb_word_rounds = 0;  // word-mode rounds that launched class-B tiles (before k_words)
   unsigned long long k3_radix = 0;            // 1: K3 of class A ran by radix partition (k_pairradix.hip)
+  unsigned long long index_radix_builds = 0;  // of index_builds: filled by radix partition of the postings (k_index.hip)
   unsigned long long front_end_chunks = 0;    // > 0: the corpus was taken in this many chunks (front_end_chunked)
   bool corpus_resident() const { return !chunked_; }  // false: only the distinct words' bytes are in HBM
   unsigned long long peak_device_bytes() const;       // high-water mark of the device memory pool since this context was made
@@ -292,7 +296,7 @@ class GpuCtx {
   unsigned int hot_target_words_ = 1u << 16, words_inline_max_ = 1u << 18, words_fuse_max_ = 1u << 30, word_hint_floor_ = 16384;
   unsigned int word_div_ = 200;    // switch when (merge sites of the last round) * word_div_ < (tokens a pass over the tiles streams)
   unsigned int word_min_tiles_ = 16384;
-  unsigned long long idx_agg_min_ = 16ull << 20, word_min_tokens_ = 48ull << 20;
+  unsigned long long idx_agg_min_ = 16ull << 20, idx_radix_min_ = 0, word_min_tokens_ = 48ull << 20;
   unsigned long long *d_wmeta_ = nullptr;
   GatherCtl *d_gather_ = nullptr;
   uint32_t *d_xyz_ = nullptr;      // a batch too large for BatchArgs, as (x, y, z) triples

@@ -96,19 +96,37 @@ void GpuCtx::build_index(uint32_t z_next) {
   launch_fill_u64(idx_.key, PT_EMPTY, want, strm());
   HIP_CHECK(hipMemsetAsync(idx_.cnt, 0, want * IDX_SHARDS * 4, strm()));
   HIP_CHECK(hipMemsetAsync(idx_.bloom, 0, ENC_BLOOM_WORDS * 4, strm()));
+  // The radix build (k_index.hip) wants 4 B per class-A token slot for the resolved adjacencies and, once the postings are counted, 8 B per
+  // posting for their records: it runs from idx_radix_min_ live tokens on and when all of that -- sized for a posting per token slot -- fits what
+  // is free with room to spare (as the radix K3 decides, gpu_pairs.cpp); else the streaming build.
+  const unsigned long long slots_n = (unsigned long long)c.n_tiles * c.slot;
+  const bool radix = word_live_tokens_ >= idx_radix_min_ && idx_radix_takes(idx_.mask, c.n_tiles) &&
+                     12ull * slots_n + 4ull * idx_radix_scratch_u32() + (64ull << 20) <= free_device_bytes() / 4 * 3;
+  DevScope scope;  // (a thrown GpuError leaks none of the build's transient buffers)
+  uint32_t *rx_scratch = nullptr, *rx_slots = nullptr;
+  unsigned long long *rx_rec = nullptr;
+  scope.hold(rx_scratch); scope.hold(rx_slots); scope.hold(rx_rec);
   t_begin(KT_CAND);
   launch_idx_seed(pt_, idx_, listed, strm());
-  if (!idx_save_) idx_save_ = dmalloc<unsigned char>(idx_save_bytes());
-  launch_idx_stream(false, c.ts, idx_, strm(), true, idx_save_);
-  // offsets = exclusive scan of the counts (one extra zero count behind the last slot: off[mask + 1] = the total)
-  HIP_CHECK(hipMemsetAsync(idx_.cnt + want * IDX_SHARDS, 0, 4, strm()));
-  launch_exclusive_scan(idx_.cnt, want * IDX_SHARDS + 1, idx_.off, idx_scan_tmp_, d_counters_ + 56, strm());
-  HIP_CHECK(hipMemsetAsync(idx_.cnt, 0, want * IDX_SHARDS * 4, strm()));  // the fill pass's cursors
   unsigned long long total = 0;
-  HIP_CHECK(hipMemcpyAsync(&total, d_counters_ + 56, 8, hipMemcpyDeviceToHost, strm()));
+  if (radix) {
+    rx_scratch = dmalloc<uint32_t>(idx_radix_scratch_u32());
+    rx_slots = dmalloc<uint32_t>(slots_n);
+    HIP_CHECK(hipMemsetAsync(rx_scratch, 0, idx_radix_scratch_head_bytes(), strm()));
+    launch_idx_radix_sweep(c.ts, idx_, rx_scratch, rx_slots, strm());
+    HIP_CHECK(hipMemcpyAsync(&total, rx_scratch, 8, hipMemcpyDeviceToHost, strm()));
+  } else {
+    if (!idx_save_) idx_save_ = dmalloc<unsigned char>(idx_save_bytes());
+    launch_idx_stream(false, c.ts, idx_, strm(), true, idx_save_);
+    // offsets = exclusive scan of the counts (one extra zero count behind the last slot: off[mask + 1] = the total)
+    HIP_CHECK(hipMemsetAsync(idx_.cnt + want * IDX_SHARDS, 0, 4, strm()));
+    launch_exclusive_scan(idx_.cnt, want * IDX_SHARDS + 1, idx_.off, idx_scan_tmp_, d_counters_ + 56, strm());
+    HIP_CHECK(hipMemsetAsync(idx_.cnt, 0, want * IDX_SHARDS * 4, strm()));  // the fill pass's cursors
+    HIP_CHECK(hipMemcpyAsync(&total, d_counters_ + 56, 8, hipMemcpyDeviceToHost, strm()));
+  }
   sync();
   index_builds++;
-  if (cfg_->trace.set) fprintf(stderr, "[yttm] index build at round %llu: %u listed pairs, %llu postings, %u tiles, last round touched %llu tiles\n", merge_rounds, listed, total, c.n_tiles, touched_last_);
+  if (cfg_->trace.set) fprintf(stderr, "[yttm] index build at round %llu: %u listed pairs, %llu postings, %u tiles, last round touched %llu tiles%s\n", merge_rounds, listed, total, c.n_tiles, touched_last_, radix ? " (radix)" : "");
   if (total == 0 || total > 0xfffffff0ull) {  // (no postings, or more than the 32-bit run offsets hold: the rounds take every word)
     t_end(KT_CAND, 4ull * c.n_tiles * c.nom);
     return;
@@ -118,7 +136,18 @@ void GpuCtx::build_index(uint32_t z_next) {
     post_cap_ = total + total / 4 + 1024;
     idx_.post = dmalloc<uint32_t>(post_cap_);
   }
-  launch_idx_stream(true, c.ts, idx_, strm(), /*agg=*/total > idx_agg_min_, idx_save_);
+  if (radix) {
+    rx_rec = dmalloc<unsigned long long>(total);
+    launch_idx_radix_scatter(c.ts, idx_, rx_scratch, rx_slots, rx_rec, total, strm());
+    // (all of a key's postings are counted in its shard 0: the run bounds off[s * IDX_SHARDS] come out of the same scan)
+    HIP_CHECK(hipMemsetAsync(idx_.cnt + want * IDX_SHARDS, 0, 4, strm()));
+    launch_exclusive_scan(idx_.cnt, want * IDX_SHARDS + 1, idx_.off, idx_scan_tmp_, d_counters_ + 56, strm());
+    HIP_CHECK(hipMemsetAsync(idx_.cnt, 0, want * IDX_SHARDS * 4, strm()));  // the place pass's cursors
+    launch_idx_radix_place(idx_, rx_scratch, rx_rec, total, strm());
+    index_radix_builds++;
+  } else {
+    launch_idx_stream(true, c.ts, idx_, strm(), /*agg=*/total > idx_agg_min_, idx_save_);
+  }
   t_end(KT_CAND, 8ull * c.n_tiles * c.nom);
   const unsigned long long stamps = c.n_unique;  // (a posting is a word, and a round claims words)
   if (stamps > stamp_cap_) {
@@ -134,6 +163,26 @@ void GpuCtx::build_index(uint32_t z_next) {
   }
   idx_valid_ = true;
   idx_zbuild_ = z_next;
+}
+
+void GpuCtx::download_index(std::vector<unsigned long long> &keys, std::vector<unsigned long long> &lo, std::vector<unsigned long long> &hi, std::vector<uint32_t> &post) {
+  if (fused_pending_) throw GpuError{"download_index: a candidate scan rides in the last merge round -- call candidates first"};
+  keys.clear(); lo.clear(); hi.clear(); post.clear();
+  if (!idx_valid_) return;
+  const size_t slots = (size_t)idx_.mask + 1;
+  std::vector<unsigned long long> k(slots), off(slots * IDX_SHARDS + 1);
+  HIP_CHECK(hipMemcpyAsync(k.data(), idx_.key, slots * 8, hipMemcpyDeviceToHost, strm()));
+  HIP_CHECK(hipMemcpyAsync(off.data(), idx_.off, off.size() * 8, hipMemcpyDeviceToHost, strm()));
+  sync();
+  post.resize(off.back());
+  if (!post.empty()) HIP_CHECK(hipMemcpyAsync(post.data(), idx_.post, post.size() * 4, hipMemcpyDeviceToHost, strm()));
+  sync();
+  for (size_t s = 0; s < slots; s++) {
+    if (k[s] == PT_EMPTY) continue;
+    keys.push_back(k[s]);
+    lo.push_back(off[s * IDX_SHARDS]);
+    hi.push_back(off[(s + 1) * IDX_SHARDS]);
+  }
 }
 
 }  // namespace yttm

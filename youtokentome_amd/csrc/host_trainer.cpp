@@ -362,6 +362,7 @@ Status learn_bpe(GpuCtx &g, int vocab_size, const std::string &model_path, const
     rep->peak_device_bytes = g.peak_device_bytes();
     rep->top_refills = g.top_refills;
     rep->index_builds = g.index_builds;
+    rep->index_radix_builds = g.index_radix_builds;
     rep->word_rounds = g.word_rounds;
     rep->word_switch_round = g.word_switch_round;
     rep->word_all_rounds = g.word_all_rounds;

@@ -80,6 +80,7 @@ struct Hook {
   X(words_inline_max, "YTTM_WORDS_INLINE_MAX", "262144", "tune", "rounds of at most this many words apply their records themselves")       \
   X(words_fuse_max, "YTTM_WORDS_FUSE_MAX", "1073741824", "path", "rounds of at most this many words are ONE launch (0: never)")            \
   X(index_agg_min, "YTTM_INDEX_AGG_MIN", "16777216", "tune", "index fill pass: postings from which a workgroup sums per key in LDS first") \
+  X(index_radix_min, "YTTM_INDEX_RADIX_MIN", "1048576", "path", "pair index: class-A live tokens from which it is built by radix partition of its postings (0: always; huge: never)") \
   X(word_drec, "YTTM_WORD_DREC", "32768", "test", "records per workgroup region of k_words (tests: overflow)")                              \
   X(word_log, "YTTM_WORD_LOG", "0", "test", "capacity of the instance-record log (tests: overflow; 0: sized from the tokens)")             \
   X(wgather_grid, "YTTM_WGATHER_GRID", "", "test", "grid of k_wgather")                                                                      \

@@ -206,6 +206,17 @@ void launch_idx_stream(bool fill, const TileSet &ts, const PairIndexArgs &a, hip
                        bool agg = true /* fill pass: sum a workgroup's postings per key in LDS first (worth a second sweep only when they are many) */,
                        void *save = nullptr /* [idx_save_bytes()] the count pass's per-workgroup tables, reused by an agg fill pass */);
 size_t idx_save_bytes();
+// The same index by radix partition of its postings (k_index.hip): sweep (adjacency -> slot, records per level-1 group; the posting total lands in
+// scratch[0..1] as a uint64) -> scatter (records to their groups, counts per slot into a.cnt) -> [exclusive scan of a.cnt, cursors cleared] -> place.
+// scratch: idx_radix_scratch_u32() words, the first idx_radix_scratch_head_bytes() zeroed; slots: one word per class-A token slot; rec: one
+// 8-byte record per posting.  idx_radix_takes: the index and the tile set are of a size the path is laid out for.
+size_t idx_radix_scratch_u32();
+size_t idx_radix_scratch_head_bytes();
+bool idx_radix_takes(unsigned int mask, unsigned int n_tiles);
+void launch_idx_radix_sweep(const TileSet &ts, const PairIndexArgs &a, uint32_t *scratch, uint32_t *slots, hipStream_t st);
+void launch_idx_radix_scatter(const TileSet &ts, const PairIndexArgs &a, const uint32_t *scratch, const uint32_t *slots, unsigned long long *rec,
+                              unsigned long long total, hipStream_t st);
+void launch_idx_radix_place(const PairIndexArgs &a, const uint32_t *scratch, const unsigned long long *rec, unsigned long long total, hipStream_t st);
 // ---- word mode (k_words.hip)
 void launch_words_init(const TileSet &ts, unsigned long long *wmeta, hipStream_t st);
 struct WGatherArgs {  // (a kernel argument of k_wgather and k_words<FUSED>)
