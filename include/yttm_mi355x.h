@@ -208,6 +208,34 @@ int yttm_spans_copy_padded(yttm_encoder *enc, void *d_matrix, uint64_t n_sent, u
 int yttm_encode_as_ids_spans(yttm_encoder *enc, const uint8_t *bytes, const uint64_t *offsets, uint64_t n_sent, int bos, int eos, int reverse,
                              double dropout_prob, int32_t **ids, uint64_t **out_offsets, uint32_t **spans, char *err, int errlen);
 
+/* Token frequencies on the device: for n_bins > 0 the result is uint64 counts[n_bins + 1]; counts[v] = the number of ids equal to v for
+ * 0 <= v < n_bins, counts[n_bins] = the number of ids outside [0, n_bins) -- negative ids (a parsed id file can hold them), ids >= n_bins,
+ * INT32_MIN, INT32_MAX.  No id is an error, and sum(counts) = the number of ids counted, always.  n_bins == 0 means yttm_vocab_size(enc); the
+ * largest n_bins is 2^31 (code 1 beyond).  The counts live in a slot of their own inside the encoder: no later encode, decode, parse or file call
+ * empties it.  accumulate == 0 zeroes the slot before counting; accumulate != 0 adds on top and requires the slot's n_bins to match (else code 1
+ * and nothing is changed; on an encoder that has not counted yet it starts from zero).  Counting never changes or consumes what it counts: a
+ * pending encode result is still pending afterwards and fetches the same bytes.  Made in one pass (k_idcount.h) that reads every id once and
+ * writes nothing per id; integer sums, so the result is exact whatever the order.
+ * yttm_id_counts_device counts the pending encode result, whichever call left it (yttm_encode_device, yttm_encode_text_device,
+ * yttm_ids_parse_device, yttm_spans_device, ...); n_sent must be the pending result's, as for yttm_idtext_device.  No pending result: code 1, and
+ * nothing pending or counted is changed.  *n_counted (optional): the ids counted by this call. */
+int yttm_id_counts_device(yttm_encoder *enc, uint64_t n_sent, uint64_t n_bins, int accumulate, uint64_t *n_counted, double *kernel_ms, char *err,
+                          int errlen);
+/* ... any int32 ids[n_ids] in HBM (4-byte aligned; the caller synchronises the stream that wrote it first, as for yttm_decode_device).
+ * n_ids == 0 is legal. */
+int yttm_id_counts_ids_device(yttm_encoder *enc, const void *d_ids, uint64_t n_ids, uint64_t n_bins, int accumulate, double *kernel_ms, char *err,
+                              int errlen);
+/* The counts, n_bins + 1 values: to a host array, or to device memory the caller owns.  n_bins must be the slot's (0 = vocab size); no counts
+ * yet: code 1. */
+int yttm_id_counts_fetch(yttm_encoder *enc, uint64_t *counts, uint64_t n_bins, char *err, int errlen);
+int yttm_id_counts_copy_device(yttm_encoder *enc, void *d_counts, uint64_t n_bins, char *err, int errlen);
+/* The pipeline of yttm_encode_file (upload of one piece beside split + encode + count of the one before) with no download leg but the final
+ * vocab_size + 1 integers, written to the caller's counts[vocab_size + 1].  The same file errors and messages as yttm_encode_file, the same
+ * <BOS> / <EOS> messages; with dropout_prob == 0 the counts never depend on chunk_bytes.  It uses both lanes, so a pending device result does not
+ * survive it; the counts slot afterwards holds the file's counts.  The report's keys are those of yttm_encode_file plus "seconds_count". */
+int yttm_encode_file_counts(yttm_encoder *enc, const char *path, int bos, int eos, int reverse, double dropout_prob, uint64_t chunk_bytes,
+                            uint64_t *counts, uint64_t *n_lines, uint64_t *n_ids, char *report_json, int report_len, char *err, int errlen);
+
 /* Word-level encode cache (SURVEY.md 8f "N4"; the reference has no counterpart: bpe.cpp:1497-1632 encodes every word occurrence).
  * mode 0: every batch goes straight through the encode kernel; 1: distinct words are encoded once whenever that is possible
  * (dropout_prob == 0); 2 (default): the same for batches of at least min_bytes.  The ids are identical either way.

@@ -53,6 +53,8 @@ def kernels(build):
                 if m:
                     cur = m.group(1)
                     res[cur] = ([], meta.get(cur))
+                elif cur and line.strip() == "...":
+                    continue  # (objdump's mark for the zero padding between two functions: present behind a kernel once another follows it)
                 elif cur and line.strip():
                     text = re.sub(r"\s*//.*$", "", line).strip().replace(cur, "SELF")
                     at = re.search(r"//\s*([0-9A-Fa-f]+):", line)

@@ -27,6 +27,7 @@ EXPORTS = [
     "yttm_subword_device", "yttm_subword_text_device", "yttm_encode_file_subword",
     "yttm_ids_parse_device", "yttm_decode_text_device", "yttm_decode_file", "yttm_idtext_device", "yttm_encode_file_idtext",
     "yttm_spans_device", "yttm_spans_text_device", "yttm_spans_fetch", "yttm_spans_copy_device", "yttm_spans_copy_padded", "yttm_encode_as_ids_spans",
+    "yttm_id_counts_device", "yttm_id_counts_ids_device", "yttm_id_counts_fetch", "yttm_id_counts_copy_device", "yttm_encode_file_counts",
     "yttm_device_info", "yttm_comm_rccl_unique_id", "yttm_comm_rccl_create", "yttm_comm_callback_create",
     "yttm_comm_destroy", "yttm_train_bpe_comm", "yttm_train_bpe_from_device_comm", "yttm_train_bpe_from_memory_comm",
     # include/yttm_gpu.h
@@ -88,6 +89,11 @@ def load():
     L.yttm_spans_copy_device.argtypes = [cvp, cvp, C.c_uint64, cs, ci]
     L.yttm_spans_copy_padded.argtypes = [cvp, cvp, C.c_uint64, C.c_uint64, u64p, cs, ci]
     L.yttm_encode_as_ids_spans.argtypes = [cvp, cs, u64p, C.c_uint64, ci, ci, ci, cd, C.POINTER(i32p), C.POINTER(u64p), C.POINTER(u32p), cs, ci]
+    L.yttm_id_counts_device.argtypes = [cvp, C.c_uint64, C.c_uint64, ci, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_id_counts_ids_device.argtypes = [cvp, cvp, C.c_uint64, C.c_uint64, ci, C.POINTER(cd), cs, ci]
+    L.yttm_id_counts_fetch.argtypes = [cvp, u64p, C.c_uint64, cs, ci]
+    L.yttm_id_counts_copy_device.argtypes = [cvp, cvp, C.c_uint64, cs, ci]
+    L.yttm_encode_file_counts.argtypes = [cvp, cs, ci, ci, ci, cd, C.c_uint64, u64p, u64p, u64p, cs, ci, cs, ci]
     L.yttm_encoder_set_cache.argtypes = [cvp, ci, C.c_uint64]
     L.yttm_encode_cache_words.argtypes = [cvp]
     L.yttm_encode_cache_words.restype = C.c_uint64

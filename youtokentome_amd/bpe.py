@@ -318,6 +318,47 @@ class _Core:
         spans_a = _take(spans, 2 * int(off_a[-1]), C.c_uint32, np.uint32).reshape(-1, 2)
         return ids_a, off_a, spans_a
 
+    # ---- token frequencies on the device (include/yttm_mi355x.h): uint64 counts[n_bins + 1] in a slot of the encoder's own, the last one the ids
+    # outside [0, n_bins); n_bins = 0: the vocabulary's size
+    def id_counts_device_raw(self, n_sent, n_bins=0, accumulate=False):
+        """counts the pending encode result of n_sent sentences -> (n_counted, kernel_ms); the result stays pending"""
+        nc, ms, err = C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_id_counts_device(self._h, n_sent, int(n_bins), int(bool(accumulate)), C.byref(nc), C.byref(ms), err, _lib.ERRLEN), err)
+        return nc.value, ms.value
+
+    def id_counts_ids_device_raw(self, d_ids, n_ids, n_bins=0, accumulate=False):
+        """counts int32 ids[n_ids] in device memory -> kernel_ms"""
+        ms, err = C.c_double(), _err()
+        self._check(_lib.load().yttm_id_counts_ids_device(self._h, C.c_void_p(d_ids), n_ids, int(n_bins), int(bool(accumulate)), C.byref(ms), err,
+                                                          _lib.ERRLEN), err)
+        return ms.value
+
+    def fetch_id_counts(self, n_bins=0):
+        """the counts -> np.uint64 [n_bins + 1]"""
+        counts, err = np.zeros(int(n_bins or self.vocab_size()) + 1, np.uint64), _err()
+        self._check(_lib.load().yttm_id_counts_fetch(self._h, counts.ctypes.data_as(_lib.u64p), int(n_bins), err, _lib.ERRLEN), err)
+        return counts
+
+    def copy_id_counts_device(self, d_counts, n_bins=0):
+        err = _err()
+        self._check(_lib.load().yttm_id_counts_copy_device(self._h, C.c_void_p(d_counts), int(n_bins), err, _lib.ERRLEN), err)
+
+    def encode_file_counts(self, path, bos=False, eos=False, reverse=False, dropout_prob=0.0, chunk_bytes=None, report=False):
+        """a text file -> np.uint64 counts[vocab_size + 1] of its ids (and with report=True the call's report, a dict); report["lines"] and
+        report["ids"] are the file's"""
+        _check_dropout(dropout_prob)
+        counts = np.zeros(self.vocab_size() + 1, np.uint64)
+        nl, ni, err = C.c_uint64(), C.c_uint64(), _err()
+        rep = C.create_string_buffer(1024)
+        rc = _lib.load().yttm_encode_file_counts(self._h, os.fsencode(path), int(bos), int(eos), int(reverse), float(dropout_prob), int(chunk_bytes or 0),
+                                                 counts.ctypes.data_as(_lib.u64p), C.byref(nl), C.byref(ni), rep, len(rep), err, _lib.ERRLEN)
+        if rc != 0:
+            raise ValueError(err.value.decode(errors="replace"))
+        if report:
+            import json
+            return counts, json.loads(rep.value.decode())
+        return counts
+
     # ---- decimal id text on the device (include/yttm_mi355x.h): the format `yttm encode --output_type id` prints and `yttm decode` reads
     def ids_parse_device_raw(self, d_text, n_bytes):
         """-> (n_lines, n_ids, kernel_ms); the ids `while (ss >> x)` reads from every line are pending as after encode_device_raw with n_sent = n_lines"""
@@ -603,6 +644,22 @@ class BPE:
             spans = lead[spans + base[:, None]] - lead[base][:, None]
         o, ids_l, sp_l = off.tolist(), ids.tolist(), spans.tolist()
         return ([ids_l[o[i]:o[i + 1]] for i in range(len(sentences))], [[tuple(p) for p in sp_l[o[i]:o[i + 1]]] for i in range(len(sentences))])
+
+    # ---- how often every token is used (include/yttm_mi355x.h "Token frequencies"; the reference has no counterpart)
+    def id_counts_tensor(self, ids=None, n_bins: Optional[int] = None, accumulate: bool = False):
+        """Token frequencies made on the device -> an int64 tensor [n_bins + 1] on the encoder's device (the library's uint64 values viewed as int64,
+        as the offsets tensors are): entry v the ids equal to v, the last entry the ids outside [0, n_bins).  n_bins=None: the vocabulary's size.
+        ids=None counts the pending result of the last *_tensor encode or parse call, which stays pending; else `ids` is an int32 CUDA tensor of
+        any shape, contiguous, counted flat (a padded matrix counts its pad values too).  accumulate=True adds to the counts of the calls before."""
+        from . import tensor
+        return tensor.id_counts_tensor(self, ids=ids, n_bins=n_bins, accumulate=accumulate)
+
+    def count_file(self, path, bos: bool = False, eos: bool = False, reverse: bool = False, dropout_prob: float = 0, chunk_bytes: Optional[int] = None,
+                   report: bool = False):
+        """A text file, one sentence per line -> np.uint64 counts [vocab_size + 1] of the ids encode_file gives for it, counted on the device piece by
+        piece: only the counts come down.  The last entry counts ids outside the vocabulary (0 for an encode).  report=True: (counts, the call's
+        report as a dict).  Needs no torch."""
+        return self.bpe_cython.encode_file_counts(path, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, chunk_bytes=chunk_bytes, report=report)
 
     # ---- decimal id text, one sentence per line: the format `yttm encode --output_type id` prints and `yttm decode` reads
     def decode_file(self, path, out: str, ignore_ids: Optional[Collection] = None, chunk_bytes: Optional[int] = None, report: bool = False):

@@ -352,6 +352,32 @@ int yttm_encode_as_ids_spans(yttm_encoder *h, const uint8_t *bytes, const uint64
   return 0;
 }
 
+int yttm_id_counts_device(yttm_encoder *h, uint64_t n_sent, uint64_t n_bins, int accumulate, uint64_t *n_counted, double *kernel_ms, char *err, int errlen) {
+  unsigned long long nc = 0;
+  Status s = h->enc->id_counts_device(n_sent, n_bins, accumulate != 0, &nc, kernel_ms);
+  if (n_counted) *n_counted = nc;
+  return finish(s, err, errlen);
+}
+int yttm_id_counts_ids_device(yttm_encoder *h, const void *d_ids, uint64_t n_ids, uint64_t n_bins, int accumulate, double *kernel_ms, char *err, int errlen) {
+  return finish(h->enc->id_counts_ids_device(d_ids, n_ids, n_bins, accumulate != 0, kernel_ms), err, errlen);
+}
+int yttm_id_counts_fetch(yttm_encoder *h, uint64_t *counts, uint64_t n_bins, char *err, int errlen) {
+  return finish(h->enc->take_id_counts(counts, n_bins, false), err, errlen);
+}
+int yttm_id_counts_copy_device(yttm_encoder *h, void *d_counts, uint64_t n_bins, char *err, int errlen) {
+  return finish(h->enc->take_id_counts(d_counts, n_bins, true), err, errlen);
+}
+int yttm_encode_file_counts(yttm_encoder *h, const char *path, int bos, int eos, int reverse, double dropout_prob, uint64_t chunk_bytes, uint64_t *counts,
+                            uint64_t *n_lines, uint64_t *n_ids, char *report_json, int report_len, char *err, int errlen) {
+  unsigned long long nl = 0, ni = 0;
+  std::string report;
+  Status s = h->enc->encode_file_counts(path ? path : "", bos, eos, reverse, dropout_prob, chunk_bytes, (unsigned long long *)counts, &nl, &ni, &report);
+  if (n_lines) *n_lines = nl;
+  if (n_ids) *n_ids = ni;
+  if (s.ok() && report_json && report_len > 0) snprintf(report_json, (size_t)report_len, "%s", report.c_str());
+  return finish(s, err, errlen);
+}
+
 int yttm_encoder_set_cache(yttm_encoder *h, int mode, uint64_t min_bytes) {
   h->enc->set_cache(mode, min_bytes);
   return 0;

@@ -60,6 +60,7 @@ struct EncodeLane {
     DevBuf<int32_t> ids;
     DevBuf<unsigned long long> off, misc;  // misc[0]: longest row (k_enc_longest)
     unsigned long long n_ids = 0, n_sent = 0;
+    bool made = false;  // an encode or a parse has left a result here (n_sent == 0 is a result too)
   } res;
   struct {  // word cache (k_wcache.hip): the batch's table of distinct words, the slot of every occurrence, the list K5 encodes, its ids
     DevBuf<unsigned long long> slot, pos, extra, blk_off, ustart, uend;
@@ -129,6 +130,13 @@ struct EncoderDevice {
   DevBuf<uint8_t> sub_blob;
   DevBuf<uint32_t> sub_off;
   DevBuf<uint32_t> sub_units;  // [vocab] the units an id covers (k_spans.h), filled beside the pieces
+  // token frequencies (host_decode.cpp, k_idcount.h): uint64 [n_bins + 1], the encoder's own and no lane's -- no encode, decode, parse or file
+  // call empties it.  Read and written under lane 0's mutex, which every entry that counts or takes the counts holds.
+  struct {
+    DevBuf<unsigned long long> counts;
+    unsigned long long n_bins = 0;
+    bool valid = false;
+  } idc;
   // a free lane, locked (falls back to waiting for the caller's turn-based choice)
   // (Lane 0 last: the device-resident pair encode_device / fetch_device_result keeps its result there, unlocked, between the two
   // calls -- a host-to-host encode from another thread in between takes another lane while one is free.)
@@ -238,6 +246,11 @@ Status decode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, i
                       const int32_t *ignore_ids, unsigned long long n_ignore, unsigned long long *n_bytes, double *kernel_ms, bool newline);
 // The decimal text of the encode result pending on the lane (locked by the caller), left in the lane's text slot (k_idtext.h)
 Status idtext_on_lane(EncodeLane &d, int device, unsigned long long *n_text_bytes, double *kernel_ms);
+
+// ids[n_ids] in HBM counted into the encoder's counts slot (D.idc; lane 0 locked by the caller) on lane d's stream, which is synchronised
+// (k_idcount.h).  n_bins: 1 .. 2^31.  accumulate on a slot of another n_bins: code 1 before anything is changed; on an empty slot it starts from 0.
+Status count_on_lane(EncoderDevice &D, EncodeLane &d, int device, const int32_t *d_ids, unsigned long long n_ids, unsigned long long n_bins, bool accumulate,
+                     double *kernel_ms);
 
 // The two-pass sequence of a kernel family that measures, then writes (k_decode.h, k_subword.h, k_idtext.h), on the lane (locked by the caller,
 // on its device): launch(false) leaves n counts, scan_counts turns them into off[n + 1] and synchronises, check() may end the call there with

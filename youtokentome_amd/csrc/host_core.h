@@ -177,6 +177,15 @@ class BaseEncoder {  // bpe.h:22-82
   Status copy_spans_padded(void *d_matrix, unsigned long long n_sent, unsigned long long width, unsigned long long *longest) const;  // [n_sent, width, 2]
   Status encode_as_ids_spans(const uint8_t *bytes, const unsigned long long *offsets, unsigned long long n_sent, bool bos, bool eos, bool reverse,
                              double dropout_prob, int32_t **ids, unsigned long long **out_off, uint32_t **spans) const;  // host to host, free()
+  // Token frequencies on the device (host_decode.cpp, host_lines.cpp, k_idcount.h): uint64 counts[n_bins + 1] (n_bins == 0: vocab_size()) of the
+  // pending encode result or of any int32 array in HBM, in a slot of the encoder's own that only a count changes; counts[n_bins] holds the ids
+  // outside [0, n_bins).  What is counted is only read: a pending result stays pending.  encode_file_counts: the pipeline of encode_file with the
+  // count in place of the download; the caller's counts[vocab_size() + 1] is all that comes down.
+  Status id_counts_device(unsigned long long n_sent, unsigned long long n_bins, bool accumulate, unsigned long long *n_counted, double *kernel_ms) const;
+  Status id_counts_ids_device(const void *d_ids, unsigned long long n_ids, unsigned long long n_bins, bool accumulate, double *kernel_ms) const;
+  Status take_id_counts(void *counts, unsigned long long n_bins, bool to_device) const;  // [n_bins + 1]: to a host array or device to device
+  Status encode_file_counts(const std::string &path, bool bos, bool eos, bool reverse, double dropout_prob, unsigned long long piece_bytes,
+                            unsigned long long *counts, unsigned long long *n_lines, unsigned long long *n_ids, std::string *report) const;
   // the YTTM_* hooks as they stood when THIS encoder was made: every entry point binds them to its thread (yttm_config.h CfgBind), so that a
   // later encoder or training never changes the paths of this one
   std::shared_ptr<const Config> config() const;

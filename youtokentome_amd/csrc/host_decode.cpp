@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "enc_lanes.h"
+#include "idcount_plan.h"
 
 namespace yttm {
 
@@ -284,6 +285,72 @@ Status BaseEncoder::idtext_device(unsigned long long n_sent, unsigned long long 
   EncodeLane &d = l.d;
   if (n_sent != d.res.n_sent) return Status(1, "idtext_device: no matching encode result");  // (before any work: a pending text stays)
   return idtext_on_lane(d, device_, n_text_bytes, ms.next());
+}
+
+// ---- token frequencies (k_idcount.h) -------------------------------------------------------------------------------------------------------
+// uint64 counts[n_bins + 1] of an id array in HBM, in the encoder's own slot (EncoderDevice::idc): counts[v] the ids equal to v, the last one the
+// ids outside [0, n_bins).  One pass that writes nothing per id; what it counts is only read.
+Status count_on_lane(EncoderDevice &D, EncodeLane &d, int device, const int32_t *d_ids, unsigned long long n_ids, unsigned long long n_bins, bool accumulate,
+                     double *kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  if (n_bins == 0 || n_bins > IDC_BINS_MAX) return Status(1, "id_counts: n_bins must be within 1 .. 2^31");
+  const bool fresh = !accumulate || !D.idc.valid;
+  if (!fresh && D.idc.n_bins != n_bins)
+    return Status(1, "id_counts: accumulate needs the n_bins of the counts so far (" + std::to_string(D.idc.n_bins) + ", not " + std::to_string(n_bins) + ")");
+  if (n_ids && !d_ids) return Status(2, "id_counts: no ids");
+  return on_device(device, [&]() -> Status {
+    EventPair ev(d.st, kernel_ms != nullptr);
+    if (fresh) {
+      D.idc.valid = false;
+      D.idc.counts.grow((size_t)n_bins + 1);
+      D.idc.n_bins = n_bins;
+    }
+    ev.start();
+    if (fresh) HIP_CHECK(hipMemsetAsync(D.idc.counts, 0, ((size_t)n_bins + 1) * 8, d.st));
+    launch_idcount(d_ids, n_ids, n_bins, D.idc.counts, d.st);
+    ev.stop();
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    if (kernel_ms) *kernel_ms = ev.elapsed_ms();
+    D.idc.valid = true;
+    return Status();
+  });
+}
+
+Status BaseEncoder::id_counts_device(unsigned long long n_sent, unsigned long long n_bins, bool accumulate, unsigned long long *n_counted,
+                                     double *kernel_ms) const {
+  if (n_counted) *n_counted = 0;
+  StageClock ms(kernel_ms);
+  if (!dev_) return Status(1, "id_counts_device: no matching encode result");
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
+  if (!d.res.made || n_sent != d.res.n_sent) return Status(1, "id_counts_device: no matching encode result");  // (before any work: the counts stay)
+  const Status s = count_on_lane(*dev_, d, device_, d.res.ids, d.res.n_ids, n_bins ? n_bins : (unsigned long long)vocab_size(), accumulate, ms.next());
+  if (s.ok() && n_counted) *n_counted = d.res.n_ids;
+  return s;
+}
+
+Status BaseEncoder::id_counts_ids_device(const void *d_ids, unsigned long long n_ids, unsigned long long n_bins, bool accumulate, double *kernel_ms) const {
+  StageClock ms(kernel_ms);
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (((uintptr_t)d_ids & 3u) != 0) return Status(2, "id_counts_ids_device: the ids must be 4-byte aligned");
+  const Lane0 l(*dev_);
+  return count_on_lane(*dev_, l.d, device_, (const int32_t *)d_ids, n_ids, n_bins ? n_bins : (unsigned long long)vocab_size(), accumulate, ms.next());
+}
+
+Status BaseEncoder::take_id_counts(void *counts, unsigned long long n_bins, bool to_device) const {
+  const char *who = to_device ? "copy_id_counts: no matching counts" : "fetch_id_counts: no matching counts";
+  if (!dev_) return Status(1, who);
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
+  if (!dev_->idc.valid || (n_bins ? n_bins : (unsigned long long)vocab_size()) != dev_->idc.n_bins) return Status(1, who);
+  if (!counts) return Status(2, "id_counts: no output");
+  const size_t bytes = ((size_t)dev_->idc.n_bins + 1) * 8;
+  return on_device(device_, [&]() -> Status {
+    if (to_device) HIP_CHECK(hipMemcpyAsync(counts, dev_->idc.counts, bytes, hipMemcpyDeviceToDevice, d.st));
+    else copy_down(device_, counts, dev_->idc.counts, bytes, d.st);
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    return Status();
+  });
 }
 
 Status BaseEncoder::subword_device(const void *d_bytes, const void *d_offsets, unsigned long long n_sent, unsigned long long total_bytes,

@@ -280,6 +280,7 @@ Status encode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, i
   return on_device(device, [&]() -> Status {
     d.res.n_sent = n_sent;
     d.res.n_ids = 0;
+    d.res.made = true;
     d.sp.valid = false;  // (spans belong to the ids they were made from)
     if (n_ids_out) *n_ids_out = 0;
     if (n_sent == 0) return Status();

@@ -163,6 +163,7 @@ static Status parse_on_lane(EncodeLane &d, int device, const void *d_text, unsig
     const unsigned long long n_lines = d.ln.n_lines;
     d.res.n_sent = n_lines;
     d.res.n_ids = 0;
+    d.res.made = true;
     d.sp.valid = false;  // (spans belong to the ids they were made from)
     if (n_ids_out) *n_ids_out = 0;
     if (kernel_ms) *kernel_ms = 0;
@@ -511,6 +512,66 @@ Status BaseEncoder::encode_file(const std::string &path, const char *out_prefix,
   if (n_lines_out) *n_lines_out = lines_total;
   if (n_ids_out) *n_ids_out = ids_total;
   if (report) *report = fp.report(n_pieces, lines_total, ids_total, nullptr, s_split, s_enc, {}, s_down);
+  return Status();
+}
+
+// ---- a text file to its token frequencies ------------------------------------------------------------------------------------------------
+// The same pipeline with no download leg: piece k is split, encoded and counted (k_idcount.h) into the encoder's counts slot while piece k + 1 is
+// read and uploaded; the slot is zeroed first and every piece adds to it -- `work` runs on one thread and ends synchronised, so the lanes never
+// add at once --, and counts[vocab_size + 1] is all that comes down.
+Status BaseEncoder::encode_file_counts(const std::string &path, bool bos, bool eos, bool reverse, double dropout_prob, unsigned long long piece_bytes,
+                                       unsigned long long *counts, unsigned long long *n_lines_out, unsigned long long *n_ids_out, std::string *report) const {
+  if (n_lines_out) *n_lines_out = 0;
+  if (n_ids_out) *n_ids_out = 0;
+  const Status tokens = check_bos_eos(*this, bos, eos);
+  if (!tokens.ok()) return tokens;
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (!counts) return Status(2, "encode_file_counts: no output");
+  FilePieces fp(path, dev_, device_, piece_bytes);
+  const Status opened = fp.open_input();
+  if (!opened.ok()) return opened;
+  const std::shared_ptr<const Config> C = dev_->cfg;
+  const CfgBind bind(C);
+  const int device = device_;
+  EncoderDevice *dev = dev_;
+  const unsigned long long n_bins = (unsigned long long)vocab_size();
+  std::lock_guard<std::mutex> lk0(dev->lane[0].mu), lk1(dev->lane[1].mu);  // (lane 0 first, always: nobody else waits for two lanes)
+
+  const Status zeroed = count_on_lane(*dev, dev->lane[0], device, nullptr, 0, n_bins, false, nullptr);  // (an empty file counts nothing into zeroes)
+  if (!zeroed.ok()) return zeroed;
+  double s_split = 0, s_enc = 0, s_count = 0;
+  unsigned long long lines_total = 0, ids_total = 0;
+  auto upload = [&](size_t i, bool *exhausted) { return fp.upload(i, exhausted); };
+  auto work = [&](size_t i) {
+    FilePieces::Piece &p = fp.piece[i & 1];
+    EncodeLane &d = dev->lane[i & 1];
+    const auto t0 = std::chrono::steady_clock::now();
+    Status st = encode_text_on_lane(*this, *dev, d, device, d.in.bytes, p.bytes, bos, eos, reverse, dropout_prob, &p.n_lines, &p.n_ids, &p.ms_split, nullptr);
+    if (st.ok()) st = count_on_lane(*dev, d, device, d.res.ids, p.n_ids, n_bins, true, &p.ms_a);
+    s_split += p.ms_split * 1e-3;
+    s_count += p.ms_a * 1e-3;
+    s_enc += secs_since(t0) - (p.ms_split + p.ms_a) * 1e-3;
+    return st;
+  };
+  auto download = [&](size_t i) {  // (nothing comes down: the piece's totals, in file order)
+    lines_total += fp.piece[i & 1].n_lines;
+    ids_total += fp.piece[i & 1].n_ids;
+    return Status();
+  };
+  size_t n_pieces = 0;
+  const Status piped = run_two_lanes("encode_file_counts", C, device, PIPE_UNTIL_EXHAUSTED, upload, work, download, &n_pieces);
+  if (!piped.ok()) return piped;
+  const auto t_down = std::chrono::steady_clock::now();
+  const Status down = on_device(device, [&]() -> Status {
+    EncodeLane &d = dev->lane[0];
+    copy_down(device, counts, dev->idc.counts, ((size_t)n_bins + 1) * 8, d.st);
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    return Status();
+  });
+  if (!down.ok()) return down;
+  if (n_lines_out) *n_lines_out = lines_total;
+  if (n_ids_out) *n_ids_out = ids_total;
+  if (report) *report = fp.report(n_pieces, lines_total, ids_total, nullptr, s_split, s_enc, {{"seconds_count", s_count}}, secs_since(t_down));
   return Status();
 }
 

@@ -21,7 +21,12 @@ struct Hook {
   const char *c_str() const { return set ? raw.c_str() : nullptr; }  // what getenv returned
 };
 
-// X(field, "NAME", default as text, kind, "what it does")        kind: test = exists for the test-suite; tune = a measured default, kept
+// The largest LDS window k_idcount is built with (idcount_plan.h, k_idcount.h), here because it is the default of its hook in the table below.
+#define YTTM_IDCOUNT_WINDOW_BUILT 32768
+#define YTTM_STR2(x) #x
+#define YTTM_STR(x) YTTM_STR2(x)
+
+// X(field, "NAME", default as text, kind, "what it does")       kind: test = exists for the test-suite; tune = a measured default, kept
 // adjustable for A/B runs; diag = diagnostics / tracing; path = selects a code path that must give the same result (differential tests)
 #define YTTM_HOOKS(X)                                                                                                                         \
   /* ---- diagnostics */                                                                                                                     \
@@ -110,7 +115,8 @@ struct Hook {
   X(enc_sub_mb, "YTTM_ENC_SUB_MB", "320", "tune", "host -> host encode: sub-batch size, MB")                                                \
   X(enc_sub_kb, "YTTM_ENC_SUB_KB", "", "test", "the same in KB")                                                                             \
   X(enc_pipe_from, "YTTM_ENC_PIPE_FROM", "536870912", "tune", "host -> host batches of at least this many bytes are pipelined in sub-batches") \
-  X(cli_batch_bytes, "YTTM_CLI_BATCH_BYTES", "0", "test", "`yttm encode` batch size in bytes (0: the reference's 10 MiB)")
+  X(cli_batch_bytes, "YTTM_CLI_BATCH_BYTES", "0", "test", "`yttm encode` batch size in bytes (0: the reference's 10 MiB)")                  \
+  X(idcount_window, "YTTM_IDCOUNT_WINDOW", YTTM_STR(YTTM_IDCOUNT_WINDOW_BUILT), "path", "id counts: bins a workgroup of k_idcount keeps in LDS (default: the largest built window; more clamps to it; 0: every id by global atomics)")
 
 struct Config {
 #define X(field, name, dflt, kind, doc) Hook field;

@@ -459,4 +459,9 @@ void launch_idparse(bool write, const uint8_t *text, const unsigned long long *l
 void launch_idprint(bool write, const int32_t *ids, const unsigned long long *ioff, unsigned long long n_sent, unsigned long long n_ids, uint32_t *out_len,
                     const unsigned long long *out_off, uint8_t *out, hipStream_t st);
 
+// ---- token frequencies (k_idcount.h, compiled with k_encode.hip): one pass, nothing written per id ----
+// counts[n_bins + 1] += the histogram of ids[n_ids]: counts[v] the ids equal to v, counts[n_bins] the ids outside [0, n_bins).  ids: any 4-byte
+// aligned address; 1 <= n_bins <= 2^31.  The caller zeroes counts where it does not accumulate.
+void launch_idcount(const int32_t *ids, unsigned long long n_ids, unsigned long long n_bins, unsigned long long *counts, hipStream_t st);
+
 }  // namespace yttm

@@ -1,5 +1,5 @@
 """Device tensors in, device tensors out: `BPE.encode_tensor` / `BPE.encode_text_tensor` / `BPE.text_lines_tensor` / `BPE.decode_tensor` /
-`BPE.encode_subword_tensor` / `BPE.encode_text_subword_tensor` / `BPE.encode_spans_tensor` / `BPE.encode_text_spans_tensor` / `BPE.decode_text_tensor` / `BPE.parse_ids_tensor` on top
+`BPE.encode_subword_tensor` / `BPE.encode_text_subword_tensor` / `BPE.encode_spans_tensor` / `BPE.encode_text_spans_tensor` / `BPE.decode_text_tensor` / `BPE.parse_ids_tensor` / `BPE.id_counts_tensor` on top
 of the raw device layer of `bpe._Core` (include/yttm_mi355x.h: yttm_encode_device, yttm_encode_text_device, yttm_lines_*, yttm_encode_copy_*,
 yttm_decode_device*, yttm_decode_copy_device).  torch is imported at call
 time; the rest of the package does not need it.
@@ -97,6 +97,7 @@ def encode_tensor(bpe, sentences, bos=False, eos=False, reverse=False, dropout_p
 
 def _take_encoded(torch, core, dev, n, n_ids, padded, width, pad_id):
     """the pending encode result of n sentences as tensors that torch owns"""
+    core.pending_n_sent = n  # (id_counts_tensor counts this result)
     if not padded:
         ids = torch.empty(n_ids, dtype=torch.int32, device=dev)
         out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
@@ -210,6 +211,7 @@ def encode_subword_tensor(bpe, sentences, bos=False, eos=False, reverse=False, d
     _check_dropout(dropout_prob)
     d_bytes, d_off, n, total, longest_in = _sentences_on(torch, sentences, dev)
     _, n_text, _ = _synced(torch, dev, core.subword_device_raw, d_bytes.data_ptr(), d_off.data_ptr(), n, total, longest_in, bos, eos, reverse, dropout_prob)
+    core.pending_n_sent = n
     return _take_text(torch, core, dev, n, n_text, as_str)
 
 
@@ -220,6 +222,7 @@ def encode_text_subword_tensor(bpe, text, bos=False, eos=False, reverse=False, d
     _check_dropout(dropout_prob)
     d_text, n_bytes = _text_on(torch, text, dev)
     n, _, n_text, _ = _synced(torch, dev, core.subword_text_device_raw, d_text.data_ptr(), n_bytes, bos, eos, reverse, dropout_prob)
+    core.pending_n_sent = n
     return _take_text(torch, core, dev, n, n_text, as_str)
 
 
@@ -274,6 +277,31 @@ def decode_text_tensor(bpe, text, ignore_ids=None, as_str=True):
     dev = _device_of(bpe, None)
     d_text, n_bytes = _text_on(torch, text, dev)
     n, _, n_text, _ = _synced(torch, dev, core.decode_text_device_raw, d_text.data_ptr(), n_bytes, ignore_ids)
+    core.pending_n_sent = n
     if as_str:
         return [s[:-1] for s in _take_text(torch, core, dev, n, n_text, True)]
     return _take_text(torch, core, dev, n, n_text, False)
+
+
+def id_counts_tensor(bpe, ids=None, n_bins=None, accumulate=False):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    n_bins = int(n_bins) if n_bins is not None else bpe.vocab_size()
+    if n_bins < 1:
+        raise ValueError("n_bins must be positive")
+    if ids is None:
+        n = getattr(core, "pending_n_sent", None)
+        if n is None:
+            raise ValueError("id_counts_tensor: no *_tensor encode or parse call has left a result to count")
+        _synced(torch, dev, core.id_counts_device_raw, n, n_bins, accumulate)
+    else:
+        if not hasattr(ids, "data_ptr") or ids.dtype != torch.int32:
+            raise ValueError("ids must be an int32 tensor")
+        _check_on(ids, dev, "ids")
+        if not ids.is_contiguous():
+            raise ValueError("ids must be contiguous")
+        _synced(torch, dev, core.id_counts_ids_device_raw, ids.data_ptr(), ids.numel(), n_bins, accumulate)
+    counts = torch.empty(n_bins + 1, dtype=torch.int64, device=dev)
+    _synced(torch, dev, core.copy_id_counts_device, counts.data_ptr(), n_bins)
+    return counts

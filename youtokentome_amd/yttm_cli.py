@@ -4,7 +4,8 @@ loops (bpe.cpp:1942-2028, utils.h:92-103).  Run as `python -m youtokentome_amd.y
 
 Two more commands work file to file through the device, with the same bytes as the streaming ones: `encode_file` (--output_type id: binary
 PREFIX.ids / PREFIX.off; subword and id_text: the text `encode --output_type subword` / `id` prints) and `decode_file` (a file of decimal ids
--> the text `decode` prints).
+-> the text `decode` prints).  `count_file` prints how often a text file uses every token, counted on the device: the lines of `vocab` with a
+third column.
 
 The loops themselves are C++ (youtokentome_amd/csrc/host_cli.cpp, behind yttm_encode_cli / yttm_decode_cli / yttm_vocab_cli):
 stdin and stdout stay bytes end to end, invalid UTF-8 included."""
@@ -106,6 +107,30 @@ def decode_file(model, input_path, output, ignore_ids):
     """Decode a text file of ids to a text file."""
     core = _Core(model)
     core.decode_file(input_path, output, ignore_ids=ignore_ids)  # the C++ pipeline: yttm_decode_file (host_lines.cpp)
+
+
+@main.command(name="count_file")
+@click.option("--model", type=click.Path(exists=True), required=True, help="Path to file with learned model.")
+@click.option("--input", "input_path", type=click.Path(exists=True, dir_okay=False), required=True, help="Text file, one sentence per line.")
+@click.option("--output", type=click.Path(), required=False, help="The file to write (default: stdout).")
+@click.option("--bos", is_flag=True, help="Add tab begin of sentence.")
+@click.option("--eos", is_flag=True, help="Add tab end of sentence.")
+@click.option("--dropout_prob", type=click.FLOAT, default=0, show_default=True,
+              help="BPE-dropout probability (the probability of a merge being dropped)")
+def count_file(model, input_path, output, bos, eos, dropout_prob):
+    """Print how often the file uses every token: id<TAB>subword<TAB>count, in id order."""
+    import sys
+    core = _Core(model)
+    counts = core.encode_file_counts(input_path, bos=bos, eos=eos, dropout_prob=dropout_prob)  # the C++ pipeline: yttm_encode_file_counts (host_lines.cpp)
+    # (the first two columns are those of `vocab`: the id and id_to_subword(id) as it stands)
+    text = b"".join(b"%d\t%s\t%d\n" % (i, piece.encode(), int(counts[i])) for i, piece in enumerate(core.vocab()))
+    if output is None:
+        sys.stdout.flush()
+        sys.stdout.buffer.write(text)
+        sys.stdout.buffer.flush()
+    else:
+        with open(output, "wb") as f:
+            f.write(text)
 
 
 @main.command()
