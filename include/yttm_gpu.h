@@ -23,6 +23,10 @@ const char *yttm_gpu_last_error(void);
  * synchronise the device).  This returns the cached buffers to the driver.  YTTM_NO_POOL=1 disables the pool.  (No reference
  * counterpart: bpe.cpp allocates with new/std containers.) */
 void yttm_release_device_memory(void);
+/* debug: the pool's state -- [0] bytes handed out and not yet returned, [1] bytes cached for reuse, [2] the high-water mark of [0] since the
+ * last context was made, [3] allocations asked of the pool since then (YTTM_TEST_ALLOC_FAIL=N makes the N-th of them fail).  (No reference
+ * counterpart.) */
+void yttm_gpu_pool_stats(uint64_t out[4]);
 
 /* Every YTTM_* environment hook of the library -- test and tuning knobs, none part of the drop-in surface -- as Markdown table rows
  * "| `NAME` | default | kind | what it does |" (csrc/yttm_config.h holds the one table; INTEGRATION.md prints it).  The hooks are read when a

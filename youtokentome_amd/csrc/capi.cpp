@@ -592,6 +592,11 @@ int yttm_gpu_k4_measure(yttm_ctx *c, int on, uint64_t out[6]) {
 }
 
 void yttm_release_device_memory(void) { yttm::release_device_memory(); }
+void yttm_gpu_pool_stats(uint64_t out[4]) {
+  unsigned long long v[4];
+  yttm::pool_stats(v);
+  for (int i = 0; i < 4; i++) out[i] = v[i];
+}
 const char *yttm_config_table(void) { return yttm::config_table_markdown(); }
 
 }  // extern "C"

@@ -5,12 +5,22 @@
 
 namespace yttm {
 
-GpuCtx::GpuCtx(int device) : device_(device) {
+GpuCtx::GpuCtx(int device) : m_(new Mem), device_(device) {
+  try {
+    init();
+  } catch (...) {  // (no destructor will run)
+    teardown();
+    throw;
+  }
+}
+
+void GpuCtx::init() {
   cfg_refresh();  // the environment hooks are read here, once per context (yttm_config.h); nothing below this constructor calls getenv
   cfg_ = cfg();
   const Config &C = *cfg_;
   xchg_margin_ = C.xchg_margin.d;
   pool_reset_peak();
+  pool_arm(C.test_alloc_fail.u);
   HIP_CHECK(hipSetDevice(device_));
   tl_stream = strm();
   tl_device = device_;
@@ -18,10 +28,10 @@ GpuCtx::GpuCtx(int device) : device_(device) {
   if (!st_raw_) HIP_CHECK(hipStreamCreateWithFlags(&st_raw_, hipStreamNonBlocking));
   tl_stream = strm();
   tl_device = device_;
-  d_counters_ = dmalloc<unsigned long long>(64);
-  d_stats_ = dmalloc<unsigned long long>(STATS_WORDS);  // (yttm_kernels.h: StatWord)
-  HIP_CHECK(hipMemsetAsync(d_stats_, 0, STATS_WORDS * sizeof(unsigned long long), strm()));  // (stream-ordered like everything that uses them)
-  d_round_ = dmalloc<RoundBlock>(1);  // one block for everything the host reads back per round, so that it is ONE device-to-host copy
+  m_->ctr.alloc(1);
+  m_->d_stats.alloc(STATS_WORDS);  // (yttm_kernels.h: StatWord)
+  HIP_CHECK(hipMemsetAsync(m_->d_stats, 0, STATS_WORDS * sizeof(unsigned long long), strm()));  // (stream-ordered like everything that uses them)
+  m_->d_round.alloc(1);  // one block for everything the host reads back per round, so that it is ONE device-to-host copy
   hot_cap_ = std::min((unsigned int)C.hot_cap.u, HOT_CAP);
   hot_target_ = (unsigned int)C.hot_target.u;  // measured at 1 GB: 4096..16384 equal on the abcd corpus, 8192 best on Zipf text (4279 rounds)
   hot_min_ = (unsigned int)C.hot_min.u;
@@ -49,39 +59,35 @@ GpuCtx::GpuCtx(int device) : device_(device) {
   no_batch_args_ = C.no_batch_args.set;
   trace_rounds_ = C.trace_rounds.c_str();  // (points into cfg_, which this context keeps)
   dbg_cand_ = C.dbg_cand.c_str();
-  d_hot_slots_ = dmalloc<uint32_t>(HOT_CAP);
-  d_hot_ctl_ = dmalloc<ListCtl>(1);
-  HIP_CHECK(hipMemsetAsync(d_hot_ctl_, 0, sizeof(ListCtl), strm()));
+  m_->d_hot_slots.alloc(HOT_CAP);
+  m_->d_hot_ctl.alloc(1);
+  HIP_CHECK(hipMemsetAsync(m_->d_hot_ctl, 0, sizeof(ListCtl), strm()));
   top_cap_ = std::max(16u, std::min((unsigned int)C.top_cap.u, TOP_CAP));
   top_target_ = (unsigned int)C.top_target.u;  // about four times what the host looks at per round
   top_min_ = (unsigned int)C.top_min.u;
-  d_top_slots_ = dmalloc<uint32_t>(TOP_CAP);
-  d_top_ctl_ = dmalloc<ListCtl>(1);
-  HIP_CHECK(hipMemsetAsync(d_top_ctl_, 0, sizeof(ListCtl), strm()));
-  HIP_CHECK(hipMemsetAsync(d_round_, 0, offsetof(RoundBlock, cand), strm()));  // k_hot_scan leaves its counters zeroed for the next call
+  m_->d_top_slots.alloc(TOP_CAP);
+  m_->d_top_ctl.alloc(1);
+  HIP_CHECK(hipMemsetAsync(m_->d_top_ctl, 0, sizeof(ListCtl), strm()));
+  HIP_CHECK(hipMemsetAsync(m_->d_round, 0, offsetof(RoundBlock, cand), strm()));  // k_hot_scan leaves its counters zeroed for the next call
   cand_cap_ = CAND_CAP;
-  d_rules_ = dmalloc<RuleSlot>(RULES_CAP);
+  m_->d_rules.alloc(RULES_CAP);
   rules_cap_ = RULES_CAP;
   h_pin_ = (PinBlock *)pool_take_pin();  // pinned staging: one buffer is kept across contexts (hipHostMalloc of 17 MB costs milliseconds)
   if (!h_pin_) HIP_CHECK(hipHostMalloc((void **)&h_pin_, PIN_BYTES, hipHostMallocDefault));
   memset(&h_pin_->mailbox, 0, offsetof(RoundMailbox, cand));  // (round_id: no round is published)
 }
 
-GpuCtx::~GpuCtx() {
+GpuCtx::~GpuCtx() { teardown(); }
+
+// The stream is synchronised, then every block goes back to the pool, then the pool is told that the stream is idle (its blocks may go to
+// anybody); only then the pin block and the stream are handed on.
+void GpuCtx::teardown() {
   (void)hipSetDevice(device_);
   tl_stream = strm();
   tl_device = device_;
-  (void)hipStreamSynchronize(strm());
-  drop_spec();
+  if (st_raw_) (void)hipStreamSynchronize(strm());
   for (hipEvent_t e : all_events_) (void)hipEventDestroy(e);
-  DFREE(d_text_owned_); DFREE(d_hist_); DFREE(d_chunk_segs_); DFREE(d_counters_); DFREE(d_cpmap_); DFREE(d_rules_);
-  free_class(cls_[0]); free_class(cls_[1]); free_class(cls_[2]);
-  DFREE(d_stats_); DFREE(d_round_); DFREE(d_recv_); DFREE(d_hot_slots_); DFREE(d_hot_ctl_); DFREE(d_top_slots_); DFREE(d_top_ctl_);
-  DFREE(d_xstat_); DFREE(d_bloom_); DFREE(d_maybe_); DFREE(d_maybe_ctl_);
-  DFREE(db_.keys); DFREE(db_.touched); DFREE(d_send2_[0]); DFREE(d_send2_[1]);
-  free_table(pt_);
-  free_index();
-  free_words();
+  m_.reset();
   pool_quiesce(strm());
   if (h_pin_ && pool_give_pin(h_pin_)) h_pin_ = nullptr;
   if (h_pin_) (void)hipHostFree(h_pin_);
@@ -89,9 +95,14 @@ GpuCtx::~GpuCtx() {
   if (st_raw_) (void)hipStreamDestroy(st_raw_);
 }
 
+bool GpuCtx::one_launch_rounds() const {
+  if (!(word_global_ && words_fuse_max_ != 0 && fuse_enabled_ && !instrument && hot_state_ == HOT_ACTIVE && top_state_ == TOP_ACTIVE)) return false;
+  return multi() || (word_mode_ && idx_valid_ && !m_->cls[2].n_tiles);
+}
+
 void GpuCtx::sync() { HIP_CHECK(hipStreamSynchronize(strm())); }
 void GpuCtx::read_stats(int first, int n, unsigned long long *out) {
-  HIP_CHECK(hipMemcpyAsync(out, d_stats_ + first, (size_t)n * 8, hipMemcpyDeviceToHost, strm()));
+  HIP_CHECK(hipMemcpyAsync(out, m_->d_stats + first, (size_t)n * 8, hipMemcpyDeviceToHost, strm()));
   sync();
 }
 
@@ -142,9 +153,9 @@ void GpuCtx::resolve_timers() {
     // counted once more as re-read and rewritten (8 B per token of those -- an upper bound since single-site tiles are
     // rewritten from the registers they were loaded into)
     unsigned long long st[8] = {0};
-    if (pt_cap_) launch_fold_stats(d_stats_, pt_.n_keys, strm());
+    if (pt_cap_) launch_fold_stats(m_->d_stats, pt_.n_keys, strm());
     sync();
-    if (hipMemcpy(st, d_stats_, sizeof st, hipMemcpyDeviceToHost) == hipSuccess) {
+    if (hipMemcpy(st, m_->d_stats, sizeof st, hipMemcpyDeviceToHost) == hipSuccess) {
       merge_sites = st[STAT_SITES];
       kt.bytes[KT_MERGE] = 4 * st[STAT_TOKENS] + 8 * st[STAT_TOUCHED_TOKENS];
       touched_tiles = st[STAT_TOUCHED];
@@ -273,10 +284,10 @@ void GpuCtx::round_word_mode(const Round &r) {
   // follows the decision without switching.
   if (!word_global_ && words_enabled_ && idx_enabled_ && !instrument && hot_state_ == HOT_ACTIVE) {
     const bool go = multi() ? word_mode_pays(g_tiles_a_, g_sites_last_, g_tokens_last_, (unsigned long long)comm_->world)
-                            : word_mode_pays(cls_[0].n_tiles, sites_last_, live_tokens_last_, 1);
+                            : word_mode_pays(m_->cls[0].n_tiles, sites_last_, live_tokens_last_, 1);
     if (go) {
       word_global_ = true;
-      if (cls_[0].n_tiles) enter_word_mode(r.z_base);
+      if (m_->cls[0].n_tiles) enter_word_mode(r.z_base);
       else word_switch_round = merge_rounds;
     }
   }
@@ -313,7 +324,7 @@ void GpuCtx::round_batch(Round &r) {
   }
   // A small batch goes to the kernels as an argument and nothing is uploaded (yttm_kernels.h: BatchArgs); a larger one (or any, with
   // class-C tiles: k_giant reads the rule hash from HBM) travels through k_round_begin.
-  r.by_args = r.k <= (uint32_t)BATCH_ARGS_MAX && !cls_[2].n_tiles && !no_batch_args_;
+  r.by_args = r.k <= (uint32_t)BATCH_ARGS_MAX && !m_->cls[2].n_tiles && !no_batch_args_;
   // (the common small batch needs no rule hash: the host's share of a round is on the critical path)
   if (!r.by_args) build_rule_hash(h_pin_->rules, r.cap, r.xyz, 3, r.k);
   r.ba.instr = instrument ? 1u : 0u;
@@ -332,16 +343,16 @@ void GpuCtx::round_batch(Round &r) {
 void GpuCtx::round_scan(Round &r, const unsigned long long *next_tau_cnt, uint32_t next_tau_mx, uint32_t next_want) {
   ScanArgs &sa = r.sa;
   fused_pending_ = false;
-  r.last_cls = cls_[0].n_tiles ? 0 : 1;
+  r.last_cls = m_->cls[0].n_tiles ? 0 : 1;
   if (next_tau_cnt && fuse_enabled_ && hot_state_ == HOT_ACTIVE && top_state_ == TOP_ACTIVE && !instrument &&
-      (multi() || ((cls_[0].n_tiles || cls_[1].n_tiles) && !cls_[2].n_tiles))) {
+      (multi() || ((m_->cls[0].n_tiles || m_->cls[1].n_tiles) && !m_->cls[2].n_tiles))) {
     sa = scan_args(*next_tau_cnt, next_tau_mx, ++mail_round_);
     if (sa.tau_cnt < pt_.top_tau) {  // the list is complete only from top_tau up (as in candidates())
       sa.tau_cnt = pt_.top_tau;
       sa.tau_mx = 0xffffffffu;
     }
     sa.want = next_want;  // (the scan may raise the threshold to about this many candidates: scan_top)
-    sa.done_ctr = &d_hot_ctl_->ticket;
+    sa.done_ctr = &m_->d_hot_ctl->ticket;
     fused_pending_ = true;
     fused_tau_ = *next_tau_cnt;
     fused_mx_ = next_tau_mx;
@@ -352,7 +363,7 @@ void GpuCtx::round_scan(Round &r, const unsigned long long *next_tau_cnt, uint32
   // tail as well was measured: ONE workgroup walking ten thousand claimed slots across XCDs took 45 us -- k_dt_pack's hundred take 6.)
   if (multi()) {
     r.xa.on = 2u;
-    r.xa.done_ctr = &d_hot_ctl_->ticket;
+    r.xa.done_ctr = &m_->d_hot_ctl->ticket;
   }
   // A fused round is timed by the device itself (its first launch notes the time, the tail reports the difference in the mailbox):
   // no hipEventRecord on the round's critical path (two per round were 4 us of host time: 8 % of a Zipf step).  YTTM_PROFILE_EVENTS=1
@@ -392,36 +403,36 @@ void GpuCtx::round_launch(Round &r) {
   if (!r.dev_timing) t_begin(KT_MERGE);
   if (!r.by_args) {
     pm_bloom_host(h_pin_->bloom, r.xyz, r.k);  // the batch's pair filter for the apply kernels (built here: a few hundred hashes)
-    if (!d_bloom_) d_bloom_ = dmalloc<uint32_t>(PM_BLOOM_WORDS_H);
-    launch_round_begin(h_pin_->rules, r.cap, d_rules_, cls_[0].n_tiles ? cls_[0].d_work_n : nullptr, cls_[1].n_tiles ? cls_[1].d_work_n : nullptr, h_pin_->bloom, d_bloom_, strm());
+    if (!m_->d_bloom) m_->d_bloom.alloc(PM_BLOOM_WORDS_H);
+    launch_round_begin(h_pin_->rules, r.cap, m_->d_rules, m_->cls[0].n_tiles ? m_->cls[0].d_work_n.p : nullptr, m_->cls[1].n_tiles ? m_->cls[1].d_work_n.p : nullptr, h_pin_->bloom, m_->d_bloom, strm());
   }
   r.kpt = multi() ? pt_nolist() : pt_;  // (multi-GPU: the lists are filled behind the exchange, by the final counts -- k_fold_list)
   // Class B, then class A (tiles, or word mode's k_words), on the context's one stream: stream order is the only synchronisation between
   // the round's launches, and the last of them carries the tail (tail_of).
   for (int ci = 1; ci >= 0; ci--) {
-    if (!cls_[ci].n_tiles) continue;
+    if (!m_->cls[ci].n_tiles) continue;
     if (ci == 0 && word_mode_) {
       round_launch_words(r);
       continue;
     }
     const BatchArgs tba = r.first_ba();
-    launch_merge_apply(ci, cls_[ci].ts, r.kpt, db_, d_rules_, r.cap - 1, r.self_x, r.self_z, r.z_base, d_stats_, &tba, tail_of(r, ci), d_bloom_,
+    launch_merge_apply(ci, m_->cls[ci].ts, r.kpt, db_, m_->d_rules, r.cap - 1, r.self_x, r.self_z, r.z_base, m_->d_stats, &tba, tail_of(r, ci), m_->d_bloom,
                        (unsigned int)cfg_->apply_grid.i, strm());
     if (ci == 1 && word_mode_) classb_word_rounds++;
   }
-  launch_giant(true, cls_[2].ts, cls_[2].slot, r.kpt, db_, d_rules_, r.cap - 1, r.self_x, r.self_z, cls_[2].d_scratch, d_stats_, strm());
+  launch_giant(true, m_->cls[2].ts, m_->cls[2].slot, r.kpt, db_, m_->d_rules, r.cap - 1, r.self_x, r.self_z, m_->cls[2].d_scratch, m_->d_stats, strm());
   if (r.dev_timing) kt.launches[KT_MERGE]++;
   else t_end(KT_MERGE, 0, /*chain=*/!r.sa.on);  // (a fused round is followed by the host's turn, not by another kernel: its end event must not start the next interval)
 }
 
 // class A in word mode: the batch's rules -> worklist of words (k_wgather; it also allots the new tokens' instance lists), then the words (k_words)
 void GpuCtx::round_launch_words(Round &r) {
-  WordClass &c = cls_[0];
+  WordClass &c = m_->cls[0];
   const uint32_t *d_xyz = nullptr;
   if (!r.by_args) {
     memcpy(h_pin_->xyz, r.xyz, (size_t)r.k * 12);
-    HIP_CHECK(hipMemcpyAsync(d_xyz_, h_pin_->xyz, (size_t)r.k * 12, hipMemcpyHostToDevice, strm()));
-    d_xyz = d_xyz_;
+    HIP_CHECK(hipMemcpyAsync(m_->d_xyz, h_pin_->xyz, (size_t)r.k * 12, hipMemcpyHostToDevice, strm()));
+    d_xyz = m_->d_xyz;
   }
   if (r.k > WGATHER_MAXK) throw GpuError{"merge_apply: batch too large for the word-mode gather"};
   WGatherArgs ga{};  // (the worklist's length is at zero: enter_word_mode, then every round's k_delta_apply)
@@ -429,44 +440,44 @@ void GpuCtx::round_launch_words(Round &r) {
   ga.ix_valid = idx_valid_ ? 1u : 0u;
   ga.z_static = idx_valid_ ? idx_zbuild_ : 0xffffffffu;  // (no index: every rule is "not found", the round takes every word)
   ga.tl = tl_;
-  ga.stamp = d_stamp_;
+  ga.stamp = m_->d_stamp;
   ga.round_id = (uint32_t)(merge_rounds + 1);
-  ga.worklist = d_wworklist_;
+  ga.worklist = m_->d_wworklist;
   ga.wl_seg = c.n_unique + 64;
   ga.work_n = c.d_work_n;
-  ga.gm = d_gather_->matched;
-  ga.done_ctr = &d_gather_->ticket;
+  ga.gm = m_->d_gather->matched;
+  ga.done_ctr = &m_->d_gather->ticket;
   ga.xyz = d_xyz;
   ga.k = r.k;
   ga.z_base = r.z_base;
   if (r.by_args)
     for (uint32_t j = 0; j < r.k; j++) ga.cnt[j] = r.rule_counts ? (uint32_t)std::min<unsigned long long>(r.rule_counts[j], 0xffffffffull) : 0xffffffffu;
-  if (!d_stamp_) {  // (the index could not be built yet: no stamps either -- the gather must not claim words)
+  if (!m_->d_stamp) {  // (the index could not be built yet: no stamps either -- the gather must not claim words)
     stamp_cap_ = (unsigned int)(c.n_unique + c.n_unique / 8 + 64);
-    d_stamp_ = dmalloc<uint32_t>(stamp_cap_);
-    HIP_CHECK(hipMemsetAsync(d_stamp_, 0, (size_t)stamp_cap_ * 4, strm()));
-    ga.stamp = d_stamp_;
+    m_->d_stamp.alloc(stamp_cap_);
+    HIP_CHECK(hipMemsetAsync(m_->d_stamp, 0, (size_t)stamp_cap_ * 4, strm()));
+    ga.stamp = m_->d_stamp;
   }
   // live tokens per class-A word, about: what the class held when it left the tiles, less a token per merge site since (a round or two behind)
   if (sites_last_ != ~0ull && word_sites_seen_ != sites_cum_) {
     word_live_tokens_ -= std::min(word_live_tokens_, sites_cum_ - std::min(sites_cum_, word_sites_seen_));
     word_sites_seen_ = sites_cum_;
   }
-  ga.stats = d_stats_;
+  ga.stats = m_->d_stats;
   const BatchArgs gba = r.first_ba();
   WordsRound wr{};
-  wr.ws = WordSet{c.d_tok, d_wmeta_, c.d_wcnt, (uint32_t)c.n_unique};
+  wr.ws = WordSet{c.d_tok, m_->d_wmeta, c.d_wcnt, (uint32_t)c.n_unique};
   wr.pt = r.kpt;
   wr.db = db_;
-  wr.rules = d_rules_;
+  wr.rules = m_->d_rules;
   wr.rule_mask = r.cap - 1;
-  wr.bloom_g = d_bloom_;
+  wr.bloom_g = m_->d_bloom;
   wr.self_x = r.self_x;
   wr.self_z = r.self_z;
-  wr.drec = d_drec_;
+  wr.drec = m_->d_drec;
   wr.drec_cap = drec_cap_;
-  wr.drec_n = d_drec_n_;
-  wr.irec = d_irec_;
+  wr.drec_n = m_->d_drec_n;
+  wr.irec = m_->d_irec;
   wr.ba = &gba;
   wr.scan = tail_of(r, 0);
   wr.work_hint = sites_last_ != ~0ull && idx_valid_ ? (unsigned int)std::min<unsigned long long>(2 * sites_last_ + word_hint_floor_, 1ull << 30) : 0u;
@@ -488,12 +499,12 @@ void GpuCtx::round_trace(const Round &r) {
   if (trace_rounds) {
     chain_event_ = nullptr;  // (adds a sync)
     unsigned long long stt[STAT_TAIL];
-    launch_fold_stats(d_stats_, pt_.n_keys, strm());
-    HIP_CHECK(hipMemcpyAsync(stt, d_stats_, sizeof stt, hipMemcpyDeviceToHost, strm()));
+    launch_fold_stats(m_->d_stats, pt_.n_keys, strm());
+    HIP_CHECK(hipMemcpyAsync(stt, m_->d_stats, sizeof stt, hipMemcpyDeviceToHost, strm()));
     sync();
     if (cfg_->trace_blocks.set && merge_rounds % 50 == 0) {  // PROF build: per-workgroup start / end / dirty tiles of this round
       std::vector<unsigned long long> rows(STATS_WORDS);
-      HIP_CHECK(hipMemcpy(rows.data(), d_stats_, STATS_WORDS * 8, hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(rows.data(), m_->d_stats, STATS_WORDS * 8, hipMemcpyDeviceToHost));
       std::string name = cfg_->trace_blocks.raw + "." + std::to_string(merge_rounds);
       if (FILE *fb = fopen(name.c_str(), "w")) {
         for (int b = 0; b < BLK_ROWS; b++) {
@@ -505,7 +516,7 @@ void GpuCtx::round_trace(const Round &r) {
     }
     FILE *f = fopen(trace_rounds, merge_rounds == 1 ? "w" : "a");
     if (f) {
-      fprintf(f, "%llu %u %llu %llu %llu %llu %u", merge_rounds, r.k, stt[STAT_SITES], stt[STAT_TOUCHED], stt[STAT_TOKENS], stt[STAT_TOUCHED_TOKENS], cls_[0].n_tiles);
+      fprintf(f, "%llu %u %llu %llu %llu %llu %u", merge_rounds, r.k, stt[STAT_SITES], stt[STAT_TOUCHED], stt[STAT_TOKENS], stt[STAT_TOUCHED_TOKENS], m_->cls[0].n_tiles);
       for (int i = STAT_PROF; i < STAT_PROF + STAT_PROF_N; i++) fprintf(f, " %llu", stt[i]);
       fprintf(f, "\n");
       fclose(f);
@@ -513,8 +524,8 @@ void GpuCtx::round_trace(const Round &r) {
   }
   if (instrument && split_round && merge_rounds == split_round) {  // (measurement pass only: a sync does not matter)
     unsigned long long st[8] = {0};
-    launch_fold_stats(d_stats_, pt_.n_keys, strm());
-    HIP_CHECK(hipMemcpyAsync(st, d_stats_, sizeof st, hipMemcpyDeviceToHost, strm()));
+    launch_fold_stats(m_->d_stats, pt_.n_keys, strm());
+    HIP_CHECK(hipMemcpyAsync(st, m_->d_stats, sizeof st, hipMemcpyDeviceToHost, strm()));
     sync();
     split_sites = st[STAT_SITES];
     split_touched_words = st[STAT_INSTR_WORDS];
@@ -539,7 +550,7 @@ void GpuCtx::round_finish(const Round &r) {
   // repack when the tiles are less than half full.  With the hot-list filter the fill is known for free (the previous
   // round's filters report the tokens they streamed); otherwise look every 8 rounds.
   if (hot_state_ == HOT_ACTIVE && live_tokens_last_) {
-    const unsigned long long nominal = (unsigned long long)cls_[0].n_tiles * cls_[0].nom + (unsigned long long)cls_[1].n_tiles * cls_[1].nom;
+    const unsigned long long nominal = (unsigned long long)m_->cls[0].n_tiles * m_->cls[0].nom + (unsigned long long)m_->cls[1].n_tiles * m_->cls[1].nom;
     // (word mode: class A no longer lives in tiles, and "tokens streamed last round" is small against the nominal size of everything whatever
     // the fill of class B: its looks are spaced out -- a late repack of the few long words costs less than a look every other round)
     if (live_tokens_last_ * 2 <= nominal && ++rounds_since_check_ >= (word_mode_ ? 64u : 2u)) {

@@ -1,10 +1,11 @@
-// gpu_ctx.h -- device context of the BPE trainer: owns every HBM buffer, one HIP stream, and (multi-GPU) the RCCL
-// communicator.  The C-ABI in include/yttm_gpu.h is a thin wrapper over this class.
+// gpu_ctx.h -- device context of the BPE trainer: owns every HBM buffer (GpuCtx::Mem, gpu_ctx_internal.h), one HIP stream, and (multi-GPU) the
+// RCCL communicator.  The C-ABI in include/yttm_gpu.h is a thin wrapper over this class.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -48,11 +49,10 @@ struct Comm {
 
 // returns the device (and pinned) memory cached by finished contexts to the driver
 void release_device_memory();
+// debug: the pool's bytes in use, bytes cached, their high-water mark, pool_alloc calls since the last context was made
+void pool_stats(unsigned long long out[4]);
 
-struct PinBlock;    // gpu_ctx_internal.h: the pinned block, the device's round block, list lengths + tickets, the gather's counters
-struct RoundBlock;
-struct ListCtl;
-struct GatherCtl;
+struct PinBlock;    // gpu_ctx_internal.h: the pinned block
 
 struct KernelTimes {  // accumulated GPU time per kernel family, measured with HIP events on the ctx stream
   double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -177,8 +177,6 @@ class GpuCtx {
   HotState hot_state_ = HOT_INVALID;
   enum TopState { TOP_INVALID, TOP_ACTIVE, TOP_BYPASS };  // BYPASS: ties too large for the top list, the hot list is scanned instead
   TopState top_state_ = TOP_INVALID;
-  uint32_t *d_top_slots_ = nullptr;
-  ListCtl *d_top_ctl_ = nullptr;
   unsigned int top_cap_ = 0, top_target_ = 0, top_min_ = 0, top_listed_last_ = 0, bypass_rounds_ = 0;
   void poll_mailbox(uint32_t round_id);
   ScanArgs scan_args(unsigned long long tau_cnt, uint32_t tau_mx, uint32_t round_id) const;
@@ -190,27 +188,31 @@ class GpuCtx {
   unsigned long long last_live_ = 0, hist_buf_[CAND_BINS] = {0};
   unsigned int last_top_bin_ = CAND_BINS - 1;
   unsigned long long bound_prev_ = 0;  // new-key bound of the previous round (see merge_apply)
-  uint32_t *d_hot_slots_ = nullptr;
-  ListCtl *d_hot_ctl_ = nullptr;  // (its ticket: k_hot_scan's and every fused tail's finished workgroups)
   unsigned int fullscan_rounds_ = 0;
   uint32_t mail_round_ = 0;
   bool fused_pending_ = false;  // a fused scan is in flight / in the mailbox ...
   unsigned long long fused_tau_ = 0;  // ... for this threshold
   uint32_t fused_mx_ = 0, fused_round_ = 0;
   bool no_batch_args_ = false;
-  uint32_t *d_bloom_ = nullptr;   // pair filter of a batch that does not travel in the kernel arguments
   const char *trace_rounds_ = nullptr, *dbg_cand_ = nullptr;
   bool fuse_enabled_ = true;  // YTTM_NO_FUSE=1: always the separate scan kernel (tuning hook / tests)
   uint32_t id_min_ = 0, id_max_ = 0;  // id range of the alphabet (K3)
   uint32_t max_id_ = 0xffffffffu;  // largest token id in the tiles (unknown until the word table is built)
   unsigned long long scanned_cum_ = 0, live_tokens_last_ = 0, touched_cum_ = 0, touched_last_ = ~0ull >> 2;  // (first round: dense)
   unsigned int hot_cap_ = 0, hot_target_ = 0, hot_min_ = 0, listed_last_ = 0;
-  void alloc_table(PairTable &pt, unsigned long long cap);
-  void free_table(PairTable &pt);
+  struct PairTableMem;
+  void alloc_table(PairTableMem &mem, PairTable &pt, unsigned long long cap);
+  void free_table();
   void exchange_deltas();
   void t_begin(int which);
   void t_end(int which, unsigned long long bytes, bool chain = false);
 
+  // Every device block the context owns (gpu_ctx_internal.h); the members below that point into device memory are views of its blocks or
+  // memory of somebody else's.
+  struct Mem;
+  std::unique_ptr<Mem> m_;
+  void init();      // the constructor's work
+  void teardown();  // the destructor's (the constructor's too, when init() throws half-way)
   int device_;
   std::shared_ptr<const Config> cfg_;
   double xchg_margin_ = 3.0;
@@ -220,23 +222,9 @@ class GpuCtx {
   Comm *comm_ = nullptr;
 
   // corpus
-  const uint8_t *d_text_ = nullptr;
-  uint8_t *d_text_owned_ = nullptr;
+  const uint8_t *d_text_ = nullptr;  // the text the kernels read: Mem::d_text_owned, or an attached buffer of the caller's
   unsigned long long n_text_ = 0;
-  // K1
-  unsigned long long *d_hist_ = nullptr;      // [N_CODEPOINTS]
-  uint32_t *d_chunk_segs_ = nullptr;          // [fe_chunks(n_text_)] segment starts per 4 KB chunk (K1 counts them, K2a places them)
-  // What upload_corpus_fd has done of the front end while the file was still crossing the link (single GPU: K1, K2a and K2b on the parts that
-  // had arrived; see there): char_hist() / build_word_table() take it from here instead of launching the kernels.
-  struct FrontSpec {
-    bool hist_done = false;             // d_hist_, d_counters_[0..1], d_chunk_segs_ hold K1's results for the whole text
-    bool words_done = false;            // ht holds every segment's word, deduplicated under the code-point-as-id map (valid iff the alphabet keeps every char seen)
-    unsigned long long n_segs = 0;
-    unsigned long long *ht = nullptr;
-    unsigned long long ht_cap = 0;
-    unsigned int h_status[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    bool long_segments = false;
-  } spec_;
+  struct FrontSpec;  // (gpu_ctx_internal.h) what upload_corpus_fd has done of the front end under the upload
   std::vector<uint32_t> seen_cps_;      // char_hist: the code points that occur
   void drop_spec();
   // ---- corpora that do not fit (gpu_ctx.cpp front_end_chunked): the text crosses the device in chunks, only the distinct words' bytes stay
@@ -247,34 +235,19 @@ class GpuCtx {
   void front_end_chunked(bool first_pass);
   bool overlap_front_end(unsigned long long n) const;
   void upload_overlapped(unsigned long long n, const std::function<bool(void *dst, unsigned long long off, size_t len)> &fill);
-  unsigned long long *d_counters_ = nullptr;  // small scratch of u64 counters
   // K2
-  uint32_t *d_cpmap_ = nullptr;  // [N_CODEPOINTS]
   uint32_t n_alpha_ = 0;
-  // token tiles: class 0 = short words (slot 1024), class 1 = long words (slot 4096)
-  struct WordClass {
-    TileSet ts{};
-    uint32_t *d_tok = nullptr, *d_tile_len = nullptr, *d_tile_word0 = nullptr, *d_wcnt = nullptr;
-    uint32_t *d_scratch = nullptr;  // class C only (k_giant.hip)
-    unsigned int *d_work_n = nullptr;
-    unsigned long long n_unique = 0, n_tokens0 = 0;
-    unsigned int n_tiles = 0, nom = 0, slot = 0;
-  };
-  WordClass cls_[3];  // A: words <= TILE_NOM_A tokens, B: <= TILE_NOM_B, C: longer (one workgroup per tile, k_giant.hip)
+  struct WordClass;  // (gpu_ctx_internal.h) a class of token tiles: Mem::cls[3]
   void free_class(WordClass &c);
-  void build_class(int ci, unsigned long long *uw_pos, uint32_t *uw_len, unsigned int U, uint32_t space_id);
+  void build_class(int ci, const unsigned long long *uw_pos, const uint32_t *uw_len, unsigned int U, uint32_t space_id);
   void maybe_repack(int ci);
   // pair index of word mode (k_index_core.h: PairIndex): keys = the hot list when it was built, postings = class-A words
   PairIndexArgs idx_{};
   unsigned long long idx_cap_ = 0, post_cap_ = 0;
-  unsigned long long *idx_scan_tmp_ = nullptr;
-  unsigned char *idx_save_ = nullptr;  // the index count pass's per-workgroup tables (k_idx_stream)
-  uint32_t *d_stamp_ = nullptr;   // [class-A words] round that claimed the word for its worklist last
   unsigned int stamp_cap_ = 0;
   bool idx_valid_ = false, idx_pending_ = false, idx_enabled_ = true;
   uint32_t idx_zbuild_ = 0;       // token ids below this existed when the index was built
   void build_index(uint32_t z_next);
-  void free_index();
   // word mode (k_words.hip): class-A words processed one by one from a worklist of the words that hold a merge site
   bool profile_events_ = false, dev_timing_pending_ = false;  // (merge_apply: dev_timing)
   std::vector<float> dev_round_ms_;
@@ -288,22 +261,13 @@ class GpuCtx {
   // class A is in word mode, and a batch of at most this many rules is one launch there (k_words<FUSED>): the trainer's batch split
   // (the conditions merge_apply fuses a round under, as far as they are known before the batch is -- cutting a batch for a
   // round that then runs unfused anyway only adds a round.  Multi-GPU: only what is the same on every rank -- the batches must be.)
-  bool one_launch_rounds() const {
-    if (!(word_global_ && words_fuse_max_ != 0 && fuse_enabled_ && !instrument && hot_state_ == HOT_ACTIVE && top_state_ == TOP_ACTIVE)) return false;
-    return multi() || (word_mode_ && idx_valid_ && !cls_[2].n_tiles);
-  }
+  bool one_launch_rounds() const;
  private:
   unsigned int hot_target_words_ = 1u << 16, words_inline_max_ = 1u << 18, words_fuse_max_ = 1u << 30, word_hint_floor_ = 16384;
   unsigned int word_div_ = 200;    // switch when (merge sites of the last round) * word_div_ < (tokens a pass over the tiles streams)
   unsigned int word_min_tiles_ = 16384;
   unsigned long long idx_agg_min_ = 16ull << 20, idx_radix_min_ = 0, word_min_tokens_ = 48ull << 20;
-  unsigned long long *d_wmeta_ = nullptr;
-  GatherCtl *d_gather_ = nullptr;
-  uint32_t *d_xyz_ = nullptr;      // a batch too large for BatchArgs, as (x, y, z) triples
-  uint32_t *d_wworklist_ = nullptr;  // [n_unique + 64] the round's words
-  DeltaRec *d_drec_ = nullptr;       // [WORDS_MAX_GRID * drec_cap_] the round's count updates, a region per workgroup of k_words
-  unsigned int *d_drec_n_ = nullptr, drec_cap_ = 0;
-  uint4 *d_irec_ = nullptr;          // [WORDS_MAX_GRID * drec_cap_] the round's new-instance records before they go to the tokens' lists
+  unsigned int drec_cap_ = 0;
   TokLists tl_{};
   unsigned long long word_live_tokens_ = 0, word_sites_seen_ = 0;  // class A in word mode: its live tokens (about), the merge sites already taken off them
   unsigned long long sites_cum_ = 0, sites_last_ = ~0ull;
@@ -323,18 +287,14 @@ class GpuCtx {
   PairTable pt_{};
   unsigned long long pt_cap_ = 0;
   // per-round staging
-  RuleSlot *d_rules_ = nullptr;
   unsigned int rules_cap_ = 0;
   uint32_t id_cap_ = 0;  // token ids are below this (vocab_size + slack)
-  unsigned long long *d_stats_ = nullptr;
   PinBlock *h_pin_ = nullptr;  // pinned: the mailbox, the candidates' read-back area, batch staging
   // candidates
-  RoundBlock *d_round_ = nullptr;
   unsigned int cand_cap_ = 0;
   // multi-GPU delta exchange.  db_ = the round's delta table and send block (yttm_device.h: DeltaBuf); per round the first blk_ 16-byte
-  // units of every rank's send block are all-gathered into d_recv_
+  // units of every rank's send block are all-gathered into Mem::d_recv
   DeltaBuf db_{};
-  DeltaRec *d_send2_[2] = {nullptr, nullptr}, *d_recv_ = nullptr;  // the two send blocks (rounds alternate: yttm_device.h DeltaBuf)
   const DeltaRec *xch_last_ = nullptr;                           // the block of the exchange under way (a repeat gathers it again)
   void finish_block(unsigned int n_hint);
   unsigned long long recv_cap_ = 0, blk_ = 4096, blk_min_ = 4096, send_cap_ = 0;
@@ -342,10 +302,7 @@ class GpuCtx {
   bool delta_cap_forced_ = false;  // YTTM_XCHG_TABLE_CAP (tests: the overflow verdict)
   bool pt_fresh_ = false;  // build_class(0) left an empty pair table of the initial size
   unsigned long long initial_table_keys(unsigned long long n_tok) const;
-  unsigned long long *d_xstat_ = nullptr;  // [XSTAT_WORDS] the fold's report on a round's exchange (yttm_kernels.h)
   unsigned int xch_parity_ = 0;            // which send block this round's updates go to
-  uint32_t *d_maybe_ = nullptr;            // slots whose count an add of this round saw at or above a list threshold (PairTable::maybe)
-  ListCtl *d_maybe_ctl_ = nullptr;         // (its ticket: k_dt_clean's)
   unsigned int maybe_cap_ = 0;
   unsigned long long xch_sites_ = 0;       // merge sites (summed pair counts of the batch) of the round whose exchange is under way
   double xrate_[2] = {5.0, 5.0};           // delta records of the busiest rank per merge site, last two rounds

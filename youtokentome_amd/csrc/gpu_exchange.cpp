@@ -6,9 +6,8 @@ namespace yttm {
 
 void GpuCtx::grow_recv(unsigned long long need) {
   if (need <= recv_cap_) return;
-  DFREE(d_recv_);
   recv_cap_ = need + need / 4 + 1024;
-  d_recv_ = dmalloc<DeltaRec>(recv_cap_);
+  m_->d_recv.alloc(recv_cap_);
 }
 
 // Set-up exchange (after K3, once per training): every rank's records, however many.  The counts travel first, so buffers
@@ -17,8 +16,8 @@ void GpuCtx::grow_recv(unsigned long long need) {
 void GpuCtx::exchange_deltas() {
   if (!multi()) return;
   chain_event_ = nullptr;
-  launch_fold_stats(d_stats_, pt_.n_keys, strm());  // the apply kernels leave their slot counts in per-workgroup rows
-  DeltaRec *cur = d_send2_[xch_parity_];  // (K3's updates went straight into the block's records: dt_add)
+  launch_fold_stats(m_->d_stats, pt_.n_keys, strm());  // the apply kernels leave their slot counts in per-workgroup rows
+  DeltaRec *cur = m_->delta.send[xch_parity_];  // (K3's updates went straight into the block's records: dt_add)
   unsigned long long n_local = 0;
   unsigned int nk_local = 0;  // keys in the table after this rank's own updates (one round trip for both numbers)
   HIP_CHECK(hipMemcpyAsync(&n_local, cur, 8, hipMemcpyDeviceToHost, strm()));
@@ -29,14 +28,14 @@ void GpuCtx::exchange_deltas() {
   size_t n_remote = 0;
   for (int attempt = 0;; attempt++) {
     unsigned long long need_all = 0;
-    if (comm_->allgather_recs(cur + XHDR, mine, d_recv_, (size_t)recv_cap_, strm(), &need_all, &n_remote)) break;
+    if (comm_->allgather_recs(cur + XHDR, mine, m_->d_recv, (size_t)recv_cap_, strm(), &need_all, &n_remote)) break;
     if (need_all == ~0ull) throw GpuError{"delta exchange buffer overflow (on some rank)"};
     if (attempt) throw GpuError{"delta receive buffer could not be sized"};
     grow_recv(need_all);
   }
   finish_block((unsigned int)std::min<unsigned long long>(n_local, 1u << 20));
   ensure_table_capacity(n_keys_host + n_remote);
-  launch_pt_apply(pt_, d_recv_, n_remote, strm());  // (no candidate list exists yet: nothing is listed)
+  launch_pt_apply(pt_, m_->d_recv, n_remote, strm());  // (no candidate list exists yet: nothing is listed)
   unsigned int nk = 0;
   HIP_CHECK(hipMemcpyAsync(&nk, pt_.n_keys, 4, hipMemcpyDeviceToHost, strm()));
   sync();
@@ -52,16 +51,16 @@ void GpuCtx::exchange_deltas() {
 // behind an exchange: the table's slots of the block just sent are freed, the other block is made ready, and the next round's updates go
 // there (k_dt_clean: off the critical path -- it runs while the host picks the next batch)
 void GpuCtx::finish_block(unsigned int n_hint) {
-  db_.send = d_send2_[xch_parity_];
-  launch_dt_clean(db_, d_send2_[xch_parity_ ^ 1u], n_hint, d_stats_, cls_[0].n_tiles, &d_maybe_ctl_->ticket, strm());
-  xch_last_ = d_send2_[xch_parity_];
+  db_.send = m_->delta.send[xch_parity_];
+  launch_dt_clean(db_, m_->delta.send[xch_parity_ ^ 1u], n_hint, m_->d_stats, m_->cls[0].n_tiles, &m_->d_maybe_ctl->ticket, strm());
+  xch_last_ = m_->delta.send[xch_parity_];
   xch_parity_ ^= 1u;
-  db_.send = d_send2_[xch_parity_];
+  db_.send = m_->delta.send[xch_parity_];
 }
 PairTable GpuCtx::pt_nolist() const {
   PairTable p = pt_;
-  p.maybe = d_maybe_;  // (the adds note the slots that may have crossed a threshold: k_fold_list looks at those, by their final counts)
-  p.maybe_n = &d_maybe_ctl_->n;
+  p.maybe = m_->d_maybe;  // (the adds note the slots that may have crossed a threshold: k_fold_list looks at those, by their final counts)
+  p.maybe_n = &m_->d_maybe_ctl->n;
   p.maybe_cap = maybe_cap_;
   p.maybe_hot = pt_.hot_tau;
   p.maybe_top = pt_.top_tau;
@@ -72,16 +71,16 @@ PairTable GpuCtx::pt_nolist() const {
 
 void GpuCtx::exchange_round(unsigned long long only_mask, const ScanArgs *scan) {
   chain_event_ = nullptr;
-  const DeltaRec *block = only_mask ? xch_last_ : d_send2_[xch_parity_];  // (a repeat gathers the same block again, wider)
+  const DeltaRec *block = only_mask ? xch_last_ : m_->delta.send[xch_parity_];  // (a repeat gathers the same block again, wider)
   grow_recv(blk_ * (unsigned long long)comm_->world);
-  comm_->allgather_blocks(block, d_recv_, (size_t)blk_ * sizeof(DeltaRec), strm());
+  comm_->allgather_blocks(block, m_->d_recv, (size_t)blk_ * sizeof(DeltaRec), strm());
   const bool alone = comm_->world == 1;  // (no other rank's block: phase 1 has nothing to add, the fold kernel reads the header itself)
-  if (!alone) launch_pt_apply_blocks(pt_nolist(), d_recv_, blk_, comm_->world, comm_->rank, only_mask, d_xstat_, d_stats_, strm());
+  if (!alone) launch_pt_apply_blocks(pt_nolist(), m_->d_recv, blk_, comm_->world, comm_->rank, only_mask, m_->d_xstat, m_->d_stats, strm());
   PairTable fpt = pt_;  // (the real thresholds, and the notes to go through)
-  fpt.maybe = d_maybe_;
-  fpt.maybe_n = &d_maybe_ctl_->n;
+  fpt.maybe = m_->d_maybe;
+  fpt.maybe_n = &m_->d_maybe_ctl->n;
   fpt.maybe_cap = maybe_cap_;
-  launch_fold_list(fpt, d_recv_, blk_, comm_->world, only_mask, scan, d_stats_, zero_batch(), d_xstat_, alone, strm());
+  launch_fold_list(fpt, m_->d_recv, blk_, comm_->world, only_mask, scan, m_->d_stats, zero_batch(), m_->d_xstat, alone, strm());
   if (scan) pending_zero_ = false;  // (the scan zeroes the finished batch's pairs)
   if (!only_mask) finish_block((unsigned int)std::min<unsigned long long>(blk_ / 2, 1u << 18));  // (about as many records as the block was sized for)
 }
@@ -90,23 +89,28 @@ void GpuCtx::exchange_round(unsigned long long only_mask, const ScanArgs *scan) 
 // table more than half full counts as overflow.  Called at set-up and, from merge_apply, when a round's bound on the distinct pairs it
 // can touch does not fit -- between rounds the table is empty (k_dt_pack frees what a round claimed).
 void GpuCtx::alloc_delta_table(unsigned long long cap) {
-  DFREE(db_.keys); DFREE(db_.touched); DFREE(d_send2_[0]); DFREE(d_send2_[1]);
-  db_.keys = dmalloc<DtSlot>(cap);
+  m_->delta.keys.reset();
+  m_->delta.touched.reset();
+  m_->delta.send[0].reset();
+  m_->delta.send[1].reset();
+  m_->delta.keys.alloc(cap);
+  db_.keys = m_->delta.keys;
   db_.mask = cap - 1;
   launch_dt_init(db_.keys, cap, strm());
   send_cap_ = cap / 2;
   db_.send_cap = send_cap_;
-  db_.touched = dmalloc<uint32_t>(send_cap_);
+  m_->delta.touched.alloc(send_cap_);
+  db_.touched = m_->delta.touched;
   // the two send blocks { header, records }: all zeros but the capacity in the header -- the peers check a block's count against it
   for (int b = 0; b < 2; b++) {
-    d_send2_[b] = dmalloc<DeltaRec>(send_cap_ + XHDR);
-    HIP_CHECK(hipMemsetAsync(d_send2_[b], 0, (send_cap_ + XHDR) * sizeof(DeltaRec), strm()));
+    m_->delta.send[b].alloc(send_cap_ + XHDR);
+    HIP_CHECK(hipMemsetAsync(m_->delta.send[b], 0, (send_cap_ + XHDR) * sizeof(DeltaRec), strm()));
     const long long capv = (long long)send_cap_;
-    HIP_CHECK(hipMemcpyAsync(&d_send2_[b][0].delta, &capv, 8, hipMemcpyHostToDevice, strm()));
+    HIP_CHECK(hipMemcpyAsync(&m_->delta.send[b][0].delta, &capv, 8, hipMemcpyHostToDevice, strm()));
   }
   xch_parity_ = 0;
-  xch_last_ = d_send2_[0];
-  db_.send = d_send2_[0];
+  xch_last_ = m_->delta.send[0];
+  db_.send = m_->delta.send[0];
   sync();
 }
 
@@ -128,7 +132,7 @@ bool GpuCtx::settle_exchange(unsigned long long xmask, unsigned long long xmax, 
   while (blk_ < xmax + XHDR) blk_ <<= 1;
   exchange_round(xmask, nullptr);
   {  // that fold's own report (same blocks, so nothing new): consumed here
-    HIP_CHECK(hipMemsetAsync(d_xstat_, 0, 32, strm()));
+    HIP_CHECK(hipMemsetAsync(m_->d_xstat, 0, 32, strm()));
   }
   blk_ = std::max(blk_, want);
   exchange_retries++;

@@ -5,27 +5,31 @@
 namespace yttm {
 
 // ------------------------------------------------------------------------------------------------- pair table
-void GpuCtx::alloc_table(PairTable &pt, unsigned long long cap) {
-  pt.slots = dmalloc<unsigned long long>(2 * cap);
-  pt.n_keys = dmalloc<unsigned int>(4);
+void GpuCtx::alloc_table(PairTableMem &mem, PairTable &pt, unsigned long long cap) {
+  mem.slots.alloc(2 * cap);
+  mem.n_keys.alloc(4);
+  pt.slots = mem.slots;
+  pt.n_keys = mem.n_keys;
   pt.mask = cap - 1;
   pt.hot_tau = ~0ull;  // no hot list until rebuild_hot()
-  pt.hot_slots = d_hot_slots_;
-  pt.hot_n = &d_hot_ctl_->n;
+  pt.hot_slots = m_->d_hot_slots;
+  pt.hot_n = &m_->d_hot_ctl->n;
   pt.hot_cap = hot_cap_;
   pt.top_tau = ~0ull;
-  pt.top_slots = d_top_slots_;
-  pt.top_n = &d_top_ctl_->n;
+  pt.top_slots = m_->d_top_slots;
+  pt.top_n = &m_->d_top_ctl->n;
   pt.top_cap = top_cap_;
   hot_state_ = HOT_INVALID;
   top_state_ = TOP_INVALID;
   launch_pt_clear(pt, strm());
   HIP_CHECK(hipMemsetAsync(pt.n_keys, 0, 16, strm()));
 }
-void GpuCtx::free_table(PairTable &pt) {
-  DFREE(pt.slots);
-  DFREE(pt.n_keys);
-  pt.mask = 0;
+void GpuCtx::free_table() {
+  m_->pt = PairTableMem();
+  pt_.slots = nullptr;
+  pt_.n_keys = nullptr;
+  pt_.mask = 0;
+  pt_cap_ = 0;
 }
 
 void GpuCtx::ensure_table_capacity(unsigned long long need_keys) {
@@ -34,18 +38,19 @@ void GpuCtx::ensure_table_capacity(unsigned long long need_keys) {
   // load stays below 1/2; growth is by 4x (a rehash also costs a rebuild of the hot list)
   unsigned long long new_cap = pow2_at_least(std::max<unsigned long long>(1ull << 16, need_keys * 4));
   if (!pt_cap_) {
-    alloc_table(pt_, new_cap);
+    alloc_table(m_->pt, pt_, new_cap);
     pt_cap_ = new_cap;
     return;
   }
+  PairTableMem nm;
   PairTable nt{};
-  alloc_table(nt, new_cap);
+  alloc_table(nm, nt, new_cap);
   launch_pt_rehash(pt_, nt, strm());
   rehashes++;
   unsigned int nk = 0;
   HIP_CHECK(hipMemcpyAsync(&nk, nt.n_keys, 4, hipMemcpyDeviceToHost, strm()));
   sync();
-  free_table(pt_);
+  m_->pt = std::move(nm);  // (the old table goes back to the pool here)
   pt_ = nt;
   pt_cap_ = new_cap;
   n_keys_host = nk;
@@ -68,7 +73,7 @@ void GpuCtx::pair_count() {
   unsigned long long bound = initial_table_keys(n_tokens0);
   if (multi()) {
     bound = std::min<unsigned long long>(bound * comm_->world, 1ull << 27);
-    if (!d_send2_[0]) {
+    if (!m_->delta.send[0]) {
       // distinct pairs a round of this rank can touch: bounded by its updates (a handful per live token); sized for a
       // quarter of that -- dense rounds touch few distinct pairs, sparse rounds few tokens -- and checked: a rank whose table or
       // send block overflowed says so in its block's header and every rank stops
@@ -81,12 +86,12 @@ void GpuCtx::pair_count() {
         delta_cap_forced_ = true;
       }
       alloc_delta_table(cap);
-      d_xstat_ = dmalloc<unsigned long long>(XSTAT_WORDS);
-      HIP_CHECK(hipMemsetAsync(d_xstat_, 0, XSTAT_WORDS * 8, strm()));
+      m_->d_xstat.alloc(XSTAT_WORDS);
+      HIP_CHECK(hipMemsetAsync(m_->d_xstat, 0, XSTAT_WORDS * 8, strm()));
       maybe_cap_ = std::max(1u, (unsigned int)cfg_->xchg_notes.u);  // (tests shrink it: the fold then walks every record)
-      d_maybe_ = dmalloc<uint32_t>(maybe_cap_);
-      d_maybe_ctl_ = dmalloc<ListCtl>(1);
-      HIP_CHECK(hipMemsetAsync(d_maybe_ctl_, 0, sizeof(ListCtl), strm()));
+      m_->d_maybe.alloc(maybe_cap_);
+      m_->d_maybe_ctl.alloc(1);
+      HIP_CHECK(hipMemsetAsync(m_->d_maybe_ctl, 0, sizeof(ListCtl), strm()));
       blk_min_ = std::max(2u * XHDR, (unsigned int)cfg_->xchg_blk_min.u);  // (tests shrink it to force the repeat path)
       blk_ = blk_min_;
       grow_recv(std::max<unsigned long long>(send_cap_, blk_ * (unsigned long long)comm_->world));
@@ -94,8 +99,7 @@ void GpuCtx::pair_count() {
   }
   if (multi()) bound = std::max(bound, std::min<unsigned long long>(n_tokens0 / 16 * (unsigned long long)comm_->world, 1ull << 25));
   if (!pt_fresh_ || bound * 2 > pt_cap_) {  // (normally build_class(0) has put a cleared table of this size in place)
-    free_table(pt_);
-    pt_cap_ = 0;
+    free_table();
   }
   pt_fresh_ = false;
   ensure_table_capacity(bound);
@@ -103,26 +107,28 @@ void GpuCtx::pair_count() {
   const uint32_t n_ids = id_max_ >= id_min_ ? id_max_ - id_min_ + 1 : 0;
   // class A of a large alphabet (CJK: thousands of symbols, millions of pairs): records partitioned by their first token instead of one random
   // atomic per adjacency (k_pairradix.hip; 16 B of scratch per class-A token for the length of the count)
-  uint32_t *rx_scratch = nullptr;
-  unsigned long long *rx_buf1 = nullptr, *rx_buf2 = nullptr;
+  PoolBuf<uint32_t> rx_scratch;
+  PoolBuf<unsigned long long> rx_buf1, rx_buf2;
   // (its scratch -- two 8-byte records per class-A token -- must fit what is free with room to spare: else the general kernel, never an out-of-memory)
-  bool radix = cls_[0].n_tiles && pair_count_radix_takes(n_ids, cls_[0].n_tokens0) && cls_[0].n_tokens0 >= cfg_->k3_radix_min.u && !cfg_->k3_general.set &&
-               16ull * (cls_[0].n_tokens0 + 1) + (64ull << 20) <= free_device_bytes() / 4 * 3;
+  bool radix = m_->cls[0].n_tiles && pair_count_radix_takes(n_ids, m_->cls[0].n_tokens0) && m_->cls[0].n_tokens0 >= cfg_->k3_radix_min.u && !cfg_->k3_general.set &&
+               16ull * (m_->cls[0].n_tokens0 + 1) + (64ull << 20) <= free_device_bytes() / 4 * 3;
   if (radix) {
-    rx_scratch = dmalloc<uint32_t>(pair_count_radix_scratch_u32(n_ids));
-    rx_buf1 = dmalloc<unsigned long long>(cls_[0].n_tokens0 + 1);
-    rx_buf2 = dmalloc<unsigned long long>(cls_[0].n_tokens0 + 1);
+    rx_scratch.alloc(pair_count_radix_scratch_u32(n_ids));
+    rx_buf1.alloc(m_->cls[0].n_tokens0 + 1);
+    rx_buf2.alloc(m_->cls[0].n_tokens0 + 1);
     HIP_CHECK(hipMemsetAsync(rx_scratch, 0, (size_t)n_ids * 4, strm()));
-    radix = launch_pair_count_radix(cls_[0].ts, pt_, db_, id_min_, n_ids, rx_scratch, rx_buf1, rx_buf2, cls_[0].n_tokens0, strm());  // (false: nothing launched)
+    radix = launch_pair_count_radix(m_->cls[0].ts, pt_, db_, id_min_, n_ids, rx_scratch, rx_buf1, rx_buf2, m_->cls[0].n_tokens0, strm());  // (false: nothing launched)
     k3_radix = radix ? 1 : 0;
   }
-  for (int ci = radix ? 1 : 0; ci < 2; ci++) launch_pair_count(ci, cls_[ci].ts, pt_, db_, id_min_, n_ids, strm());
-  launch_giant(false, cls_[2].ts, cls_[2].slot, pt_, db_, nullptr, 0, 0xffffffffu, 0, cls_[2].d_scratch, d_stats_, strm());
+  for (int ci = radix ? 1 : 0; ci < 2; ci++) launch_pair_count(ci, m_->cls[ci].ts, pt_, db_, id_min_, n_ids, strm());
+  launch_giant(false, m_->cls[2].ts, m_->cls[2].slot, pt_, db_, nullptr, 0, 0xffffffffu, 0, m_->cls[2].d_scratch, m_->d_stats, strm());
   t_end(KT_PAIR_COUNT, 4 * n_tokens0 + 8 * n_unique);
   unsigned int nk = 0;
   HIP_CHECK(hipMemcpyAsync(&nk, pt_.n_keys, 4, hipMemcpyDeviceToHost, strm()));
   sync();
-  DFREE(rx_scratch); DFREE(rx_buf1); DFREE(rx_buf2);
+  rx_scratch.reset();
+  rx_buf1.reset();
+  rx_buf2.reset();
   n_keys_host = nk;
   exchange_deltas();
 }
@@ -143,7 +149,7 @@ void GpuCtx::download_pairs(std::vector<unsigned long long> &keys, std::vector<u
 unsigned int GpuCtx::fetch_candidates(CandRec *h, unsigned int n, std::vector<CandRec> &out) {
   const unsigned int take = std::min(n, cand_cap_);
   if (take > CAND_FAST) {
-    HIP_CHECK(hipMemcpyAsync(h + CAND_FAST, d_round_->cand + CAND_FAST, (size_t)(take - CAND_FAST) * sizeof(CandRec), hipMemcpyDeviceToHost, strm()));
+    HIP_CHECK(hipMemcpyAsync(h + CAND_FAST, m_->d_round->cand + CAND_FAST, (size_t)(take - CAND_FAST) * sizeof(CandRec), hipMemcpyDeviceToHost, strm()));
     sync();
   }
   out.assign(h, h + take);
@@ -163,16 +169,16 @@ uint32_t GpuCtx::scan_full(unsigned long long tau_cnt, uint32_t tau_mx, std::vec
     return 0;
   }
   flush_pending_zero();
-  launch_fold_stats(d_stats_, pt_.n_keys, strm());
-  HIP_CHECK(hipMemsetAsync(d_round_->n_out, 0, sizeof d_round_->n_out, strm()));
-  HIP_CHECK(hipMemsetAsync(d_round_->hist, 0, CAND_BINS * 8, strm()));
+  launch_fold_stats(m_->d_stats, pt_.n_keys, strm());
+  HIP_CHECK(hipMemsetAsync(m_->d_round->n_out, 0, sizeof m_->d_round->n_out, strm()));
+  HIP_CHECK(hipMemsetAsync(m_->d_round->hist, 0, CAND_BINS * 8, strm()));
   t_begin(KT_CAND);
-  launch_cand_scan(pt_, tau_cnt, tau_mx, d_round_->cand, cand_cap_, d_round_->n_out, d_round_->hist, strm());  // (always with the histogram: last_hist())
+  launch_cand_scan(pt_, tau_cnt, tau_mx, m_->d_round->cand, cand_cap_, m_->d_round->n_out, m_->d_round->hist, strm());  // (always with the histogram: last_hist())
   t_end(KT_CAND, 16 * pt_cap_);
   // ONE device-to-host copy per round: header + histogram + the first CAND_FAST candidates; a second copy only when
   // more candidates passed (the host rarely looks past a few thousand)
   const RoundBlock &h = h_pin_->round;  // (the device's round block, copied over the mailbox)
-  HIP_CHECK(hipMemcpyAsync(&h_pin_->round, d_round_, offsetof(RoundBlock, cand) + (size_t)CAND_FAST * sizeof(CandRec), hipMemcpyDeviceToHost, strm()));
+  HIP_CHECK(hipMemcpyAsync(&h_pin_->round, m_->d_round, offsetof(RoundBlock, cand) + (size_t)CAND_FAST * sizeof(CandRec), hipMemcpyDeviceToHost, strm()));
   sync();
   const unsigned int n = h.n_out[0];
   n_keys_host = h.n_out[1];
@@ -183,8 +189,8 @@ uint32_t GpuCtx::scan_full(unsigned long long tau_cnt, uint32_t tau_mx, std::vec
   last_top_bin_ = CAND_BINS - 1;
   for (int b = 1; b < CAND_BINS; b++) last_live_ += hist_buf_[b];
   fetch_candidates(h_pin_->round.cand, n, out);
-  HIP_CHECK(hipMemsetAsync(d_round_->n_out, 0, sizeof d_round_->n_out, strm()));  // the hot-list filter expects its counters cleared
-  HIP_CHECK(hipMemsetAsync(d_round_->hist, 0, CAND_BINS * 8, strm()));
+  HIP_CHECK(hipMemsetAsync(m_->d_round->n_out, 0, sizeof m_->d_round->n_out, strm()));  // the hot-list filter expects its counters cleared
+  HIP_CHECK(hipMemsetAsync(m_->d_round->hist, 0, CAND_BINS * 8, strm()));
   return n;
 }
 
@@ -216,7 +222,7 @@ void GpuCtx::rebuild_hot() {
     return;
   }
   pt_.hot_tau = std::max<unsigned long long>(1, cand_bin_lower(chosen));
-  HIP_CHECK(hipMemsetAsync(&d_hot_ctl_->n, 0, 4, strm()));
+  HIP_CHECK(hipMemsetAsync(&m_->d_hot_ctl->n, 0, 4, strm()));
   t_begin(KT_CAND);
   launch_hot_rebuild(pt_, strm());
   t_end(KT_CAND, 8 * pt_cap_);
@@ -230,7 +236,7 @@ ScanArgs GpuCtx::scan_args(unsigned long long tau_cnt, uint32_t tau_mx, uint32_t
   sa.on = 1u;
   sa.tau_cnt = tau_cnt;
   sa.tau_mx = tau_mx;
-  sa.out = d_round_->cand;
+  sa.out = m_->d_round->cand;
   sa.cap = cand_cap_;
   sa.fast = CAND_FAST;
   sa.mailbox = &h_pin_->mailbox;
@@ -284,13 +290,13 @@ bool GpuCtx::scan_hot(unsigned long long t, uint32_t tm) {
   HotScan hs{};
   hs.pt = pt_;
   hs.sa = scan_args(t, tm, ++mail_round_);
-  hs.sa.done_ctr = &d_hot_ctl_->ticket;
-  hs.n_out = d_round_->n_out;
-  hs.hist = d_round_->hist;
-  hs.stats = d_stats_;
+  hs.sa.done_ctr = &m_->d_hot_ctl->ticket;
+  hs.n_out = m_->d_round->n_out;
+  hs.hist = m_->d_round->hist;
+  hs.stats = m_->d_stats;
   hs.zero = zero_batch();
   hs.listed_hint = listed_last_ ? listed_last_ + 4096 : hot_cap_;
-  hs.xstat = multi() ? d_xstat_ : nullptr;
+  hs.xstat = multi() ? m_->d_xstat.p : nullptr;
   t_begin(KT_CAND);
   launch_hot_scan(hs, strm());
   pending_zero_ = false;
@@ -332,7 +338,7 @@ bool GpuCtx::refill_top() {
     return true;
   }
   pt_.top_tau = std::max<unsigned long long>(pt_.hot_tau, cand_bin_lower(chosen));
-  HIP_CHECK(hipMemsetAsync(&d_top_ctl_->n, 0, 4, strm()));
+  HIP_CHECK(hipMemsetAsync(&m_->d_top_ctl->n, 0, 4, strm()));
   t_begin(KT_CAND);
   launch_top_rebuild(pt_, listed_last_, strm());
   t_end(KT_CAND, 20ull * listed_last_);
@@ -366,8 +372,8 @@ uint32_t GpuCtx::candidates(unsigned long long tau_cnt, uint32_t tau_mx, std::ve
       // whole-table scans ahead (list rebuild, or no list at all): they synchronise anyway, so the verdict of this round's
       // exchange is fetched directly instead of travelling with the mailbox
       unsigned long long x[4] = {0, 0, 0, 0};
-      HIP_CHECK(hipMemcpyAsync(x, d_xstat_, 32, hipMemcpyDeviceToHost, strm()));
-      HIP_CHECK(hipMemsetAsync(d_xstat_, 0, 32, strm()));
+      HIP_CHECK(hipMemcpyAsync(x, m_->d_xstat, 32, hipMemcpyDeviceToHost, strm()));
+      HIP_CHECK(hipMemsetAsync(m_->d_xstat, 0, 32, strm()));
       sync();
       settle_exchange(x[0], x[1], x[3]);
     }
@@ -403,7 +409,7 @@ uint32_t GpuCtx::candidates(unsigned long long tau_cnt, uint32_t tau_mx, std::ve
       const uint32_t round_id = use_fused ? fused_round_ : ++mail_round_;
       if (!use_fused) {
         t_begin(KT_CAND);
-        launch_top_scan(pt_, scan_args(t, tm, round_id), d_stats_, zero_batch(), multi() ? d_xstat_ : nullptr, strm());
+        launch_top_scan(pt_, scan_args(t, tm, round_id), m_->d_stats, zero_batch(), multi() ? m_->d_xstat.p : nullptr, strm());
         pending_zero_ = false;
         t_end(KT_CAND, 20ull * top_listed_last_);
       }
@@ -484,18 +490,16 @@ void GpuCtx::pair_query(const unsigned long long *keys, uint32_t n, unsigned lon
   if (!n) return;
   if (fused_pending_) throw GpuError{"pair_query: a candidate scan rides in the last merge round -- call candidates first"};
   flush_pending_zero();
-  unsigned long long *d_k = dmalloc<unsigned long long>(n), *d_o = dmalloc<unsigned long long>(n);
+  PoolBuf<unsigned long long> d_k(n), d_o(n);
   HIP_CHECK(hipMemcpyAsync(d_k, keys, (size_t)n * 8, hipMemcpyHostToDevice, strm()));
   launch_pt_query(pt_, d_k, n, d_o, strm());
   HIP_CHECK(hipMemcpyAsync(outv, d_o, (size_t)n * 8, hipMemcpyDeviceToHost, strm()));
   sync();
-  DFREE(d_k);
-  DFREE(d_o);
 }
 
 ZeroBatch GpuCtx::zero_batch() const {
   const bool by_args = zero_ba_.k != 0;  // (the batch travelled as a kernel argument: its rule hash never went to HBM)
-  return ZeroBatch{pending_zero_ && !by_args ? d_rules_ : nullptr, zero_cap_ - 1, zero_self_key_, pending_zero_ && by_args ? &zero_ba_ : nullptr};
+  return ZeroBatch{pending_zero_ && !by_args ? m_->d_rules.p : nullptr, zero_cap_ - 1, zero_self_key_, pending_zero_ && by_args ? &zero_ba_ : nullptr};
 }
 
 void GpuCtx::flush_pending_zero() {
@@ -504,10 +508,10 @@ void GpuCtx::flush_pending_zero() {
   if (zero_ba_.k) {  // the batch never went to HBM: upload its rule hash for k_pt_zero (rare: only readers other than the hot scan)
     std::vector<RuleSlot> tab(zero_cap_);
     build_rule_hash(tab.data(), zero_cap_, zero_ba_.xy, 2, zero_ba_.k);
-    HIP_CHECK(hipMemcpyAsync(d_rules_, tab.data(), tab.size() * sizeof(RuleSlot), hipMemcpyHostToDevice, strm()));
+    HIP_CHECK(hipMemcpyAsync(m_->d_rules, tab.data(), tab.size() * sizeof(RuleSlot), hipMemcpyHostToDevice, strm()));
     sync();
   }
-  launch_pt_zero(pt_, d_rules_, zero_cap_, zero_self_key_, strm());
+  launch_pt_zero(pt_, m_->d_rules, zero_cap_, zero_self_key_, strm());
   pending_zero_ = false;
 }
 

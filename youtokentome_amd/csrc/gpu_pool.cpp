@@ -33,13 +33,21 @@ DevPool g_pool;
 void *g_pin_cached = nullptr;  // one pinned staging buffer (PIN_BYTES) kept between contexts
 std::vector<std::pair<int, hipStream_t>> g_streams_cached;  // streams of finished contexts, by device (creating and destroying one costs ~2 ms of a training)
 constexpr size_t POOL_MAX_CACHED = 96ull << 30;  // (a third of the HBM: the segment starts of 4.4e9 one-letter words alone are 35 GB)
+std::atomic<unsigned long long> g_alloc_calls{0};    // pool_alloc calls since the last context was made (pool_arm)
+std::atomic<unsigned long long> g_alloc_fail_at{0};  // YTTM_TEST_ALLOC_FAIL: the call among them that throws (0: none)
 }  // namespace
+
+void pool_arm(unsigned long long fail_at) {
+  g_alloc_calls.store(0, std::memory_order_relaxed);
+  g_alloc_fail_at.store(fail_at, std::memory_order_relaxed);
+}
 
 bool pool_enabled() {
   static const bool on = !(cfg()->no_pool.set && cfg()->no_pool.raw.c_str()[0] == '1');  // (one verdict per process: blocks cached under one policy are not freed under the other)
   return on;
 }
 void *pool_alloc(size_t bytes) {
+  if (g_alloc_calls.fetch_add(1, std::memory_order_relaxed) + 1 == g_alloc_fail_at.load(std::memory_order_relaxed)) throw GpuError{"pool_alloc: injected failure"};
   if (bytes == 0) bytes = 1;
   bytes = (bytes + 255) & ~(size_t)255;
   if (pool_enabled()) {
@@ -112,6 +120,13 @@ unsigned long long pool_peak_bytes() {
 void pool_reset_peak() {
   std::lock_guard<std::mutex> g(g_pool.mu);
   g_pool.peak = g_pool.in_use;
+}
+void pool_stats(unsigned long long out[4]) {
+  std::lock_guard<std::mutex> g(g_pool.mu);
+  out[0] = g_pool.in_use;
+  out[1] = g_pool.cached;
+  out[2] = g_pool.peak;
+  out[3] = g_alloc_calls.load(std::memory_order_relaxed);
 }
 hipStream_t pool_take_stream(int device) {
   if (!pool_enabled()) return nullptr;

@@ -23,11 +23,10 @@ void GpuCtx::upload_corpus(const uint8_t *host, unsigned long long n) {
     HIP_CHECK(hipSetDevice(device_));
     tl_stream = strm();
     tl_device = device_;
-    DFREE(d_text_owned_);
-    d_text_owned_ = dmalloc<uint8_t>(n + 64);
-    if (n) HIP_CHECK(hipMemcpyAsync(d_text_owned_, host, n, hipMemcpyHostToDevice, strm()));
+    m_->d_text_owned.alloc(n + 64);
+    if (n) HIP_CHECK(hipMemcpyAsync(m_->d_text_owned, host, n, hipMemcpyHostToDevice, strm()));
     sync();
-    d_text_ = d_text_owned_;
+    d_text_ = m_->d_text_owned;
     n_text_ = n;
     corpus_bytes = n;
     return;
@@ -86,13 +85,12 @@ void GpuCtx::upload_staged(unsigned long long n, const std::function<bool(void *
   HIP_CHECK(hipSetDevice(device_));
   tl_stream = strm();
   tl_device = device_;
-  DFREE(d_text_owned_);
-  d_text_owned_ = dmalloc<uint8_t>(n + 64);
-  d_text_ = d_text_owned_;
+  m_->d_text_owned.alloc(n + 64);
+  d_text_ = m_->d_text_owned;
   n_text_ = n;
   corpus_bytes = n;
   if (!n) return;
-  staged_transfer(device_, d_text_owned_, n, true, fill);
+  staged_transfer(device_, m_->d_text_owned, n, true, fill);
 }
 
 // n bytes between HBM and the host through the workers' pinned chunks.  to_device: host_side(chunk, off, len) FILLS the pinned chunk with
@@ -242,10 +240,7 @@ void staged_transfer(int device, uint8_t *d_ptr, unsigned long long n, bool to_d
   if (failed.load()) throw GpuError{first_error};
 }
 
-void GpuCtx::drop_spec() {
-  if (spec_.ht) DFREE(spec_.ht);
-  spec_ = FrontSpec();
-}
+void GpuCtx::drop_spec() { m_->spec = FrontSpec(); }
 
 // The front end under the upload (single GPU).  A GB of file needs 18 ms on the link, and the device idles through them; K1, K2a and K2b of
 // the same GB are 10 ms of work that needs nothing but the bytes: K1 and K2a by construction, K2b -- the dedup -- if every word is compared
@@ -260,9 +255,8 @@ void GpuCtx::upload_overlapped(unsigned long long n, const std::function<bool(vo
   tl_stream = strm();
   tl_device = device_;
   drop_spec();
-  DFREE(d_text_owned_);
-  d_text_owned_ = dmalloc<uint8_t>(n + 64);
-  d_text_ = d_text_owned_;
+  m_->d_text_owned.alloc(n + 64);
+  d_text_ = m_->d_text_owned;
   n_text_ = n;
   corpus_bytes = n;
   // K1's variant from four samples of the SOURCE (char_hist samples the text in HBM, which is not there yet)
@@ -279,14 +273,13 @@ void GpuCtx::upload_overlapped(unsigned long long n, const std::function<bool(vo
     wide_chars = true;
   }
   if (cfg_->k1_wide.set) wide_chars = cfg_->k1_wide.i != 0;
-  if (!d_hist_) d_hist_ = dmalloc<unsigned long long>(N_CODEPOINTS);
-  HIP_CHECK(hipMemsetAsync(d_hist_, 0, (size_t)N_CODEPOINTS * 8, strm()));
-  HIP_CHECK(hipMemsetAsync(d_counters_, 0, 64 * 8, strm()));
+  if (!m_->d_hist) m_->d_hist.alloc(N_CODEPOINTS);
+  HIP_CHECK(hipMemsetAsync(m_->d_hist, 0, (size_t)N_CODEPOINTS * 8, strm()));
+  HIP_CHECK(hipMemsetAsync(m_->ctr, 0, sizeof(CounterBlock), strm()));
   const unsigned long long nch = fe_chunks(n);
-  DFREE(d_chunk_segs_);
-  d_chunk_segs_ = dmalloc<uint32_t>(nch + 1);
+  m_->d_chunk_segs.alloc(nch + 1);
   // the speculative map: a char's id is its code point
-  uint32_t *d_cpmap_spec = dmalloc<uint32_t>(N_CODEPOINTS);
+  PoolBuf<uint32_t> d_cpmap_spec(N_CODEPOINTS);
   {
     static std::vector<uint32_t> ident;
     static std::once_flag once;
@@ -298,7 +291,7 @@ void GpuCtx::upload_overlapped(unsigned long long n, const std::function<bool(vo
     });
     HIP_CHECK(hipMemcpyAsync(d_cpmap_spec, ident.data(), (size_t)N_CODEPOINTS * 4, hipMemcpyHostToDevice, strm()));
   }
-  unsigned long long *d_chunk_off = dmalloc<unsigned long long>(nch + 1);
+  PoolBuf<unsigned long long> d_chunk_off(nch + 1);
   // ---- the upload, on a thread of its own; what has landed, in order
   const size_t io_chunk = staged_chunk_bytes();
   const size_t n_io = (size_t)((n + io_chunk - 1) / io_chunk);
@@ -320,7 +313,7 @@ void GpuCtx::upload_overlapped(unsigned long long n, const std::function<bool(vo
   };
   std::thread up([&] {
     try {
-      staged_transfer(device_, d_text_owned_, n, true, fill_or_stop, [&](unsigned long long off, size_t) {
+      staged_transfer(device_, m_->d_text_owned, n, true, fill_or_stop, [&](unsigned long long off, size_t) {
         std::lock_guard<std::mutex> g(mu);
         landed[(size_t)(off / io_chunk)] = 1;
         bool moved = false;
@@ -357,8 +350,9 @@ void GpuCtx::upload_overlapped(unsigned long long n, const std::function<bool(vo
   part = std::max(FC, part / FC * FC);
   bool spec_on = !cfg_->fe_no_spec.set;
   const unsigned int k2b_blocks = (unsigned int)cfg_->fe_k2b_blocks.u;  // (tuning hook)
-  unsigned long long *d_seg = nullptr, seg_cap = 0, base = 0;
-  unsigned int *d_status = (unsigned int *)(d_counters_ + 24);
+  PoolBuf<unsigned long long> d_seg;
+  unsigned long long seg_cap = 0, base = 0;
+  unsigned int *d_status = m_->ctr->status;
   unsigned long long pending = 0;  // the last segment so far: not inserted yet
   bool have_pending = false;
   std::string fail;
@@ -368,27 +362,27 @@ void GpuCtx::upload_overlapped(unsigned long long n, const std::function<bool(vo
       if (!wait_for(std::min(n, b1 + FC))) break;
       const unsigned long long c_lo = b0 / FC, c_hi = fe_chunks(b1);
       t_begin(KT_CHAR_HIST);
-      launch_char_hist(d_text_, n, d_hist_, d_counters_, wide_chars, d_chunk_segs_, strm(), c_lo, c_hi);
+      launch_char_hist(d_text_, n, m_->d_hist, m_->ctr->hist_totals, wide_chars, m_->d_chunk_segs, strm(), c_lo, c_hi);
       t_end(KT_CHAR_HIST, b1 - b0);
       if (!spec_on) continue;
       // the part's segments: where they go (relative to the part's first), how many
-      unsigned long long *scan_tmp = dmalloc<unsigned long long>(scan_scratch_blocks(c_hi - c_lo));
+      PoolBuf<unsigned long long> scan_tmp(scan_scratch_blocks(c_hi - c_lo));
       t_begin(KT_SEGS);
-      launch_exclusive_scan(d_chunk_segs_ + c_lo, c_hi - c_lo, d_chunk_off + c_lo, scan_tmp, d_counters_ + 16, strm());
+      launch_exclusive_scan(m_->d_chunk_segs + c_lo, c_hi - c_lo, d_chunk_off + c_lo, scan_tmp, &m_->ctr->chunk_scan_total, strm());
       unsigned long long n_p = 0;
-      HIP_CHECK(hipMemcpyAsync(&n_p, d_counters_ + 16, 8, hipMemcpyDeviceToHost, strm()));
+      HIP_CHECK(hipMemcpyAsync(&n_p, &m_->ctr->chunk_scan_total, 8, hipMemcpyDeviceToHost, strm()));
       sync();
-      DFREE(scan_tmp);
+      scan_tmp.reset();
       if (b0 == 0) {  // sizes from the first part's density of segments (build_word_table's rules, on an estimate)
         const double est = (double)n_p * ((double)n / (double)(b1 - b0)) * 1.1 + 1024.0;
         seg_cap = (unsigned long long)(est * 1.1);
-        d_seg = dmalloc<unsigned long long>(seg_cap);
-        spec_.long_segments = n_p == 0 || (b1 - b0) / std::max<unsigned long long>(n_p, 1) >= 16;
+        d_seg.alloc(seg_cap);
+        m_->spec.long_segments = n_p == 0 || (b1 - b0) / std::max<unsigned long long>(n_p, 1) >= 16;
         const unsigned long long ns = (unsigned long long)est;
-        spec_.ht_cap = !spec_.long_segments && !cfg_->word_table_full.set ? pow2_at_least(std::max<unsigned long long>(ns / 4, 1ull << 16))
+        m_->spec.ht_cap = !m_->spec.long_segments && !cfg_->word_table_full.set ? pow2_at_least(std::max<unsigned long long>(ns / 4, 1ull << 16))
                                                                                 : pow2_at_least(ns + ns / 2 + 1024);
-        spec_.ht = dmalloc<unsigned long long>(3 * spec_.ht_cap);
-        launch_word_table_clear(spec_.ht, spec_.ht_cap, strm());
+        m_->spec.ht.alloc(3 * m_->spec.ht_cap);
+        launch_word_table_clear(m_->spec.ht, m_->spec.ht_cap, strm());
         HIP_CHECK(hipMemsetAsync(d_status, 0, 32, strm()));
       }
       if (base + n_p > seg_cap) {  // denser than the first part promised: no room for the segment starts -- the usual way then
@@ -404,7 +398,7 @@ void GpuCtx::upload_overlapped(unsigned long long n, const std::function<bool(vo
         const unsigned long long from = have_pending ? pending : base, to = base + n_p - 1;
         if (to > from) {
           t_begin(KT_DEDUP);
-          launch_insert_words(d_text_, n, d_cpmap_spec, d_seg + from, to - from, spec_.ht, spec_.ht_cap - 1, d_status, strm(), k2b_blocks);
+          launch_insert_words(d_text_, n, d_cpmap_spec, d_seg + from, to - from, m_->spec.ht, m_->spec.ht_cap - 1, d_status, strm(), k2b_blocks);
           t_end(KT_DEDUP, (b1 - b0) + 8 * n_p);
         }
         pending = to;
@@ -423,30 +417,30 @@ void GpuCtx::upload_overlapped(unsigned long long n, const std::function<bool(vo
       if (spec_on && d_seg) {
         if (have_pending) {
           t_begin(KT_DEDUP);
-          launch_insert_words(d_text_, n, d_cpmap_spec, d_seg + pending, 1, spec_.ht, spec_.ht_cap - 1, d_status, strm());
+          launch_insert_words(d_text_, n, d_cpmap_spec, d_seg + pending, 1, m_->spec.ht, m_->spec.ht_cap - 1, d_status, strm());
           t_end(KT_DEDUP, 0);
         }
-        HIP_CHECK(hipMemcpyAsync(spec_.h_status, d_status, 32, hipMemcpyDeviceToHost, strm()));
+        HIP_CHECK(hipMemcpyAsync(m_->spec.h_status, d_status, 32, hipMemcpyDeviceToHost, strm()));
       }
       sync();
     } catch (const GpuError &e) {
       fail = e.msg;
     }
   }
-  DFREE(d_seg);
-  DFREE(d_chunk_off);
-  DFREE(d_cpmap_spec);
+  d_seg.reset();
+  d_chunk_off.reset();
+  d_cpmap_spec.reset();
   if (!fail.empty()) {
     drop_spec();
     throw GpuError{fail};
   }
   if (cfg_->trace.set)
     fprintf(stderr, "[yttm] front end under the upload: the last byte landed after %.2f ms, the last part was done after %.2f ms (%llu segments, parts of %llu MB, word table %s)\n",
-            ms_link, ms_now(), base, part >> 20, spec_on && spec_.ht ? "made" : "left to build_word_table");
-  spec_.hist_done = true;
-  spec_.n_segs = base;
-  spec_.words_done = spec_on && spec_.ht != nullptr;
-  if (!spec_.words_done && spec_.ht) DFREE(spec_.ht);
+            ms_link, ms_now(), base, part >> 20, spec_on && m_->spec.ht ? "made" : "left to build_word_table");
+  m_->spec.hist_done = true;
+  m_->spec.n_segs = base;
+  m_->spec.words_done = spec_on && m_->spec.ht != nullptr;
+  if (!m_->spec.words_done) m_->spec.ht.reset();
 }
 
 // (the front end under the upload: a text worth the trouble.  Round 5: on every rank of a multi-GPU run too -- K1, K2a and K2b of a rank's byte
@@ -530,7 +524,7 @@ void GpuCtx::front_end_chunked(bool first_pass) {
   unsigned long long C = (!first_pass && chunk_cap_) ? chunk_cap_ : chunk_bytes_for(n);  // (a second pass: the first one's size -- less memory is free now)
   if (!C) C = std::max<unsigned long long>(n / 4096 * 4096 + 4096, 4096);
   drop_spec();
-  DFREE(d_text_owned_);
+  m_->d_text_owned.reset();
   chunked_ = true;
   chunk_cap_ = C;
   corpus_bytes = n;
@@ -564,23 +558,20 @@ void GpuCtx::front_end_chunked(bool first_pass) {
   const unsigned long long GAP = 64, LEX0 = C + GAP;
   lex_cap_ = std::max<unsigned long long>(C / 4, 4096);
   lex_used_ = 0;
-  uint8_t *B = dmalloc<uint8_t>(LEX0 + lex_cap_ + 2 * GAP);
-  d_text_owned_ = B;
+  m_->d_text_owned.alloc(LEX0 + lex_cap_ + 2 * GAP);
+  uint8_t *B = m_->d_text_owned;
   d_text_ = B;
   const unsigned long long sub = std::min<unsigned long long>(std::max<unsigned long long>(C / 16, 256), 4ull << 20);  // segments per K2b launch
   unsigned long long cap = pow2_at_least(std::max<unsigned long long>(4 * sub, 1024));
-  // every block this function holds in a local: freed when it is left by a throw as well (a caller that catches the error and retries -- the C
-  // ABI's guarded() -- must not lose up to a chunk of HBM per attempt); `landing` outlives the uploader's future (Landed, declared below)
-  unsigned long long *ht = nullptr, *nht = nullptr, *d_seg = nullptr, *d_chunk_off = nullptr, *scan_tmp = nullptr, *scratch_hist = nullptr;
-  uint32_t *d_map_spec = nullptr;
-  uint8_t *landing = nullptr;
-  DevScope scope;
-  scope.hold(ht); scope.hold(nht); scope.hold(d_seg); scope.hold(d_chunk_off); scope.hold(scan_tmp); scope.hold(scratch_hist); scope.hold(d_map_spec); scope.hold(landing);
-  ht = dmalloc<unsigned long long>(3 * cap);
+  // (`landing` outlives the uploader's future: Landed, declared below)
+  PoolBuf<unsigned long long> ht, d_seg, d_chunk_off, scan_tmp, scratch_hist;
+  PoolBuf<uint32_t> d_map_spec;
+  PoolBuf<uint8_t> landing;
+  ht.alloc(3 * cap);
   launch_word_table_clear(ht, cap, strm());
-  unsigned int *d_status = (unsigned int *)(d_counters_ + 24);
+  unsigned int *d_status = m_->ctr->status;
   HIP_CHECK(hipMemsetAsync(d_status, 0, 32, strm()));
-  unsigned long long *d_cur = d_counters_ + 56;  // [0] the lexicon's end (an offset into B), [1] bytes a relocation will need
+  unsigned long long *d_cur = m_->ctr->lexicon_cur;  // [0] the lexicon's end (an offset into B), [1] bytes a relocation will need
   {
     const unsigned long long init[2] = {LEX0, 0};
     HIP_CHECK(hipMemcpyAsync(d_cur, init, 16, hipMemcpyHostToDevice, strm()));
@@ -599,40 +590,39 @@ void GpuCtx::front_end_chunked(bool first_pass) {
   if (cfg_->k1_wide.set) wide_chars = cfg_->k1_wide.i != 0;
   unsigned long long *hist = nullptr, *counters = nullptr;
   if (first_pass) {
-    if (!d_hist_) d_hist_ = dmalloc<unsigned long long>(N_CODEPOINTS);
-    HIP_CHECK(hipMemsetAsync(d_hist_, 0, (size_t)N_CODEPOINTS * 8, strm()));
-    HIP_CHECK(hipMemsetAsync(d_counters_, 0, 24 * 8, strm()));
-    hist = d_hist_;
-    counters = d_counters_;
+    if (!m_->d_hist) m_->d_hist.alloc(N_CODEPOINTS);
+    HIP_CHECK(hipMemsetAsync(m_->d_hist, 0, (size_t)N_CODEPOINTS * 8, strm()));
+    HIP_CHECK(hipMemsetAsync(m_->ctr, 0, offsetof(CounterBlock, status), strm()));  // (status and lexicon_cur are live)
+    hist = m_->d_hist;
+    counters = m_->ctr->hist_totals;
   } else {  // (the second pass needs K1 only for the chunks' segment counts: its histogram and counters go to a scratch copy)
-    scratch_hist = dmalloc<unsigned long long>(N_CODEPOINTS + 8);
+    scratch_hist.alloc(N_CODEPOINTS + 8);
     HIP_CHECK(hipMemsetAsync(scratch_hist, 0, ((size_t)N_CODEPOINTS + 8) * 8, strm()));
     hist = scratch_hist;
     counters = scratch_hist + N_CODEPOINTS;
   }
   // the char map words are compared by: code points (first pass) or the alphabet's ids
-  const uint32_t *d_map = d_cpmap_;
+  const uint32_t *d_map = m_->d_cpmap;
   if (first_pass) {
     std::vector<uint32_t> ident(N_CODEPOINTS);
     for (uint32_t c = 0; c < N_CODEPOINTS; c++) ident[c] = c;
     for (uint32_t sp : {9u, 10u, 11u, 12u, 13u, 32u, 9601u}) ident[sp] = CP_SPACE;
-    d_map_spec = dmalloc<uint32_t>(N_CODEPOINTS);
+    d_map_spec.alloc(N_CODEPOINTS);
     HIP_CHECK(hipMemcpyAsync(d_map_spec, ident.data(), (size_t)N_CODEPOINTS * 4, hipMemcpyHostToDevice, strm()));
     sync();  // (ident goes out of scope)
     d_map = d_map_spec;
   }
   const unsigned long long nch_max = fe_chunks(C) + 2;
-  DFREE(d_chunk_segs_);
-  d_chunk_segs_ = dmalloc<uint32_t>(nch_max);
-  d_chunk_off = dmalloc<unsigned long long>(nch_max);
-  scan_tmp = dmalloc<unsigned long long>(scan_scratch_blocks(nch_max));
+  m_->d_chunk_segs.alloc(nch_max);
+  d_chunk_off.alloc(nch_max);
+  scan_tmp.alloc(scan_scratch_blocks(nch_max));
   unsigned long long segs_total = 0, n_unique_host = 0;
   unsigned int h_status[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const auto t0 = std::chrono::steady_clock::now();
   // The link and the kernels at once: chunk k + 1 crosses the link into a landing buffer of its own while the kernels work on chunk k in
   // the region; a device-to-device copy (C bytes at HBM's rate: 0.3 ms per 512 MB) then moves it over.  Two regions the kernels alternate
   // between would save that copy and cost every offset in the word table a region base; the copy is 1 % of a chunk's upload.
-  landing = n_chunks > 1 && !cfg_->fe_chunk_serial.set ? dmalloc<uint8_t>(C) : nullptr;
+  if (n_chunks > 1 && !cfg_->fe_chunk_serial.set) landing.alloc(C);
   auto upload = [&](size_t ck, uint8_t *dst) {
     const unsigned long long b0 = cuts[ck], len = cuts[ck + 1] - b0;
     if (len) staged_transfer(device_, dst, len, true, [&fill, b0](void *d, unsigned long long off, size_t l) { return fill(d, b0 + off, l); });
@@ -644,7 +634,7 @@ void GpuCtx::front_end_chunked(bool first_pass) {
       if (f.valid()) f.wait();
     }
   } landed{in_flight};
-  if (landing) in_flight = std::async(std::launch::async, upload, (size_t)0, landing);
+  if (landing) in_flight = std::async(std::launch::async, upload, (size_t)0, landing.p);
   for (size_t ck = 0; ck < n_chunks; ck++) {
     const unsigned long long len = cuts[ck + 1] - cuts[ck];
     // ---- the chunk, then spaces behind it (its last segment ends there if the text does not end with white space)
@@ -652,7 +642,7 @@ void GpuCtx::front_end_chunked(bool first_pass) {
       in_flight.get();  // (rethrows the uploader's error)
       if (len) HIP_CHECK(hipMemcpyAsync(B, landing, (size_t)len, hipMemcpyDeviceToDevice, strm()));
       sync();
-      if (ck + 1 < n_chunks) in_flight = std::async(std::launch::async, upload, ck + 1, landing);
+      if (ck + 1 < n_chunks) in_flight = std::async(std::launch::async, upload, ck + 1, landing.p);
     } else {
       upload(ck, B);
     }
@@ -660,14 +650,14 @@ void GpuCtx::front_end_chunked(bool first_pass) {
     HIP_CHECK(hipMemsetAsync(B + len, 32, GAP, strm()));
     const unsigned long long nch = fe_chunks(len);
     t_begin(KT_CHAR_HIST);
-    launch_char_hist(B, len, hist, counters, wide_chars, d_chunk_segs_, strm());
+    launch_char_hist(B, len, hist, counters, wide_chars, m_->d_chunk_segs, strm());
     t_end(KT_CHAR_HIST, first_pass ? len : 0);
     t_begin(KT_SEGS);
-    launch_exclusive_scan(d_chunk_segs_, nch, d_chunk_off, scan_tmp, d_counters_ + 16, strm());
+    launch_exclusive_scan(m_->d_chunk_segs, nch, d_chunk_off, scan_tmp, &m_->ctr->chunk_scan_total, strm());
     unsigned long long n_p = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_p, d_counters_ + 16, 8, hipMemcpyDeviceToHost, strm()));
+    HIP_CHECK(hipMemcpyAsync(&n_p, &m_->ctr->chunk_scan_total, 8, hipMemcpyDeviceToHost, strm()));
     sync();
-    d_seg = dmalloc<unsigned long long>(std::max<unsigned long long>(n_p, 1));
+    d_seg.alloc(std::max<unsigned long long>(n_p, 1));
     launch_seg_write(B, len, d_seg, d_chunk_off, strm());
     t_end(KT_SEGS, len + 8 * n_p);
     segs_total += n_p;
@@ -678,13 +668,11 @@ void GpuCtx::front_end_chunked(bool first_pass) {
       if (2 * (n_unique_host + cnt) > cap) {
         unsigned long long ncap = cap;
         while (2 * (n_unique_host + cnt) > ncap / 2) ncap <<= 1;  // (a quarter full at most after this launch: growth is rare)
-        nht = dmalloc<unsigned long long>(3 * ncap);
+        PoolBuf<unsigned long long> nht(3 * ncap);
         launch_word_table_clear(nht, ncap, strm());
         launch_word_table_rehash(B, extent, d_map, ht, cap, nht, ncap, strm());
         sync();
-        DFREE(ht);
-        ht = nht;
-        nht = nullptr;
+        ht = std::move(nht);  // (the old table goes back to the pool here)
         cap = ncap;
         word_table_retries++;
       }
@@ -696,7 +684,7 @@ void GpuCtx::front_end_chunked(bool first_pass) {
       if (h_status[6]) throw GpuError{"word table overflow (chunked front end)"};
       n_unique_host = h_status[0];
     }
-    DFREE(d_seg);
+    d_seg.reset();
     // ---- the chunk's new words move to the lexicon: first how many bytes, the lexicon grown if they do not fit, then the move
     HIP_CHECK(hipMemsetAsync(d_cur + 1, 0, 8, strm()));
     launch_words_relocate(B, C, len + 1, ht, cap, d_cur + 1, /*move=*/false, strm());
@@ -706,12 +694,11 @@ void GpuCtx::front_end_chunked(bool first_pass) {
     if (lex_used_ + need > lex_cap_) {
       unsigned long long ncap = lex_cap_;
       while (lex_used_ + need > ncap) ncap <<= 1;
-      uint8_t *NB = dmalloc<uint8_t>(LEX0 + ncap + 2 * GAP);
+      PoolBuf<uint8_t> NB(LEX0 + ncap + 2 * GAP);
       HIP_CHECK(hipMemcpyAsync(NB, B, (size_t)(LEX0 + lex_used_), hipMemcpyDeviceToDevice, strm()));  // (the chunk too: its new words are still read from it)
       sync();
-      DFREE(d_text_owned_);
-      B = NB;
-      d_text_owned_ = B;
+      m_->d_text_owned = std::move(NB);
+      B = m_->d_text_owned;
       d_text_ = B;
       lex_cap_ = ncap;
     }
@@ -722,33 +709,28 @@ void GpuCtx::front_end_chunked(bool first_pass) {
   HIP_CHECK(hipMemsetAsync(B + LEX0 + lex_used_, 32, 2 * GAP, strm()));
   HIP_CHECK(hipMemcpyAsync(h_status, d_status, 32, hipMemcpyDeviceToHost, strm()));
   sync();
-  DFREE(landing);
-  DFREE(d_chunk_off);
-  DFREE(scan_tmp);
-  DFREE(d_map_spec);
-  DFREE(scratch_hist);
   n_text_ = LEX0 + lex_used_ + GAP;  // what build_word_table reads words from: offsets into B, the lexicon behind the (now idle) chunk region
   if (cfg_->trace.set)
     fprintf(stderr, "[yttm] chunked front end (%s pass): %zu chunks of <= %llu MB in %.1f ms, %llu segments, %u distinct words in %llu slots, lexicon %llu bytes\n",
             first_pass ? "first" : "second", n_chunks, C >> 20, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), segs_total,
             h_status[0], cap, lex_used_);
-  spec_.hist_done = first_pass;
-  spec_.words_done = true;
-  spec_.n_segs = segs_total;
-  spec_.ht = ht;
-  ht = nullptr;  // (handed on: no longer this scope's to free)
-  spec_.ht_cap = cap;
-  spec_.long_segments = true;  // (the table's fill is what the growth rule above made it: no second guess in build_word_table)
-  memcpy(spec_.h_status, h_status, sizeof h_status);
+  m_->spec.hist_done = first_pass;
+  m_->spec.words_done = true;
+  m_->spec.n_segs = segs_total;
+  m_->spec.ht = std::move(ht);
+  m_->spec.ht_cap = cap;
+  m_->spec.long_segments = true;  // (the table's fill is what the growth rule above made it: no second guess in build_word_table)
+  memcpy(m_->spec.h_status, h_status, sizeof h_status);
 }
 
 // multi-GPU, small word tables (host_trainer.cpp learn_bpe): every rank ends up with the WHOLE corpus -- the ranks' byte ranges in rank
 // order are the file -- and goes on alone.  Returns the ranks' summed dedup token count when called with gather = false (the decision).
 unsigned long long GpuCtx::allreduce_scalar(unsigned long long v) {
-  HIP_CHECK(hipMemcpyAsync(d_counters_ + 40, &v, 8, hipMemcpyHostToDevice, strm()));
-  comm_->allreduce_sum_u64(d_counters_ + 40, 1, strm());
+  unsigned long long *d_v = &m_->ctr->allreduce_scratch;
+  HIP_CHECK(hipMemcpyAsync(d_v, &v, 8, hipMemcpyHostToDevice, strm()));
+  comm_->allreduce_sum_u64(d_v, 1, strm());
   unsigned long long out = 0;
-  HIP_CHECK(hipMemcpyAsync(&out, d_counters_ + 40, 8, hipMemcpyDeviceToHost, strm()));
+  HIP_CHECK(hipMemcpyAsync(&out, d_v, 8, hipMemcpyDeviceToHost, strm()));
   sync();
   return out;
 }
@@ -766,31 +748,30 @@ void GpuCtx::gather_full_corpus() {
   chain_event_ = nullptr;
   const int W = comm_->world, R = comm_->rank;
   std::vector<unsigned long long> sizes((size_t)W, 0);
-  unsigned long long *d_sz = dmalloc<unsigned long long>((size_t)W);
+  PoolBuf<unsigned long long> d_sz((size_t)W);
   sizes[(size_t)R] = n_text_;
   HIP_CHECK(hipMemcpyAsync(d_sz, sizes.data(), 8 * (size_t)W, hipMemcpyHostToDevice, strm()));
   comm_->allreduce_sum_u64(d_sz, (size_t)W, strm());
   HIP_CHECK(hipMemcpyAsync(sizes.data(), d_sz, 8 * (size_t)W, hipMemcpyDeviceToHost, strm()));
   sync();
-  DFREE(d_sz);
+  d_sz.reset();
   unsigned long long maxb = 8, total = 0;
   for (unsigned long long v : sizes) { maxb = std::max(maxb, (v + 7) & ~7ull); total += v; }
-  uint8_t *d_send = dmalloc<uint8_t>(maxb), *d_recv = dmalloc<uint8_t>(maxb * (unsigned long long)W);
+  PoolBuf<uint8_t> d_send(maxb), d_recv(maxb * (unsigned long long)W);
   HIP_CHECK(hipMemsetAsync(d_send, 32, maxb, strm()));
   if (n_text_) HIP_CHECK(hipMemcpyAsync(d_send, d_text_, n_text_, hipMemcpyDeviceToDevice, strm()));
   comm_->allgather_blocks(d_send, d_recv, maxb, strm());
-  uint8_t *d_full = dmalloc<uint8_t>(total + 64);
+  PoolBuf<uint8_t> d_full(total + 64);
   unsigned long long off = 0;
   for (int r = 0; r < W; r++) {
     if (sizes[(size_t)r]) HIP_CHECK(hipMemcpyAsync(d_full + off, d_recv + maxb * (unsigned long long)r, sizes[(size_t)r], hipMemcpyDeviceToDevice, strm()));
     off += sizes[(size_t)r];
   }
   sync();
-  DFREE(d_send);
-  DFREE(d_recv);
-  DFREE(d_text_owned_);
-  d_text_owned_ = d_full;
-  d_text_ = d_full;
+  d_send.reset();
+  d_recv.reset();
+  m_->d_text_owned = std::move(d_full);
+  d_text_ = m_->d_text_owned;
   n_text_ = total;
   corpus_bytes = total;
 }
@@ -801,7 +782,7 @@ void GpuCtx::attach_corpus(const void *dev, unsigned long long n) {
   HIP_CHECK(hipSetDevice(device_));
   tl_stream = strm();
   tl_device = device_;
-  DFREE(d_text_owned_);
+  m_->d_text_owned.reset();
   if (((uintptr_t)dev & 15u) != 0) throw GpuError{"attach_corpus: device pointer must be 16-byte aligned"};
   d_text_ = (const uint8_t *)dev;
   n_text_ = n;

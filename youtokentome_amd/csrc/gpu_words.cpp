@@ -5,8 +5,8 @@
 namespace yttm {
 
 void GpuCtx::free_words() {
-  DFREE(d_wmeta_); DFREE(d_gather_); DFREE(d_xyz_); DFREE(d_wworklist_); DFREE(d_drec_); DFREE(d_drec_n_); DFREE(d_irec_);
-  DFREE(tl_.base); DFREE(tl_.cap); DFREE(tl_.fill); DFREE(tl_.rec_word); DFREE(tl_.rec_l); DFREE(tl_.rec_r); DFREE(tl_.cursor);
+  m_->d_wmeta.reset(); m_->d_gather.reset(); m_->d_xyz.reset(); m_->d_wworklist.reset(); m_->d_drec.reset(); m_->d_drec_n.reset(); m_->d_irec.reset();
+  m_->tl = {};
   tl_ = TokLists{};
   word_mode_ = false;
   word_global_ = false;
@@ -18,35 +18,38 @@ void GpuCtx::free_words() {
 // The switch to word mode (k_words.hip): from here on class-A words live in the slots they have now and a round visits the words
 // that hold a merge site.  Called between rounds.
 void GpuCtx::enter_word_mode(uint32_t z_next) {
-  WordClass &c = cls_[0];
+  WordClass &c = m_->cls[0];
   chain_event_ = nullptr;
-  d_wmeta_ = dmalloc<unsigned long long>(c.n_unique + 1);
-  launch_words_init(c.ts, d_wmeta_, strm());
-  d_wworklist_ = dmalloc<uint32_t>(c.n_unique + 64);
+  m_->d_wmeta.alloc(c.n_unique + 1);
+  launch_words_init(c.ts, m_->d_wmeta, strm());
+  m_->d_wworklist.alloc(c.n_unique + 64);
   HIP_CHECK(hipMemsetAsync(c.d_work_n, 0, 64, strm()));
-  d_gather_ = dmalloc<GatherCtl>(1);
-  HIP_CHECK(hipMemsetAsync(d_gather_, 0, sizeof(GatherCtl), strm()));
-  d_xyz_ = dmalloc<uint32_t>(3 * (size_t)RULES_CAP);
+  m_->d_gather.alloc(1);
+  HIP_CHECK(hipMemsetAsync(m_->d_gather, 0, sizeof(GatherCtl), strm()));
+  m_->d_xyz.alloc(3 * (size_t)RULES_CAP);
   drec_cap_ = (unsigned int)cfg_->word_drec.u;  // (tests: a region that overflows)
-  d_drec_ = dmalloc<DeltaRec>((size_t)WORDS_MAX_GRID * drec_cap_);
-  d_drec_n_ = dmalloc<unsigned int>(WORDS_MAX_GRID);
-  d_irec_ = dmalloc<uint4>((size_t)WORDS_MAX_GRID * drec_cap_);
-  tl_.base = dmalloc<unsigned long long>(id_cap_);
-  tl_.cap = dmalloc<uint32_t>(id_cap_);
-  tl_.fill = dmalloc<uint32_t>(id_cap_);
-  HIP_CHECK(hipMemsetAsync(tl_.base, 0, (size_t)id_cap_ * 8, strm()));
-  HIP_CHECK(hipMemsetAsync(tl_.cap, 0, (size_t)id_cap_ * 4, strm()));
-  HIP_CHECK(hipMemsetAsync(tl_.fill, 0, (size_t)id_cap_ * 4, strm()));
-  tl_.cursor = dmalloc<unsigned long long>(2);
-  HIP_CHECK(hipMemsetAsync(tl_.cursor, 0, 16, strm()));
+  m_->d_drec.alloc((size_t)WORDS_MAX_GRID * drec_cap_);
+  m_->d_drec_n.alloc(WORDS_MAX_GRID);
+  m_->d_irec.alloc((size_t)WORDS_MAX_GRID * drec_cap_);
+  auto &t = m_->tl;  // (tl_ is the view of it that the kernels get)
+  t.base.alloc(id_cap_);
+  t.cap.alloc(id_cap_);
+  t.fill.alloc(id_cap_);
+  HIP_CHECK(hipMemsetAsync(t.base, 0, (size_t)id_cap_ * 8, strm()));
+  HIP_CHECK(hipMemsetAsync(t.cap, 0, (size_t)id_cap_ * 4, strm()));
+  HIP_CHECK(hipMemsetAsync(t.fill, 0, (size_t)id_cap_ * 4, strm()));
+  t.cursor.alloc(2);
+  HIP_CHECK(hipMemsetAsync(t.cursor, 0, 16, strm()));
   // every record ever matched is a site at most once through each of its two neighbours, and a site removes a token: a few records per
   // live token bound the log between two index builds; should it fill up all the same, the round says so and the index is rebuilt
   const unsigned long long live = std::max<unsigned long long>(live_tokens_last_, 1ull << 16);
   const unsigned long long log_env = cfg_->word_log.u;  // (tests: a log that overflows)
   tl_.log_cap = log_env ? log_env : 2 * live + (1ull << 20);
-  tl_.rec_word = dmalloc<uint32_t>(tl_.log_cap);
-  tl_.rec_l = dmalloc<uint32_t>(tl_.log_cap);
-  tl_.rec_r = dmalloc<uint32_t>(tl_.log_cap);
+  t.rec_word.alloc(tl_.log_cap);
+  t.rec_l.alloc(tl_.log_cap);
+  t.rec_r.alloc(tl_.log_cap);
+  tl_.base = t.base; tl_.cap = t.cap; tl_.fill = t.fill; tl_.cursor = t.cursor;
+  tl_.rec_word = t.rec_word; tl_.rec_l = t.rec_l; tl_.rec_r = t.rec_r;
   tl_.broken = &h_pin_->broken;  // (the kernels write it with system-scope stores)
   *(volatile unsigned int *)tl_.broken = 0;
   word_mode_ = true;
@@ -61,37 +64,35 @@ void GpuCtx::enter_word_mode(uint32_t z_next) {
   build_index(z_next);
 }
 
-void GpuCtx::free_index() {
-  DFREE(idx_.key); DFREE(idx_.cnt); DFREE(idx_.off); DFREE(idx_.bloom); DFREE(idx_.post); DFREE(d_stamp_); DFREE(idx_scan_tmp_); DFREE(idx_save_);
-  idx_cap_ = post_cap_ = 0;
-  stamp_cap_ = 0;
-  idx_valid_ = false;
-}
-
 // (Re)builds the pair index of word mode from the hot list as it is now and the class-A words as they are now (see k_index_core.h PairIndex).
 // Called between rounds.
 void GpuCtx::build_index(uint32_t z_next) {
   idx_pending_ = false;
   idx_valid_ = false;
-  WordClass &c = cls_[0];
+  WordClass &c = m_->cls[0];
   if (!c.n_tiles || hot_state_ != HOT_ACTIVE || !word_mode_) return;
   chain_event_ = nullptr;
   unsigned int listed = 0;  // (the list has grown since the scan that last reported its length)
-  HIP_CHECK(hipMemcpyAsync(&listed, &d_hot_ctl_->n, 4, hipMemcpyDeviceToHost, strm()));
+  HIP_CHECK(hipMemcpyAsync(&listed, &m_->d_hot_ctl->n, 4, hipMemcpyDeviceToHost, strm()));
   sync();
   if (listed > hot_cap_) return;  // overflowed: the next scan rebuilds the list, and the index after it
   unsigned long long want = 1024;
   while (want < 2ull * ((unsigned long long)listed + 256)) want <<= 1;
   if (want > idx_cap_) {
-    DFREE(idx_.key); DFREE(idx_.cnt); DFREE(idx_.off);
-    idx_.key = dmalloc<unsigned long long>(want);
-    idx_.cnt = dmalloc<uint32_t>(want * IDX_SHARDS + 1);
-    idx_.off = dmalloc<unsigned long long>(want * IDX_SHARDS + 2);
-    DFREE(idx_scan_tmp_);
-    idx_scan_tmp_ = dmalloc<unsigned long long>(scan_scratch_blocks(want * IDX_SHARDS + 1));
+    m_->idx.key.reset();  // (all three back in the pool before any is taken again: the order decides which blocks are reused)
+    m_->idx.cnt.reset();
+    m_->idx.off.reset();
+    m_->idx.key.alloc(want);
+    m_->idx.cnt.alloc(want * IDX_SHARDS + 1);
+    m_->idx.off.alloc(want * IDX_SHARDS + 2);
+    m_->idx_scan_tmp.alloc(scan_scratch_blocks(want * IDX_SHARDS + 1));
     idx_cap_ = want;
   }
-  if (!idx_.bloom) idx_.bloom = dmalloc<uint32_t>(ENC_BLOOM_WORDS);
+  if (!m_->idx.bloom) m_->idx.bloom.alloc(ENC_BLOOM_WORDS);
+  idx_.key = m_->idx.key;
+  idx_.cnt = m_->idx.cnt;
+  idx_.off = m_->idx.off;
+  idx_.bloom = m_->idx.bloom;
   idx_.mask = (unsigned int)(want - 1);
   launch_fill_u64(idx_.key, PT_EMPTY, want, strm());
   HIP_CHECK(hipMemsetAsync(idx_.cnt, 0, want * IDX_SHARDS * 4, strm()));
@@ -102,27 +103,25 @@ void GpuCtx::build_index(uint32_t z_next) {
   const unsigned long long slots_n = (unsigned long long)c.n_tiles * c.slot;
   const bool radix = word_live_tokens_ >= idx_radix_min_ && idx_radix_takes(idx_.mask, c.n_tiles) &&
                      12ull * slots_n + 4ull * idx_radix_scratch_u32() + (64ull << 20) <= free_device_bytes() / 4 * 3;
-  DevScope scope;  // (a thrown GpuError leaks none of the build's transient buffers)
-  uint32_t *rx_scratch = nullptr, *rx_slots = nullptr;
-  unsigned long long *rx_rec = nullptr;
-  scope.hold(rx_scratch); scope.hold(rx_slots); scope.hold(rx_rec);
+  PoolBuf<uint32_t> rx_scratch, rx_slots;
+  PoolBuf<unsigned long long> rx_rec;
   t_begin(KT_CAND);
   launch_idx_seed(pt_, idx_, listed, strm());
   unsigned long long total = 0;
   if (radix) {
-    rx_scratch = dmalloc<uint32_t>(idx_radix_scratch_u32());
-    rx_slots = dmalloc<uint32_t>(slots_n);
+    rx_scratch.alloc(idx_radix_scratch_u32());
+    rx_slots.alloc(slots_n);
     HIP_CHECK(hipMemsetAsync(rx_scratch, 0, idx_radix_scratch_head_bytes(), strm()));
     launch_idx_radix_sweep(c.ts, idx_, rx_scratch, rx_slots, strm());
     HIP_CHECK(hipMemcpyAsync(&total, rx_scratch, 8, hipMemcpyDeviceToHost, strm()));
   } else {
-    if (!idx_save_) idx_save_ = dmalloc<unsigned char>(idx_save_bytes());
-    launch_idx_stream(false, c.ts, idx_, strm(), true, idx_save_);
+    if (!m_->idx_save) m_->idx_save.alloc(idx_save_bytes());
+    launch_idx_stream(false, c.ts, idx_, strm(), true, m_->idx_save);
     // offsets = exclusive scan of the counts (one extra zero count behind the last slot: off[mask + 1] = the total)
     HIP_CHECK(hipMemsetAsync(idx_.cnt + want * IDX_SHARDS, 0, 4, strm()));
-    launch_exclusive_scan(idx_.cnt, want * IDX_SHARDS + 1, idx_.off, idx_scan_tmp_, d_counters_ + 56, strm());
+    launch_exclusive_scan(idx_.cnt, want * IDX_SHARDS + 1, idx_.off, m_->idx_scan_tmp, &m_->ctr->index_scan_total, strm());
     HIP_CHECK(hipMemsetAsync(idx_.cnt, 0, want * IDX_SHARDS * 4, strm()));  // the fill pass's cursors
-    HIP_CHECK(hipMemcpyAsync(&total, d_counters_ + 56, 8, hipMemcpyDeviceToHost, strm()));
+    HIP_CHECK(hipMemcpyAsync(&total, &m_->ctr->index_scan_total, 8, hipMemcpyDeviceToHost, strm()));
   }
   sync();
   index_builds++;
@@ -132,30 +131,29 @@ void GpuCtx::build_index(uint32_t z_next) {
     return;
   }
   if (total > post_cap_) {
-    DFREE(idx_.post);
     post_cap_ = total + total / 4 + 1024;
-    idx_.post = dmalloc<uint32_t>(post_cap_);
+    m_->idx.post.alloc(post_cap_);
+    idx_.post = m_->idx.post;
   }
   if (radix) {
-    rx_rec = dmalloc<unsigned long long>(total);
+    rx_rec.alloc(total);
     launch_idx_radix_scatter(c.ts, idx_, rx_scratch, rx_slots, rx_rec, total, strm());
     // (all of a key's postings are counted in its shard 0: the run bounds off[s * IDX_SHARDS] come out of the same scan)
     HIP_CHECK(hipMemsetAsync(idx_.cnt + want * IDX_SHARDS, 0, 4, strm()));
-    launch_exclusive_scan(idx_.cnt, want * IDX_SHARDS + 1, idx_.off, idx_scan_tmp_, d_counters_ + 56, strm());
+    launch_exclusive_scan(idx_.cnt, want * IDX_SHARDS + 1, idx_.off, m_->idx_scan_tmp, &m_->ctr->index_scan_total, strm());
     HIP_CHECK(hipMemsetAsync(idx_.cnt, 0, want * IDX_SHARDS * 4, strm()));  // the place pass's cursors
     launch_idx_radix_place(idx_, rx_scratch, rx_rec, total, strm());
     index_radix_builds++;
   } else {
-    launch_idx_stream(true, c.ts, idx_, strm(), /*agg=*/total > idx_agg_min_, idx_save_);
+    launch_idx_stream(true, c.ts, idx_, strm(), /*agg=*/total > idx_agg_min_, m_->idx_save);
   }
   t_end(KT_CAND, 8ull * c.n_tiles * c.nom);
   const unsigned long long stamps = c.n_unique;  // (a posting is a word, and a round claims words)
   if (stamps > stamp_cap_) {
-    DFREE(d_stamp_);
     stamp_cap_ = (unsigned int)(stamps + stamps / 8 + 64);
-    d_stamp_ = dmalloc<uint32_t>(stamp_cap_);
+    m_->d_stamp.alloc(stamp_cap_);
   }
-  HIP_CHECK(hipMemsetAsync(d_stamp_, 0, (size_t)stamp_cap_ * 4, strm()));
+  HIP_CHECK(hipMemsetAsync(m_->d_stamp, 0, (size_t)stamp_cap_ * 4, strm()));
   {  // every token that exists now is covered by the postings: the instance lists start over
     HIP_CHECK(hipMemsetAsync(tl_.cursor, 0, 16, strm()));
     sync();

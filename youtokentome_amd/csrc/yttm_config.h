@@ -44,6 +44,7 @@ struct Hook {
   X(io_chunk_kb, "YTTM_IO_CHUNK_KB", "0", "test", "the same in KB (tests: many chunks of a small input)")                                  \
   X(io_threads, "YTTM_IO_THREADS", "0", "tune", "upload / download workers (0: by size, at most 8)")                                       \
   X(test_free_bytes, "YTTM_TEST_FREE_BYTES", "0", "test", "pretend this many bytes of HBM are free (replication's memory check)")         \
+  X(test_alloc_fail, "YTTM_TEST_ALLOC_FAIL", "0", "test", "the N-th allocation from the device-memory pool after a trainer context is made fails (0: none)") \
   /* ---- front end */                                                                                                                       \
   X(k1_wide, "YTTM_K1_WIDE", "0", "path", "force K1's variant: 1 = wide chars counted in an LDS hash, 0 = global atomics")                 \
   X(fe_overlap_min, "YTTM_FE_OVERLAP_MIN", "33554432", "tune", "texts of at least this many bytes run K1/K2a/K2b under the upload")       \
