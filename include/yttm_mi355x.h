@@ -236,6 +236,36 @@ int yttm_id_counts_copy_device(yttm_encoder *enc, void *d_counts, uint64_t n_bin
 int yttm_encode_file_counts(yttm_encoder *enc, const char *path, int bos, int eos, int reverse, double dropout_prob, uint64_t chunk_bytes,
                             uint64_t *counts, uint64_t *n_lines, uint64_t *n_ids, char *report_json, int report_len, char *err, int errlen);
 
+/* Encode under a restricted vocabulary (subword-nmt's --vocabulary / --vocabulary-threshold, SentencePiece's SetVocabulary; the reference has no
+ * counterpart).  A model has rules (x, y, z) with distinct z, as written in the model file behind the char section.  Let V = yttm_vocab_size(enc)
+ * and A, a subset of [0, V), the allowed set.  The expansion E(v) of an id:
+ *   E(v) = [v]            if v is outside [0, V) -- no id is an error, as in the id counts;
+ *   E(v) = [v]            if v is in A;
+ *   E(v) = [v]            if v is no rule's z: chars, <PAD>, <UNK>, <BOS>, <EOS> -- a leaf stays even when it is not allowed, as in subword-nmt;
+ *   E(v) = E(x) ++ E(y)   otherwise, for the one rule with z == v.
+ * A sentence's restricted ids are the concatenation of E(id) over its ids in forward order; of a sentence that is stored back to front
+ * (reverse) the restricted result is the reverse of that: each stored id is replaced by E(id) reversed.  So: decoding the restricted ids gives
+ * the bytes that decoding the originals gives; the units the tokens cover (the spans' rule above) sum to the same value, so spans and SUBWORD
+ * text stay well defined; restricting twice equals restricting once; A = [0, V) is the identity.  Every expansion is made without regard to
+ * its neighbours: this is NOT the encoding a model trained with fewer merges would give (such a model could merge the pieces differently).
+ *
+ * yttm_encoder_set_vocabulary: allowed[n], n == V (else code 1), non-zero = allowed; allowed == NULL clears the vocabulary (n is not looked at).
+ * It builds exp_off[V + 1] and exp_ids[] in rule order, and the same with every expansion reversed, in HBM.  From then on EVERY encode of this
+ * encoder -- ids, tensors, padded matrices, SUBWORD text, id text, spans, counts, files, the command line -- gives restricted ids: a pass
+ * (k_restrict.h: measure, scan, write) runs behind the encode kernel; n_ids and kernel_ms of those calls include it.  Off unless asked for:
+ * with no vocabulary set nothing changes.  The call waits for both of the encoder's lanes; a result already pending is not changed.  info
+ * (optional): {allowed ids, ids whose expansion is longer than one id, the longest expansion}.
+ * yttm_encoder_vocabulary_stats: {restricted calls, calls where nothing split, ids in, ids out} since the encoder was made. */
+int yttm_encoder_set_vocabulary(yttm_encoder *enc, const uint8_t *allowed, uint64_t n, uint64_t *info, char *err, int errlen);
+int yttm_encoder_vocabulary_stats(yttm_encoder *enc, uint64_t out[4]);
+/* The pass over ids the encoder did not make: int32 d_ids[n_ids] + uint64 d_offsets[n_sent + 1] in HBM (offsets[0] = 0, the conventions of
+ * yttm_decode_device: 4-byte aligned ids, the caller synchronises the stream that wrote them first).  reverse: the sentences are stored back to
+ * front.  It leaves a pending encode result of n_sent sentences and *n_out ids, exactly as after yttm_encode_device (yttm_encode_fetch,
+ * yttm_encode_copy_device, yttm_encode_copy_padded, yttm_idtext_device, yttm_id_counts_device); the spans slot is emptied.  No vocabulary set:
+ * code 1, and nothing pending is replaced.  kernel_ms (optional) = measure + scan + write. */
+int yttm_restrict_ids_device(yttm_encoder *enc, const void *d_ids, const void *d_offsets, uint64_t n_sent, uint64_t n_ids, int reverse,
+                             uint64_t *n_out, double *kernel_ms, char *err, int errlen);
+
 /* Word-level encode cache (SURVEY.md 8f "N4"; the reference has no counterpart: bpe.cpp:1497-1632 encodes every word occurrence).
  * mode 0: every batch goes straight through the encode kernel; 1: distinct words are encoded once whenever that is possible
  * (dropout_prob == 0); 2 (default): the same for batches of at least min_bytes.  The ids are identical either way.

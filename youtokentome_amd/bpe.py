@@ -107,6 +107,36 @@ class _Core:
     def cache_words(self):
         return int(_lib.load().yttm_encode_cache_words(self._h))
 
+    # ---- encode under a restricted vocabulary (include/yttm_mi355x.h): a mask of allowed ids; tokens outside it are split back into smaller pieces
+    def set_vocabulary(self, allowed=None):
+        """allowed: a sequence of vocab_size() truth values, or None to clear the vocabulary -> (allowed ids, ids that split, longest expansion)"""
+        info, err = (C.c_uint64 * 3)(), _err()
+        if allowed is None:
+            self._check(_lib.load().yttm_encoder_set_vocabulary(self._h, None, 0, info, err, _lib.ERRLEN), err)
+        else:
+            mask = np.ascontiguousarray(np.asarray(allowed) != 0, dtype=np.uint8)
+            if mask.ndim != 1:
+                raise ValueError("allowed must be one-dimensional")
+            self._check(_lib.load().yttm_encoder_set_vocabulary(self._h, mask.ctypes.data_as(_lib.u8p), len(mask), info, err, _lib.ERRLEN), err)
+        self._vocabulary_info = tuple(int(v) for v in info)
+        return self._vocabulary_info
+
+    def vocabulary_info(self):
+        return getattr(self, "_vocabulary_info", (0, 0, 0))
+
+    def vocabulary_stats(self):
+        """-> (restricted calls, calls where nothing split, ids in, ids out)"""
+        out = (C.c_uint64 * 4)()
+        _lib.load().yttm_encoder_vocabulary_stats(self._h, out)
+        return tuple(int(v) for v in out)
+
+    def restrict_ids_device_raw(self, d_ids, d_offsets, n_sent, n_ids, reverse=False):
+        """-> (n_out, kernel_ms); the restricted ids are pending as after encode_device_raw"""
+        n, ms, err = C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_restrict_ids_device(self._h, C.c_void_p(d_ids), C.c_void_p(d_offsets), n_sent, n_ids, int(bool(reverse)), C.byref(n),
+                                                         C.byref(ms), err, _lib.ERRLEN), err)
+        return n.value, ms.value
+
     # ---- packed fast path (SURVEY.md N2): bytes + offsets -> numpy ids + offsets
     def encode_packed(self, blob: bytes, offsets, bos=False, eos=False, reverse=False, dropout_prob=0.0):
         L = _lib.load()
@@ -660,6 +690,43 @@ class BPE:
         piece: only the counts come down.  The last entry counts ids outside the vocabulary (0 for an encode).  report=True: (counts, the call's
         report as a dict).  Needs no torch."""
         return self.bpe_cython.encode_file_counts(path, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, chunk_bytes=chunk_bytes, report=report)
+
+    # ---- encode with only the tokens a corpus uses often enough (include/yttm_mi355x.h "Encode under a restricted vocabulary")
+    def set_vocabulary(self, allowed=None, counts=None, threshold: int = 1):
+        """Restricts every later encode of this object to the allowed ids: a token outside them is split back into the two pieces it was merged
+        from, and those again, down to allowed tokens or single chars (subword-nmt's --vocabulary / --vocabulary-threshold).  `allowed`: a bool
+        mask [vocab_size]; or `counts`: what count_file / id_counts_tensor return (its last entry, the ids outside the vocabulary, is dropped),
+        allowed = counts >= threshold.  Neither: the vocabulary is cleared.  Returns vocabulary_info()."""
+        if allowed is not None and counts is not None:
+            raise ValueError("pass allowed or counts, not both")
+        if counts is not None:
+            if hasattr(counts, "cpu"):
+                counts = counts.cpu().numpy()
+            counts = np.asarray(counts).ravel()
+            V = self.vocab_size()
+            if len(counts) not in (V, V + 1):
+                raise ValueError("counts must have vocab_size or vocab_size + 1 entries, not %d" % len(counts))
+            allowed = counts[:V].astype(np.uint64) >= int(threshold)
+        elif allowed is not None:
+            if hasattr(allowed, "cpu"):
+                allowed = allowed.cpu().numpy()
+            allowed = np.asarray(allowed).ravel()
+        return self.bpe_cython.set_vocabulary(allowed)
+
+    def vocabulary_info(self):
+        """(allowed ids, ids that split, the longest expansion) of the vocabulary that is set; zeros when none is"""
+        return self.bpe_cython.vocabulary_info()
+
+    def vocabulary_stats(self):
+        """(restricted calls, calls where nothing split, ids in, ids out) since this object was made"""
+        return self.bpe_cython.vocabulary_stats()
+
+    def restrict_tensor(self, ids, lengths=None, offsets=None, reverse: bool = False, padded: Optional[bool] = None, width: Optional[int] = None,
+                        pad_id: Optional[int] = None):
+        """Restricts ids this object did not encode under the vocabulary that is set: `ids`, `lengths`, `offsets` as decode_tensor takes them (a
+        2-D padded matrix with lengths, or 1-D ids with offsets [n + 1]) -> what encode_tensor returns; padded=None gives the input's form back."""
+        from . import tensor
+        return tensor.restrict_tensor(self, ids, lengths=lengths, offsets=offsets, reverse=reverse, padded=padded, width=width, pad_id=pad_id)
 
     # ---- decimal id text, one sentence per line: the format `yttm encode --output_type id` prints and `yttm decode` reads
     def decode_file(self, path, out: str, ignore_ids: Optional[Collection] = None, chunk_bytes: Optional[int] = None, report: bool = False):

@@ -378,6 +378,26 @@ int yttm_encode_file_counts(yttm_encoder *h, const char *path, int bos, int eos,
   return finish(s, err, errlen);
 }
 
+int yttm_encoder_set_vocabulary(yttm_encoder *h, const uint8_t *allowed, uint64_t n, uint64_t *info, char *err, int errlen) {
+  unsigned long long i3[3] = {0, 0, 0};
+  Status s = h->enc->set_vocabulary(allowed, n, i3);
+  if (info) for (int i = 0; i < 3; i++) info[i] = i3[i];
+  return finish(s, err, errlen);
+}
+int yttm_encoder_vocabulary_stats(yttm_encoder *h, uint64_t out[4]) {
+  unsigned long long o4[4] = {0, 0, 0, 0};
+  h->enc->vocabulary_stats(o4);
+  for (int i = 0; i < 4; i++) out[i] = o4[i];
+  return 0;
+}
+int yttm_restrict_ids_device(yttm_encoder *h, const void *d_ids, const void *d_offsets, uint64_t n_sent, uint64_t n_ids, int reverse, uint64_t *n_out,
+                             double *kernel_ms, char *err, int errlen) {
+  unsigned long long no = 0;
+  Status s = h->enc->restrict_ids_device(d_ids, d_offsets, n_sent, n_ids, reverse != 0, &no, kernel_ms);
+  if (n_out) *n_out = no;
+  return finish(s, err, errlen);
+}
+
 int yttm_encoder_set_cache(yttm_encoder *h, int mode, uint64_t min_bytes) {
   h->enc->set_cache(mode, min_bytes);
   return 0;

@@ -62,6 +62,11 @@ struct EncodeLane {
     unsigned long long n_ids = 0, n_sent = 0;
     bool made = false;  // an encode or a parse has left a result here (n_sent == 0 is a result too)
   } res;
+  struct {  // the vocabulary restriction (k_restrict.h): the second pair of buffers its pass writes, swapped with res's; the lengths it measures
+    DevBuf<int32_t> ids;
+    DevBuf<unsigned long long> off;
+    DevBuf<uint32_t> len;
+  } rs;
   struct {  // word cache (k_wcache.hip): the batch's table of distinct words, the slot of every occurrence, the list K5 encodes, its ids
     DevBuf<unsigned long long> slot, pos, extra, blk_off, ustart, uend;
     DevBuf<uint32_t> occ, blk, uslot, ucounts;
@@ -137,6 +142,16 @@ struct EncoderDevice {
     unsigned long long n_bins = 0;
     bool valid = false;
   } idc;
+  // the restricted vocabulary (host_encoder.cpp set_vocabulary, k_restrict.h): exp_ids[exp_off[v] .. exp_off[v + 1]) = E(v), and the same with every
+  // expansion back to front.  Written with every lane locked, read by a call that holds its lane: a call never sees half a table.
+  struct {
+    bool set = false;
+    DevBuf<uint32_t> exp_off;
+    DevBuf<int32_t> exp_fwd, exp_rev;
+    uint32_t vocab = 0;
+    unsigned long long info[3] = {0, 0, 0};               // allowed ids, ids that split, the longest expansion
+    std::atomic<unsigned long long> stats[4] = {{0}, {0}, {0}, {0}};  // restricted calls, calls where nothing split, ids in, ids out
+  } voc;
   // a free lane, locked (falls back to waiting for the caller's turn-based choice)
   // (Lane 0 last: the device-resident pair encode_device / fetch_device_result keeps its result there, unlocked, between the two
   // calls -- a host-to-host encode from another thread in between takes another lane while one is free.)
@@ -251,6 +266,13 @@ Status idtext_on_lane(EncodeLane &d, int device, unsigned long long *n_text_byte
 // (k_idcount.h).  n_bins: 1 .. 2^31.  accumulate on a slot of another n_bins: code 1 before anything is changed; on an empty slot it starts from 0.
 Status count_on_lane(EncoderDevice &D, EncodeLane &d, int device, const int32_t *d_ids, unsigned long long n_ids, unsigned long long n_bins, bool accumulate,
                      double *kernel_ms);
+
+// The vocabulary restriction of ids[n_ids] / off[n_sent + 1] in HBM on the lane (locked by the caller; a vocabulary is set): measure -> scan ->
+// write (k_restrict.h) into the lane's second pair of buffers, which then becomes the lane's encode result.  pending: the input IS that result
+// (d.res); where nothing splits the write pass is skipped and the result stays where it is.  Otherwise the input is the caller's and the result
+// is installed as after an encode of n_sent sentences.  *n_out: the ids of the result.
+Status restrict_on_lane(EncoderDevice &D, EncodeLane &d, int device, const int32_t *ids, const unsigned long long *off, unsigned long long n_sent,
+                        unsigned long long n_ids, bool reverse, bool pending, unsigned long long *n_out, double *kernel_ms);
 
 // The two-pass sequence of a kernel family that measures, then writes (k_decode.h, k_subword.h, k_idtext.h), on the lane (locked by the caller,
 // on its device): launch(false) leaves n counts, scan_counts turns them into off[n + 1] and synchronises, check() may end the call there with

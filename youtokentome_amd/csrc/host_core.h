@@ -186,6 +186,14 @@ class BaseEncoder {  // bpe.h:22-82
   Status take_id_counts(void *counts, unsigned long long n_bins, bool to_device) const;  // [n_bins + 1]: to a host array or device to device
   Status encode_file_counts(const std::string &path, bool bos, bool eos, bool reverse, double dropout_prob, unsigned long long piece_bytes,
                             unsigned long long *counts, unsigned long long *n_lines, unsigned long long *n_ids, std::string *report) const;
+  // Encode under a restricted vocabulary (host_encoder.cpp, k_restrict.h; the rule is in include/yttm_mi355x.h): allowed[vocab_size()] (null:
+  // clears it) -> the expansion tables in HBM; from then on every encode on this encoder leaves restricted ids.  info (optional): allowed ids,
+  // ids that split, the longest expansion.  vocabulary_stats: restricted calls, calls where nothing split, ids in, ids out.
+  // restrict_ids_device: the pass over ids + offsets in HBM that the encoder did not make; the result is pending as after encode_device.
+  Status set_vocabulary(const uint8_t *allowed, unsigned long long n, unsigned long long *info) const;
+  void vocabulary_stats(unsigned long long out[4]) const;
+  Status restrict_ids_device(const void *d_ids, const void *d_offsets, unsigned long long n_sent, unsigned long long n_ids, bool reverse,
+                             unsigned long long *n_out, double *kernel_ms) const;
   // the YTTM_* hooks as they stood when THIS encoder was made: every entry point binds them to its thread (yttm_config.h CfgBind), so that a
   // later encoder or training never changes the paths of this one
   std::shared_ptr<const Config> config() const;

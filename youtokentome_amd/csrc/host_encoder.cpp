@@ -272,6 +272,144 @@ Status check_bos_eos(const BaseEncoder &enc, bool bos, bool eos) {
   return Status();
 }
 
+// ---- the restricted vocabulary (k_restrict.h; the rule is in include/yttm_mi355x.h) ---------------------------------------------------------
+Status restrict_on_lane(EncoderDevice &D, EncodeLane &d, int device, const int32_t *ids, const unsigned long long *off, unsigned long long n_sent,
+                        unsigned long long n_ids, bool reverse, bool pending, unsigned long long *n_out, double *kernel_ms) {
+  return on_device(device, [&]() -> Status {
+    if (kernel_ms) *kernel_ms = 0;
+    if (n_out) *n_out = 0;
+    unsigned long long total = 0;
+    bool skip = false;
+    if (n_sent) {
+      const RestrictTable tb{D.voc.exp_off, reverse ? D.voc.exp_rev : D.voc.exp_fwd, D.voc.vocab};
+      const Status s = two_pass_on_lane(
+          d, n_sent, d.rs.len, d.rs.off, kernel_ms, &total,
+          [&](bool write) {
+            if (write && skip) return;
+            launch_restrict(write, ids, off, n_sent, n_ids, tb, d.rs.len, d.rs.off, d.rs.ids, d.st);
+          },
+          [] { return Status(); },
+          [&](unsigned long long need) {
+            skip = pending && need == n_ids;  // (every expansion has an id, and one of a single id is that id: nothing splits)
+            if (skip) return;
+            d.rs.ids.grow((size_t)need + 4);
+            if (((uintptr_t)d.rs.ids.p & 15u) != 0) throw GpuError{"restrict: the output is not 16-byte aligned"};
+          });
+      if (!s.ok()) return s;
+      if (!skip) {
+        std::swap(d.res.ids, d.rs.ids);
+        std::swap(d.res.off, d.rs.off);
+      }
+    }
+    if (!pending) {
+      d.res.n_sent = n_sent;
+      d.res.made = true;
+      d.sp.valid = false;  // (spans belong to the ids they were made from)
+    }
+    d.res.n_ids = total;
+    if (n_out) *n_out = total;
+    D.voc.stats[0] += 1;
+    if (total == n_ids) D.voc.stats[1] += 1;
+    D.voc.stats[2] += n_ids;
+    D.voc.stats[3] += total;
+    return Status();
+  });
+}
+
+// The tail of encode_on_lane: with a vocabulary set, the pass over the ids the encode has just left on the lane.
+static Status restrict_tail(EncoderDevice &D, EncodeLane &d, int device, bool reverse, unsigned long long *n_ids_out, double *kernel_ms) {
+  if (!D.voc.set) return Status();
+  double ms = 0;
+  unsigned long long n = 0;
+  const Status s = restrict_on_lane(D, d, device, d.res.ids, d.res.off, d.res.n_sent, d.res.n_ids, reverse, true, &n, kernel_ms ? &ms : nullptr);
+  if (!s.ok()) return s;
+  if (n_ids_out) *n_ids_out = n;
+  if (kernel_ms) *kernel_ms += ms;
+  return Status();
+}
+
+Status BaseEncoder::set_vocabulary(const uint8_t *allowed, unsigned long long n, unsigned long long *info) const {
+  if (info) info[0] = info[1] = info[2] = 0;
+  if (!dev_) return Status(2, "encoder has no device state");
+  const size_t V = (size_t)vocab_size();
+  if (allowed && n != V)
+    return Status(1, "set_vocabulary: n must be the vocabulary's size. Current value: vocab_size = " + std::to_string(V) + "; n = " + std::to_string(n) + ";");
+  EncoderDevice &D = *dev_;
+  const CfgBind bind(D.cfg);
+  std::lock_guard<std::mutex> lk0(D.lane[0].mu), lk1(D.lane[1].mu);  // (always in this order; a result already pending stays as it is)
+  if (!allowed) {
+    D.voc.set = false;
+    D.voc.info[0] = D.voc.info[1] = D.voc.info[2] = 0;
+    return Status();
+  }
+  // E(v) in rule order: x and y are made before z (a char, or an earlier rule's z), so no recursion is needed
+  std::vector<std::vector<int32_t>> E(V);
+  for (size_t v = 0; v < V; v++) E[v].assign(1, (int32_t)v);
+  unsigned long long n_allowed = 0, n_split = 0, longest = 1, total = V;
+  for (size_t v = 0; v < V; v++) n_allowed += allowed[v] ? 1 : 0;
+  for (const BPE_Rule &r : bpe_state.rules) {
+    if (r.z >= V || r.x >= V || r.y >= V) return Status(2, "set_vocabulary: a rule names an id outside the vocabulary");
+    if (allowed[r.z]) continue;
+    std::vector<int32_t> e = E[r.x];
+    e.insert(e.end(), E[r.y].begin(), E[r.y].end());
+    total += e.size() - E[r.z].size();
+    if (total >= 0xfffffff0ull) return Status(2, "set_vocabulary: the expansions do not fit 2^32 ids");
+    E[r.z] = std::move(e);
+  }
+  std::vector<uint32_t> exp_off(V + 1, 0);
+  std::vector<int32_t> fwd, rev;
+  fwd.reserve((size_t)total);
+  rev.reserve((size_t)total);
+  for (size_t v = 0; v < V; v++) {
+    exp_off[v] = (uint32_t)fwd.size();
+    fwd.insert(fwd.end(), E[v].begin(), E[v].end());
+    rev.insert(rev.end(), E[v].rbegin(), E[v].rend());
+    if (E[v].size() > 1) n_split++;
+    longest = std::max<unsigned long long>(longest, E[v].size());
+  }
+  exp_off[V] = (uint32_t)fwd.size();
+  const Status s = on_device(device_, [&]() -> Status {
+    // all three are allocated and filled, then handed to the encoder together: a failure on the way leaves the vocabulary as it was
+    DevBuf<uint32_t> d_off;
+    DevBuf<int32_t> d_fwd, d_rev;
+    d_off.alloc(exp_off.size());
+    d_fwd.alloc(fwd.size());
+    d_rev.alloc(rev.size());
+    HIP_CHECK(hipMemcpy(d_off, exp_off.data(), exp_off.size() * 4, hipMemcpyHostToDevice));
+    if (!fwd.empty()) HIP_CHECK(hipMemcpy(d_fwd, fwd.data(), fwd.size() * 4, hipMemcpyHostToDevice));
+    if (!rev.empty()) HIP_CHECK(hipMemcpy(d_rev, rev.data(), rev.size() * 4, hipMemcpyHostToDevice));
+    D.voc.exp_off = std::move(d_off);
+    D.voc.exp_fwd = std::move(d_fwd);
+    D.voc.exp_rev = std::move(d_rev);
+    return Status();
+  });
+  if (!s.ok()) return s;
+  D.voc.vocab = (uint32_t)V;
+  D.voc.info[0] = n_allowed;
+  D.voc.info[1] = n_split;
+  D.voc.info[2] = longest;
+  D.voc.set = true;
+  if (info) for (int i = 0; i < 3; i++) info[i] = D.voc.info[i];
+  return Status();
+}
+
+void BaseEncoder::vocabulary_stats(unsigned long long out[4]) const {
+  for (int i = 0; i < 4; i++) out[i] = dev_ ? dev_->voc.stats[i].load() : 0ull;
+}
+
+Status BaseEncoder::restrict_ids_device(const void *d_ids, const void *d_offsets, unsigned long long n_sent, unsigned long long n_ids, bool reverse,
+                                        unsigned long long *n_out, double *kernel_ms) const {
+  if (n_out) *n_out = 0;
+  StageClock ms(kernel_ms);
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (n_sent && !d_offsets) return Status(2, "restrict_ids_device: no offsets");
+  if (n_ids && !d_ids) return Status(2, "restrict_ids_device: no ids");
+  if (((uintptr_t)d_ids & 3u) != 0) return Status(2, "restrict_ids_device: the ids must be 4-byte aligned");
+  const Lane0 l(*dev_);
+  if (!dev_->voc.set) return Status(1, "restrict_ids_device: no vocabulary is set");  // (before any work: what was pending stays)
+  return restrict_on_lane(*dev_, l.d, device_, (const int32_t *)d_ids, (const unsigned long long *)d_offsets, n_sent, n_ids, reverse, false, n_out, ms.next());
+}
+
 Status encode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_bytes, const void *d_offsets,
                       unsigned long long n_sent, unsigned long long total_bytes, unsigned long long max_sentence_bytes, bool bos, bool eos, bool reverse,
                       double dropout_prob, unsigned long long *n_ids_out, double *kernel_ms) {
@@ -297,7 +435,7 @@ Status encode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, i
       encode_cached(D, d, d_bytes, (const unsigned long long *)d_offsets, n_sent, total_bytes, max_sentence_bytes, bos, eos, reverse, n_ids_out);
       ev.stop(true);
       if (kernel_ms) *kernel_ms = ev.elapsed_ms();
-      return Status();
+      return restrict_tail(D, d, device, reverse, n_ids_out, kernel_ms);
     }
     k5_pass(D, d, d_bytes, (const unsigned long long *)d_offsets, nullptr, n_sent, total_bytes, max_sentence_bytes, bos, eos, reverse, dropout_prob,
             d.k5.counts);
@@ -309,7 +447,7 @@ Status encode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, i
     if (kernel_ms) *kernel_ms = ev.elapsed_ms();
     d.res.n_ids = total;
     if (n_ids_out) *n_ids_out = total;
-    return Status();
+    return restrict_tail(D, d, device, reverse, n_ids_out, kernel_ms);
   });
 }
 

@@ -464,4 +464,15 @@ void launch_idprint(bool write, const int32_t *ids, const unsigned long long *io
 // aligned address; 1 <= n_bins <= 2^31.  The caller zeroes counts where it does not accumulate.
 void launch_idcount(const int32_t *ids, unsigned long long n_ids, unsigned long long n_bins, unsigned long long *counts, hipStream_t st);
 
+// ---- the vocabulary restriction (k_restrict.h, compiled with k_encode.hip): measure -> launch_exclusive_scan -> write ----
+struct RestrictTable {
+  const uint32_t *exp_off;  // [vocab + 1]
+  const int32_t *exp_ids;   // the expansion of every id of [0, vocab) back to back (the forward table, or the one with every expansion reversed)
+  uint32_t vocab;
+};
+// sentence s = ids[off[s] .. off[s + 1]) -> out_len[n_sent], the ids of its expansions, then those ids at out[out_off[s] ..), out_off the
+// exclusive scan of out_len.  out: 16-byte aligned.  n_ids sizes the groups of sentences.
+void launch_restrict(bool write, const int32_t *ids, const unsigned long long *off, unsigned long long n_sent, unsigned long long n_ids,
+                     const RestrictTable &tb, uint32_t *out_len, const unsigned long long *out_off, int32_t *out, hipStream_t st);
+
 }  // namespace yttm

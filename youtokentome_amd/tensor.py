@@ -283,6 +283,54 @@ def decode_text_tensor(bpe, text, ignore_ids=None, as_str=True):
     return _take_text(torch, core, dev, n, n_text, False)
 
 
+def restrict_tensor(bpe, ids, lengths=None, offsets=None, reverse=False, padded=None, width=None, pad_id=None):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    _check_on(ids, dev, "ids")
+    if ids.dtype == torch.int64:
+        ids = ids.to(torch.int32)
+    elif ids.dtype != torch.int32:
+        raise ValueError("ids must be an int32 or int64 tensor")
+    if ids.dim() == 2:
+        if offsets is not None:
+            raise ValueError("offsets go with 1-D ids; a 2-D matrix takes lengths")
+        n, w = ids.shape
+        if lengths is None:
+            lens = torch.full((n,), w, dtype=torch.int64, device=dev)
+        else:
+            _check_on(lengths, dev, "lengths")
+            if lengths.dim() != 1 or lengths.numel() != n:
+                raise ValueError("lengths must have one entry per row")
+            lens = lengths.to(torch.int64).clamp(0, w)
+        # the rows' ids back to back (the library's pass takes the ragged form)
+        keep = torch.arange(w, device=dev).unsqueeze(0) < lens.unsqueeze(1)
+        flat = ids[keep].contiguous()
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(lens, 0, out=offsets[1:])
+        ids = flat
+        if padded is None:
+            padded = True
+    elif ids.dim() == 1:
+        if offsets is None or lengths is not None:
+            raise ValueError("1-D ids take offsets [n + 1] (and no lengths)")
+        offsets = _offsets_u64(torch, offsets, dev)
+        ids = ids.contiguous()
+        n = offsets.numel() - 1
+        if n < 0:
+            raise ValueError("offsets must have at least one entry")
+        if n and (int(offsets[-1]) > ids.numel() or int(offsets[0]) != 0 or bool((offsets[1:] < offsets[:-1]).any())):
+            raise ValueError("offsets must start at 0, be non-decreasing and end inside ids")
+        if padded is None:
+            padded = False
+    else:
+        raise ValueError("ids must be 1-D (with offsets) or 2-D (padded)")
+    pad_id = _pad_id(bpe, padded, pad_id)
+    n_in = int(offsets[-1]) if n else 0
+    n_out, _ = _synced(torch, dev, core.restrict_ids_device_raw, ids.data_ptr(), offsets.data_ptr(), n, n_in, reverse)
+    return _take_encoded(torch, core, dev, n, n_out, padded, width, pad_id)
+
+
 def id_counts_tensor(bpe, ids=None, n_bins=None, accumulate=False):
     torch = _torch()
     core = bpe.bpe_cython

@@ -5,7 +5,8 @@ loops (bpe.cpp:1942-2028, utils.h:92-103).  Run as `python -m youtokentome_amd.y
 Two more commands work file to file through the device, with the same bytes as the streaming ones: `encode_file` (--output_type id: binary
 PREFIX.ids / PREFIX.off; subword and id_text: the text `encode --output_type subword` / `id` prints) and `decode_file` (a file of decimal ids
 -> the text `decode` prints).  `count_file` prints how often a text file uses every token, counted on the device: the lines of `vocab` with a
-third column.
+third column.  `encode`, `encode_file` and `count_file` take `--vocabulary FILE --vocabulary_threshold N`: FILE is what `count_file` wrote, and tokens
+it counts fewer than N times are split back into smaller pieces (subword-nmt's --vocabulary / --vocabulary-threshold).
 
 The loops themselves are C++ (youtokentome_amd/csrc/host_cli.cpp, behind yttm_encode_cli / yttm_decode_cli / yttm_vocab_cli):
 stdin and stdout stay bytes end to end, invalid UTF-8 included."""
@@ -18,6 +19,37 @@ from .bpe import _Core
 @click.group()
 def main():
     pass
+
+
+def _vocabulary_options(f):
+    f = click.option("--vocabulary_threshold", type=click.INT, default=1, show_default=True,
+                     help="With --vocabulary: tokens the file counts fewer times than this are split into smaller pieces.")(f)
+    return click.option("--vocabulary", type=click.Path(exists=True, dir_okay=False), required=False,
+                        help="A file `count_file` wrote (id<TAB>subword<TAB>count): encode with the tokens it counts often enough only.")(f)
+
+
+def _set_vocabulary(core, path, threshold):
+    """the vocabulary file -> the allowed set of the encoder; ids missing from the file count 0"""
+    if path is None:
+        return
+    vocab = core.vocab()
+    counts = [0] * len(vocab)
+    with open(path, "rb") as f:
+        for no, line in enumerate(f.read().split(b"\n"), 1):
+            if not line:
+                continue
+            cols = line.split(b"\t")
+            try:
+                if len(cols) != 3:
+                    raise ValueError
+                i, n = int(cols[0]), int(cols[2])
+            except ValueError:
+                raise click.ClickException("%s:%d: expected id<TAB>subword<TAB>count" % (path, no))
+            if not 0 <= i < len(vocab) or vocab[i].encode() != cols[1]:
+                raise click.ClickException("%s:%d: id %d is not this model's %r: the vocabulary belongs to another model" % (
+                    path, no, i, cols[1].decode(errors="replace")))
+            counts[i] = n
+    core.set_vocabulary([n >= threshold for n in counts])
 
 
 @main.command()
@@ -46,11 +78,13 @@ def bpe(data, model, vocab_size, coverage, n_threads, pad_id, unk_id, bos_id, eo
 @click.option("--stream", is_flag=True, help="Process each line before reading the next one.")
 @click.option("--dropout_prob", type=click.FLOAT, default=0, show_default=True,
               help="BPE-dropout probability (the probability of a merge being dropped)")
-def encode(model, output_type, n_threads, bos, eos, reverse, stream, dropout_prob):
+@_vocabulary_options
+def encode(model, output_type, n_threads, bos, eos, reverse, stream, dropout_prob, vocabulary, vocabulary_threshold):
     """Encode text to ids or subwords."""
     if n_threads < -1 or n_threads == 0:  # yttm_cli.py:110-114
         raise ValueError('Invalid value for "--n_threads": must be -1 or positive integer, not "%d"' % n_threads)
     core = _Core(model, n_threads)
+    _set_vocabulary(core, vocabulary, vocabulary_threshold)
     core.encode_cli(output_type, stream, bos, eos, reverse, dropout_prob)  # the C++ loop: yttm_encode_cli (host_cli.cpp)
 
 
@@ -66,9 +100,11 @@ def encode(model, output_type, n_threads, bos, eos, reverse, stream, dropout_pro
 @click.option("--reverse", is_flag=True, help="Reverse output sequence of tokens.")
 @click.option("--dropout_prob", type=click.FLOAT, default=0, show_default=True,
               help="BPE-dropout probability (the probability of a merge being dropped)")
-def encode_file(model, input_path, output, output_type, bos, eos, reverse, dropout_prob):
+@_vocabulary_options
+def encode_file(model, input_path, output, output_type, bos, eos, reverse, dropout_prob, vocabulary, vocabulary_threshold):
     """Encode a text file to binary ids and line offsets, or to a text file of subwords."""
     core = _Core(model)
+    _set_vocabulary(core, vocabulary, vocabulary_threshold)
     if output_type == "subword":  # the same pipeline with the formatter behind the encode: yttm_encode_file_subword (host_lines.cpp)
         core.encode_file_subword(input_path, output, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob)
         return
@@ -117,10 +153,12 @@ def decode_file(model, input_path, output, ignore_ids):
 @click.option("--eos", is_flag=True, help="Add tab end of sentence.")
 @click.option("--dropout_prob", type=click.FLOAT, default=0, show_default=True,
               help="BPE-dropout probability (the probability of a merge being dropped)")
-def count_file(model, input_path, output, bos, eos, dropout_prob):
+@_vocabulary_options
+def count_file(model, input_path, output, bos, eos, dropout_prob, vocabulary, vocabulary_threshold):
     """Print how often the file uses every token: id<TAB>subword<TAB>count, in id order."""
     import sys
     core = _Core(model)
+    _set_vocabulary(core, vocabulary, vocabulary_threshold)
     counts = core.encode_file_counts(input_path, bos=bos, eos=eos, dropout_prob=dropout_prob)  # the C++ pipeline: yttm_encode_file_counts (host_lines.cpp)
     # (the first two columns are those of `vocab`: the id and id_to_subword(id) as it stands)
     text = b"".join(b"%d\t%s\t%d\n" % (i, piece.encode(), int(counts[i])) for i, piece in enumerate(core.vocab()))
