@@ -236,6 +236,64 @@ int yttm_id_counts_copy_device(yttm_encoder *enc, void *d_counts, uint64_t n_bin
 int yttm_encode_file_counts(yttm_encoder *enc, const char *path, int bos, int eos, int reverse, double dropout_prob, uint64_t chunk_bytes,
                             uint64_t *counts, uint64_t *n_lines, uint64_t *n_ids, char *report_json, int report_len, char *err, int errlen);
 
+/* Training blocks: sentences of ids packed into rows of exactly seq_len ids on the device (the reference has no counterpart).
+ * Input: a sequence of sentences, each a list of int32 ids in stored order (ids[K], uint64 offsets[S + 1]).
+ * Parameters: seq_len L, 1 <= L <= 2^24 (outside that range: code 1; it bounds the open row's buffer); mode, 0 = stream, 1 = whole; pad_value, any
+ * int32; tail, 0 = pad, 1 = keep, 2 = drop.
+ * An empty sentence contributes nothing anywhere.
+ * The open row: the encoder owns one open row.  It holds fewer than L ids with their sentence boundaries, starts empty, and is bound to
+ * (L, mode): a call with another L or mode while it is non-empty returns code 1 and changes nothing.  A call packs the sequence
+ * "open row ++ the call's sentences".
+ * Stream mode: the ids of all sentences are concatenated; row r holds positions [r L, (r + 1) L) of that stream.
+ * Whole mode: next-fit in order.  A sentence joins the current row if the row's ids plus its own are <= L; otherwise the row is closed and the
+ * sentence starts a new one; a row that reaches exactly L ids is closed.  A sentence longer than L is an error, as yttm_encode_copy_padded
+ * refuses width < longest: code 1, the message naming the sentence's index and length; nothing is written and the open row is unchanged.
+ * tail: after the complete rows one incomplete row of f ids (0 < f < L) may remain.  tail = 0 emits it with pad_value behind its ids and empties
+ * the open row; tail = 1 emits nothing for it and makes it the new open row; tail = 2 discards it and empties the open row.
+ * A fragment is a maximal run of ids inside one row that belong to one sentence; in whole mode the fragments are exactly the non-empty
+ * sentences, in order.
+ * Result, for n_rows rows and n_frags fragments:
+ *   int32  rows[n_rows][L]        the ids; pad_value on padding
+ *   int32  seg[n_rows][L]         1-based ordinal of the id's fragment within its row; 0 on padding
+ *   int32  pos[n_rows][L]         index of the id within its fragment, so a fragment at a row's start begins at 0 even when its sentence began in
+ *                                 the row before; 0 on padding
+ *   int32  frags[n_frags][2]      (flat start r L + c, length), in ascending order
+ *   uint64 row_frags[n_rows + 1]  row r's fragments are frags[row_frags[r] .. row_frags[r + 1])
+ * Limit: a call whose n_rows L exceeds 2^31 - 1 returns code 1 (and changes nothing).
+ * Consequences: in both modes the rows with padding removed, concatenated, are the input ids in order (but for the ids tail = 2 drops or tail = 1
+ * keeps); with tail = 1 on every call but the last, the rows of several calls concatenated are the rows of one call on the concatenated
+ * input; in stream mode only the last row can hold padding.
+ *
+ * yttm_blocks_device packs the pending encode result, whichever call left it (n_sent must be its, as for yttm_idtext_device); the result stays
+ * pending and unchanged.  yttm_blocks_ids_device: the same over int32 d_ids[n_ids] + uint64 d_offsets[n_sent + 1] in HBM that the encoder did not
+ * make (offsets[0] = 0, the conventions of yttm_decode_device: 4-byte aligned ids, the caller synchronises the stream that wrote them first).
+ * The blocks live in a slot of the encoder's own: only the next blocks call replaces it.  kernel_ms (optional) = HIP-event time of all passes.
+ * yttm_blocks_flush: the open row as a result of 0 or 1 rows (its tail padded); the open row is then empty.
+ * yttm_blocks_open: out = {ids in the open row, its L, its mode} (zeroes when it is empty).  yttm_blocks_discard empties the open row -- the reset,
+ * a call of its own so that no argument of another call has a second meaning.
+ * yttm_blocks_fetch / yttm_blocks_copy_device: the five arrays to host memory / to device memory the caller owns; any null pointer is skipped;
+ * n_rows and n_frags must match the slot's, else code 1.  (seg and pos are kept in the slot: both exits are plain copies.) */
+int yttm_blocks_device(yttm_encoder *enc, uint64_t n_sent, uint64_t seq_len, int mode, int32_t pad_value, int tail, uint64_t *n_rows, uint64_t *n_frags,
+                       double *kernel_ms, char *err, int errlen);
+int yttm_blocks_ids_device(yttm_encoder *enc, const void *d_ids, const void *d_offsets, uint64_t n_sent, uint64_t n_ids, uint64_t seq_len, int mode,
+                           int32_t pad_value, int tail, uint64_t *n_rows, uint64_t *n_frags, double *kernel_ms, char *err, int errlen);
+int yttm_blocks_flush(yttm_encoder *enc, int32_t pad_value, uint64_t *n_rows, uint64_t *n_frags, double *kernel_ms, char *err, int errlen);
+int yttm_blocks_open(yttm_encoder *enc, uint64_t out[3]);
+int yttm_blocks_discard(yttm_encoder *enc);
+int yttm_blocks_fetch(yttm_encoder *enc, int32_t *rows, int32_t *seg, int32_t *pos, int32_t *frags, uint64_t *row_frags, uint64_t n_rows, uint64_t n_frags,
+                      char *err, int errlen);
+int yttm_blocks_copy_device(yttm_encoder *enc, void *d_rows, void *d_seg, void *d_pos, void *d_frags, void *d_row_frags, uint64_t n_rows, uint64_t n_frags,
+                            char *err, int errlen);
+/* The pipeline of yttm_encode_file with the packing in place of the download of ids: every piece is packed with tail = 1, the last piece is
+ * followed by the flush (tail = 0) or the drop (tail = 2; any other value: code 1).  It writes PREFIX.rows (int32 [n_rows][L]) and PREFIX.frags
+ * (uint64 [n_frags][2], the starts flat over the whole file); with dropout_prob == 0 the two files do not depend on chunk_bytes.  The same
+ * file errors and <BOS> / <EOS> messages as yttm_encode_file; a sentence longer than L in whole mode names its line number in the file (from 1).
+ * It starts from an empty open row and leaves it empty; it uses both lanes, so a pending device result does not survive it.  The report's keys
+ * are those of yttm_encode_file plus "rows", "frags" and "seconds_blocks". */
+int yttm_encode_file_blocks(yttm_encoder *enc, const char *path, const char *out_prefix, int bos, int eos, int reverse, double dropout_prob,
+                            uint64_t chunk_bytes, uint64_t seq_len, int mode, int32_t pad_value, int tail, uint64_t *n_rows, uint64_t *n_frags,
+                            uint64_t *n_lines, uint64_t *n_ids, char *report_json, int report_len, char *err, int errlen);
+
 /* Encode under a restricted vocabulary (subword-nmt's --vocabulary / --vocabulary-threshold, SentencePiece's SetVocabulary; the reference has no
  * counterpart).  A model has rules (x, y, z) with distinct z, as written in the model file behind the char section.  Let V = yttm_vocab_size(enc)
  * and A, a subset of [0, V), the allowed set.  The expansion E(v) of an id:

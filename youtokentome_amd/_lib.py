@@ -29,6 +29,8 @@ EXPORTS = [
     "yttm_spans_device", "yttm_spans_text_device", "yttm_spans_fetch", "yttm_spans_copy_device", "yttm_spans_copy_padded", "yttm_encode_as_ids_spans",
     "yttm_id_counts_device", "yttm_id_counts_ids_device", "yttm_id_counts_fetch", "yttm_id_counts_copy_device", "yttm_encode_file_counts",
     "yttm_encoder_set_vocabulary", "yttm_encoder_vocabulary_stats", "yttm_restrict_ids_device",
+    "yttm_blocks_device", "yttm_blocks_ids_device", "yttm_blocks_flush", "yttm_blocks_open", "yttm_blocks_discard", "yttm_blocks_fetch", "yttm_blocks_copy_device",
+    "yttm_encode_file_blocks",
     "yttm_device_info", "yttm_comm_rccl_unique_id", "yttm_comm_rccl_create", "yttm_comm_callback_create",
     "yttm_comm_destroy", "yttm_train_bpe_comm", "yttm_train_bpe_from_device_comm", "yttm_train_bpe_from_memory_comm",
     # include/yttm_gpu.h
@@ -98,6 +100,14 @@ def load():
     L.yttm_encoder_set_vocabulary.argtypes = [cvp, u8p, C.c_uint64, u64p, cs, ci]
     L.yttm_encoder_vocabulary_stats.argtypes = [cvp, u64p]
     L.yttm_restrict_ids_device.argtypes = [cvp, cvp, cvp, C.c_uint64, C.c_uint64, ci, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_blocks_device.argtypes = [cvp, C.c_uint64, C.c_uint64, ci, C.c_int32, ci, u64p, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_blocks_ids_device.argtypes = [cvp, cvp, cvp, C.c_uint64, C.c_uint64, C.c_uint64, ci, C.c_int32, ci, u64p, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_blocks_flush.argtypes = [cvp, C.c_int32, u64p, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_blocks_open.argtypes = [cvp, u64p]
+    L.yttm_blocks_discard.argtypes = [cvp]
+    L.yttm_blocks_fetch.argtypes = [cvp, i32p, i32p, i32p, i32p, u64p, C.c_uint64, C.c_uint64, cs, ci]
+    L.yttm_blocks_copy_device.argtypes = [cvp, cvp, cvp, cvp, cvp, cvp, C.c_uint64, C.c_uint64, cs, ci]
+    L.yttm_encode_file_blocks.argtypes = [cvp, cs, cs, ci, ci, ci, cd, C.c_uint64, C.c_uint64, ci, C.c_int32, ci, u64p, u64p, u64p, u64p, cs, ci, cs, ci]
     L.yttm_encoder_set_cache.argtypes = [cvp, ci, C.c_uint64]
     L.yttm_encode_cache_words.argtypes = [cvp]
     L.yttm_encode_cache_words.restype = C.c_uint64

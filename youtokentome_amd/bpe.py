@@ -389,6 +389,69 @@ class _Core:
             return counts, json.loads(rep.value.decode())
         return counts
 
+    # ---- training blocks on the device (include/yttm_mi355x.h "Training blocks"): rows of exactly seq_len ids in a slot of the encoder's own
+    MODES = {"stream": 0, "whole": 1}
+    TAILS = {"pad": 0, "keep": 1, "drop": 2}
+
+    def blocks_device_raw(self, n_sent, seq_len, mode=0, pad_value=0, tail=0):
+        """packs the pending encode result of n_sent sentences -> (n_rows, n_frags, kernel_ms); the result stays pending"""
+        nr, nf, ms, err = C.c_uint64(), C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_blocks_device(self._h, n_sent, int(seq_len), int(mode), int(pad_value), int(tail), C.byref(nr), C.byref(nf), C.byref(ms),
+                                                   err, _lib.ERRLEN), err)
+        return nr.value, nf.value, ms.value
+
+    def blocks_ids_device_raw(self, d_ids, d_offsets, n_sent, n_ids, seq_len, mode=0, pad_value=0, tail=0):
+        """packs int32 ids[n_ids] + uint64 offsets[n_sent + 1] in device memory -> (n_rows, n_frags, kernel_ms)"""
+        nr, nf, ms, err = C.c_uint64(), C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_blocks_ids_device(self._h, C.c_void_p(d_ids), C.c_void_p(d_offsets), n_sent, n_ids, int(seq_len), int(mode), int(pad_value),
+                                                       int(tail), C.byref(nr), C.byref(nf), C.byref(ms), err, _lib.ERRLEN), err)
+        return nr.value, nf.value, ms.value
+
+    def blocks_flush_raw(self, pad_value=0):
+        """the open row as a result of 0 or 1 rows -> (n_rows, n_frags, kernel_ms)"""
+        nr, nf, ms, err = C.c_uint64(), C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_blocks_flush(self._h, int(pad_value), C.byref(nr), C.byref(nf), C.byref(ms), err, _lib.ERRLEN), err)
+        return nr.value, nf.value, ms.value
+
+    def blocks_open(self):
+        """(ids in the open row, its seq_len, its mode); zeroes when it is empty"""
+        out = (C.c_uint64 * 3)()
+        _lib.load().yttm_blocks_open(self._h, out)
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def blocks_discard(self):
+        _lib.load().yttm_blocks_discard(self._h)
+
+    def fetch_blocks(self, n_rows, n_frags, seq_len):
+        """the blocks slot -> (rows, seg, pos [n_rows, seq_len] int32, frags [n_frags, 2] int32, row_frags [n_rows + 1] uint64)"""
+        rows, seg, pos = (np.zeros((n_rows, seq_len), np.int32) for _ in range(3))
+        frags, row_frags, err = np.zeros((n_frags, 2), np.int32), np.zeros(n_rows + 1, np.uint64), _err()
+        self._check(_lib.load().yttm_blocks_fetch(self._h, rows.ctypes.data_as(_lib.i32p), seg.ctypes.data_as(_lib.i32p), pos.ctypes.data_as(_lib.i32p),
+                                                  frags.ctypes.data_as(_lib.i32p), row_frags.ctypes.data_as(_lib.u64p), n_rows, n_frags, err, _lib.ERRLEN), err)
+        return rows, seg, pos, frags, row_frags
+
+    def copy_blocks_device(self, d_rows, d_seg, d_pos, d_frags, d_row_frags, n_rows, n_frags):
+        err = _err()
+        self._check(_lib.load().yttm_blocks_copy_device(self._h, C.c_void_p(d_rows), C.c_void_p(d_seg), C.c_void_p(d_pos), C.c_void_p(d_frags),
+                                                        C.c_void_p(d_row_frags), n_rows, n_frags, err, _lib.ERRLEN), err)
+
+    def encode_file_blocks(self, path, out, seq_len, mode=0, bos=False, eos=False, reverse=False, dropout_prob=0.0, pad_value=0, tail=0, chunk_bytes=None,
+                           report=False):
+        """a text file -> OUT.rows (int32 [n_rows, seq_len]) and OUT.frags (uint64 [n_frags, 2]): (n_rows, n_frags, n_lines, n_ids), or with report=True
+        the call's report (a dict)"""
+        _check_dropout(dropout_prob)
+        nr, nf, nl, ni, err = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), _err()
+        rep = C.create_string_buffer(1024)
+        rc = _lib.load().yttm_encode_file_blocks(self._h, os.fsencode(path), os.fsencode(out), int(bos), int(eos), int(reverse), float(dropout_prob),
+                                                 int(chunk_bytes or 0), int(seq_len), int(mode), int(pad_value), int(tail), C.byref(nr), C.byref(nf), C.byref(nl),
+                                                 C.byref(ni), rep, len(rep), err, _lib.ERRLEN)
+        if rc != 0:
+            raise ValueError(err.value.decode(errors="replace"))
+        if report:
+            import json
+            return json.loads(rep.value.decode())
+        return nr.value, nf.value, nl.value, ni.value
+
     # ---- decimal id text on the device (include/yttm_mi355x.h): the format `yttm encode --output_type id` prints and `yttm decode` reads
     def ids_parse_device_raw(self, d_text, n_bytes):
         """-> (n_lines, n_ids, kernel_ms); the ids `while (ss >> x)` reads from every line are pending as after encode_device_raw with n_sent = n_lines"""
@@ -690,6 +753,62 @@ class BPE:
         piece: only the counts come down.  The last entry counts ids outside the vocabulary (0 for an encode).  report=True: (counts, the call's
         report as a dict).  Needs no torch."""
         return self.bpe_cython.encode_file_counts(path, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, chunk_bytes=chunk_bytes, report=report)
+
+    # ---- rows of exactly seq_len ids for language-model training (include/yttm_mi355x.h "Training blocks"; the reference has no counterpart)
+    def encode_blocks_tensor(self, sentences, seq_len: int, mode: str = "stream", bos: bool = False, eos: bool = False, reverse: bool = False,
+                             dropout_prob: float = 0, pad_id: Optional[int] = None, tail: str = "pad", device=None):
+        """encode_tensor's sentences packed on the device into rows of exactly seq_len ids -> Blocks(rows, seg, pos, frags, row_frags), tensors on
+        the encoder's device: rows, seg, pos int32 [n_rows, seq_len] (the ids; the 1-based number of the id's fragment within its row, 0 on padding;
+        the id's index within its fragment), frags int32 [n_frags, 2] ((flat start, length) of every fragment), row_frags int64 [n_rows + 1].
+        mode="stream" concatenates the sentences and cuts every seq_len ids; mode="whole" places sentences whole, several to a row (a sentence
+        longer than seq_len raises).  tail: "pad" emits the incomplete last row with pad_id (default: the model's <PAD>) behind its ids, "keep" keeps
+        it as this object's open row, which the next blocks call continues (blocks_flush_tensor ends it), "drop" discards it."""
+        from . import tensor
+        return tensor.encode_blocks_tensor(self, sentences, seq_len, mode=mode, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, pad_id=pad_id,
+                                           tail=tail, device=device)
+
+    def encode_text_blocks_tensor(self, text, seq_len: int, mode: str = "stream", bos: bool = False, eos: bool = False, reverse: bool = False,
+                                  dropout_prob: float = 0, pad_id: Optional[int] = None, tail: str = "pad"):
+        """the same for `text` as encode_text_tensor takes it, one sentence per line"""
+        from . import tensor
+        return tensor.encode_text_blocks_tensor(self, text, seq_len, mode=mode, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, pad_id=pad_id,
+                                                tail=tail)
+
+    def blocks_tensor(self, ids=None, lengths=None, offsets=None, seq_len: int = 0, mode: str = "stream", pad_id: Optional[int] = None, tail: str = "pad"):
+        """packs ids this object did not encode: `ids`, `lengths`, `offsets` as decode_tensor takes them (a 2-D padded matrix with lengths, or 1-D
+        int32 ids with offsets [n + 1]); ids=None packs the pending result of the last *_tensor encode or parse call -> Blocks as encode_blocks_tensor"""
+        from . import tensor
+        return tensor.blocks_tensor(self, ids=ids, lengths=lengths, offsets=offsets, seq_len=seq_len, mode=mode, pad_id=pad_id, tail=tail)
+
+    def blocks_flush_tensor(self, pad_id: Optional[int] = None):
+        """the open row as Blocks of 0 or 1 rows; the open row is empty afterwards"""
+        from . import tensor
+        return tensor.blocks_flush_tensor(self, pad_id=pad_id)
+
+    def blocks_open(self):
+        """(ids in the open row, its seq_len, its mode as "stream" / "whole"), or (0, 0, None) when it is empty"""
+        f, L, mode = self.bpe_cython.blocks_open()
+        return (f, L, "whole" if mode else "stream") if f else (0, 0, None)
+
+    def blocks_discard(self):
+        """empties the open row without emitting it"""
+        self.bpe_cython.blocks_discard()
+
+    def encode_file_blocks(self, path, out: str, seq_len: int, mode: str = "stream", bos: bool = False, eos: bool = False, reverse: bool = False,
+                           dropout_prob: float = 0, pad_id: Optional[int] = None, drop_last: bool = False, chunk_bytes: Optional[int] = None,
+                           report: bool = False):
+        """A text file, one sentence per line -> OUT.rows (int32 [n_rows, seq_len]) and OUT.frags (uint64 [n_frags, 2], (flat start, length) over the
+        whole file), packed on the device piece by piece; the files do not depend on chunk_bytes.  drop_last discards the incomplete last row
+        instead of padding it.  Returns (n_rows, n_frags, n_lines, n_ids), or with report=True the call's report (a dict).  Needs no torch."""
+        core = self.bpe_cython
+        if mode not in core.MODES:
+            raise ValueError('mode must be "stream" or "whole"')
+        if pad_id is None:
+            pad_id = self.subword_to_id("<PAD>")
+            if not drop_last and (pad_id == -1 or self.id_to_subword(pad_id) != "<PAD>"):
+                raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
+        return core.encode_file_blocks(path, out, seq_len, core.MODES[mode], bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, pad_value=pad_id,
+                                       tail=2 if drop_last else 0, chunk_bytes=chunk_bytes, report=report)
 
     # ---- encode with only the tokens a corpus uses often enough (include/yttm_mi355x.h "Encode under a restricted vocabulary")
     def set_vocabulary(self, allowed=None, counts=None, threshold: int = 1):

@@ -378,6 +378,59 @@ int yttm_encode_file_counts(yttm_encoder *h, const char *path, int bos, int eos,
   return finish(s, err, errlen);
 }
 
+static int blocks_done(const Status &s, unsigned long long nr, unsigned long long nf, uint64_t *n_rows, uint64_t *n_frags, char *err, int errlen) {
+  if (n_rows) *n_rows = nr;
+  if (n_frags) *n_frags = nf;
+  return finish(s, err, errlen);
+}
+int yttm_blocks_device(yttm_encoder *h, uint64_t n_sent, uint64_t seq_len, int mode, int32_t pad_value, int tail, uint64_t *n_rows, uint64_t *n_frags,
+                       double *kernel_ms, char *err, int errlen) {
+  unsigned long long nr = 0, nf = 0;
+  const Status s = h->enc->blocks_device(n_sent, seq_len, mode, pad_value, tail, &nr, &nf, kernel_ms);
+  return blocks_done(s, nr, nf, n_rows, n_frags, err, errlen);
+}
+int yttm_blocks_ids_device(yttm_encoder *h, const void *d_ids, const void *d_offsets, uint64_t n_sent, uint64_t n_ids, uint64_t seq_len, int mode,
+                           int32_t pad_value, int tail, uint64_t *n_rows, uint64_t *n_frags, double *kernel_ms, char *err, int errlen) {
+  unsigned long long nr = 0, nf = 0;
+  const Status s = h->enc->blocks_ids_device(d_ids, d_offsets, n_sent, n_ids, seq_len, mode, pad_value, tail, &nr, &nf, kernel_ms);
+  return blocks_done(s, nr, nf, n_rows, n_frags, err, errlen);
+}
+int yttm_blocks_flush(yttm_encoder *h, int32_t pad_value, uint64_t *n_rows, uint64_t *n_frags, double *kernel_ms, char *err, int errlen) {
+  unsigned long long nr = 0, nf = 0;
+  const Status s = h->enc->blocks_flush(pad_value, &nr, &nf, kernel_ms);
+  return blocks_done(s, nr, nf, n_rows, n_frags, err, errlen);
+}
+int yttm_blocks_open(yttm_encoder *h, uint64_t out[3]) {
+  unsigned long long o3[3] = {0, 0, 0};
+  h->enc->blocks_open(o3);
+  for (int i = 0; i < 3; i++) out[i] = o3[i];
+  return 0;
+}
+int yttm_blocks_discard(yttm_encoder *h) {
+  h->enc->blocks_discard();
+  return 0;
+}
+int yttm_blocks_fetch(yttm_encoder *h, int32_t *rows, int32_t *seg, int32_t *pos, int32_t *frags, uint64_t *row_frags, uint64_t n_rows, uint64_t n_frags,
+                      char *err, int errlen) {
+  return finish(h->enc->take_blocks(rows, seg, pos, frags, row_frags, n_rows, n_frags, false), err, errlen);
+}
+int yttm_blocks_copy_device(yttm_encoder *h, void *d_rows, void *d_seg, void *d_pos, void *d_frags, void *d_row_frags, uint64_t n_rows, uint64_t n_frags,
+                            char *err, int errlen) {
+  return finish(h->enc->take_blocks(d_rows, d_seg, d_pos, d_frags, d_row_frags, n_rows, n_frags, true), err, errlen);
+}
+int yttm_encode_file_blocks(yttm_encoder *h, const char *path, const char *out_prefix, int bos, int eos, int reverse, double dropout_prob, uint64_t chunk_bytes,
+                            uint64_t seq_len, int mode, int32_t pad_value, int tail, uint64_t *n_rows, uint64_t *n_frags, uint64_t *n_lines, uint64_t *n_ids,
+                            char *report_json, int report_len, char *err, int errlen) {
+  unsigned long long nr = 0, nf = 0, nl = 0, ni = 0;
+  std::string report;
+  const Status s = h->enc->encode_file_blocks(path ? path : "", out_prefix ? out_prefix : "", bos, eos, reverse, dropout_prob, chunk_bytes, seq_len, mode, pad_value,
+                                              tail, &nr, &nf, &nl, &ni, &report);
+  if (n_lines) *n_lines = nl;
+  if (n_ids) *n_ids = ni;
+  if (s.ok() && report_json && report_len > 0) snprintf(report_json, (size_t)report_len, "%s", report.c_str());
+  return blocks_done(s, nr, nf, n_rows, n_frags, err, errlen);
+}
+
 int yttm_encoder_set_vocabulary(yttm_encoder *h, const uint8_t *allowed, uint64_t n, uint64_t *info, char *err, int errlen) {
   unsigned long long i3[3] = {0, 0, 0};
   Status s = h->enc->set_vocabulary(allowed, n, i3);

@@ -142,6 +142,22 @@ struct EncoderDevice {
     unsigned long long n_bins = 0;
     bool valid = false;
   } idc;
+  // training blocks (host_decode.cpp, k_blocks.h), the encoder's own like the counts and under lane 0's mutex: the slot of the last blocks call
+  // (rows, seg, pos: [n_rows][L] rounded up to a multiple of 4 elements; frags [n_frags][2]; row_frags [n_rows + 1]), the open row in two
+  // generations (a call reads one and writes the other), and the passes' working arrays.
+  struct {
+    DevBuf<int32_t> rows, seg, pos, frags;
+    DevBuf<unsigned long long> row_frags;
+    unsigned long long n_rows = 0, n_frags = 0, L = 0;
+    bool valid = false;
+    DevBuf<int32_t> open_ids[2];
+    DevBuf<unsigned long long> open_off[2];
+    int gen = 0;                                              // the generation that holds the open row
+    unsigned long long open_f = 0, open_m = 0, open_L = 0;    // its ids and fragments; the (L, mode) it is bound to while open_f > 0
+    int open_mode = 0;
+    DevBuf<uint32_t> cnt, nxt, entry, rowbase, rowsent, rowcnt;
+    DevBuf<unsigned long long> ne, hop, rowsrc, info;  // info[0 .. 2] (k_blocks.h), info[3]: a sentence longer than L
+  } blk;
   // the restricted vocabulary (host_encoder.cpp set_vocabulary, k_restrict.h): exp_ids[exp_off[v] .. exp_off[v + 1]) = E(v), and the same with every
   // expansion back to front.  Written with every lane locked, read by a call that holds its lane: a call never sees half a table.
   struct {
@@ -266,6 +282,19 @@ Status idtext_on_lane(EncodeLane &d, int device, unsigned long long *n_text_byte
 // (k_idcount.h).  n_bins: 1 .. 2^31.  accumulate on a slot of another n_bins: code 1 before anything is changed; on an empty slot it starts from 0.
 Status count_on_lane(EncoderDevice &D, EncodeLane &d, int device, const int32_t *d_ids, unsigned long long n_ids, unsigned long long n_bins, bool accumulate,
                      double *kernel_ms);
+
+// Training blocks of ids[n_ids] / off[n_sent + 1] in HBM behind the encoder's open row, into the encoder's blocks slot (D.blk; lane 0 locked by the
+// caller) on lane d's stream, which ends synchronised (k_blocks.h).  Every error is found before anything is changed: the slot and the open row
+// stay.  first_line: what the message about a sentence longer than seq_len (whole mode) adds to its index, and what it calls it.
+struct BlkParams {
+  unsigned long long L;
+  int mode;  // 0 stream, 1 whole
+  int32_t pad;
+  int tail;  // 0 pad, 1 keep, 2 drop
+};
+Status blocks_on_lane(EncoderDevice &D, EncodeLane &d, int device, const int32_t *ids, const unsigned long long *off, unsigned long long n_sent,
+                      unsigned long long n_ids, const BlkParams &p, const char *what, unsigned long long first_index, unsigned long long *n_rows,
+                      unsigned long long *n_frags, double *kernel_ms);
 
 // The vocabulary restriction of ids[n_ids] / off[n_sent + 1] in HBM on the lane (locked by the caller; a vocabulary is set): measure -> scan ->
 // write (k_restrict.h) into the lane's second pair of buffers, which then becomes the lane's encode result.  pending: the input IS that result

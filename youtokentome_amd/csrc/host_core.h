@@ -186,6 +186,24 @@ class BaseEncoder {  // bpe.h:22-82
   Status take_id_counts(void *counts, unsigned long long n_bins, bool to_device) const;  // [n_bins + 1]: to a host array or device to device
   Status encode_file_counts(const std::string &path, bool bos, bool eos, bool reverse, double dropout_prob, unsigned long long piece_bytes,
                             unsigned long long *counts, unsigned long long *n_lines, unsigned long long *n_ids, std::string *report) const;
+  // Training blocks on the device (host_decode.cpp, host_lines.cpp, k_blocks.h; the rule is in include/yttm_mi355x.h): the pending encode result, or
+  // any ids + offsets in HBM, behind the encoder's open row, packed into rows of exactly seq_len ids with segment numbers, positions and the list
+  // of fragments, in a slot of the encoder's own that only the next blocks call replaces.  What is packed is only read.  mode: 0 stream, 1 whole;
+  // tail: 0 pad, 1 keep (the incomplete row becomes the open row), 2 drop.  blocks_open: {ids in the open row, its seq_len, its mode};
+  // blocks_discard empties the open row.  take_blocks: the five arrays to host arrays or device to device, a null pointer is skipped.
+  // encode_file_blocks: the pipeline of encode_file, every piece packed with tail = keep and written to PREFIX.rows / PREFIX.frags.
+  Status blocks_device(unsigned long long n_sent, unsigned long long seq_len, int mode, int32_t pad_value, int tail, unsigned long long *n_rows,
+                       unsigned long long *n_frags, double *kernel_ms) const;
+  Status blocks_ids_device(const void *d_ids, const void *d_offsets, unsigned long long n_sent, unsigned long long n_ids, unsigned long long seq_len, int mode,
+                           int32_t pad_value, int tail, unsigned long long *n_rows, unsigned long long *n_frags, double *kernel_ms) const;
+  Status blocks_flush(int32_t pad_value, unsigned long long *n_rows, unsigned long long *n_frags, double *kernel_ms) const;
+  void blocks_open(unsigned long long out[3]) const;
+  void blocks_discard() const;
+  Status take_blocks(void *rows, void *seg, void *pos, void *frags, void *row_frags, unsigned long long n_rows, unsigned long long n_frags,
+                     bool to_device) const;
+  Status encode_file_blocks(const std::string &path, const std::string &out_prefix, bool bos, bool eos, bool reverse, double dropout_prob,
+                            unsigned long long piece_bytes, unsigned long long seq_len, int mode, int32_t pad_value, int tail, unsigned long long *n_rows,
+                            unsigned long long *n_frags, unsigned long long *n_lines, unsigned long long *n_ids, std::string *report) const;
   // Encode under a restricted vocabulary (host_encoder.cpp, k_restrict.h; the rule is in include/yttm_mi355x.h): allowed[vocab_size()] (null:
   // clears it) -> the expansion tables in HBM; from then on every encode on this encoder leaves restricted ids.  info (optional): allowed ids,
   // ids that split, the longest expansion.  vocabulary_stats: restricted calls, calls where nothing split, ids in, ids out.

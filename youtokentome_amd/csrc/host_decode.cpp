@@ -353,6 +353,207 @@ Status BaseEncoder::take_id_counts(void *counts, unsigned long long n_bins, bool
   });
 }
 
+// ---- training blocks (k_blocks.h) ----------------------------------------------------------------------------------------------------------
+// Rows of exactly L ids from the encoder's open row followed by the call's sentences, in the encoder's own slot (EncoderDevice::blk).  seg and pos
+// are kept in the slot beside the rows: the write pass has them in registers when it stores the ids, and the exits stay plain copies.
+// Order: everything that can refuse the call (the parameters, the open row's binding, a sentence longer than L, the size limit) is known before
+// the slot or the open row is touched -- the passes up to there write working arrays only.
+Status blocks_on_lane(EncoderDevice &D, EncodeLane &d, int device, const int32_t *ids, const unsigned long long *off, unsigned long long n_sent,
+                      unsigned long long n_ids, const BlkParams &p, const char *what, unsigned long long first_index, unsigned long long *n_rows_out,
+                      unsigned long long *n_frags_out, double *kernel_ms) {
+  if (n_rows_out) *n_rows_out = 0;
+  if (n_frags_out) *n_frags_out = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  auto &B = D.blk;
+  const unsigned long long L = p.L;
+  if (L < 1 || L > (1ull << 24)) return Status(1, "blocks: seq_len must be within 1 .. 2^24 (" + std::to_string(L) + ")");
+  if (p.mode != 0 && p.mode != 1) return Status(1, "blocks: mode must be 0 (stream) or 1 (whole)");
+  if (p.tail < 0 || p.tail > 2) return Status(1, "blocks: tail must be 0 (pad), 1 (keep) or 2 (drop)");
+  if (B.open_f && (B.open_L != L || B.open_mode != p.mode))
+    return Status(1, "blocks: the open row holds " + std::to_string(B.open_f) + " ids for seq_len " + std::to_string(B.open_L) + ", mode " +
+                         std::to_string(B.open_mode) + "; flush or discard it before packing with seq_len " + std::to_string(L) + ", mode " + std::to_string(p.mode));
+  if (n_sent && !off) return Status(2, "blocks: no offsets");
+  if (n_ids && !ids) return Status(2, "blocks: no ids");
+  const unsigned long long m = B.open_f ? B.open_m : 0, f = B.open_f, n = m + n_sent, total = f + n_ids;
+  if (n >= 0xfffffffeull) return Status(1, "blocks: too many sentences for one call");
+  return on_device(device, [&]() -> Status {
+    const BlkIn in{B.open_ids[B.gen], B.open_off[B.gen], m, f, ids, off, n_sent, total};
+    EventPair ev(d.st, kernel_ms != nullptr);
+    ev.start();
+    unsigned long long rows = 0, rest = 0;  // complete rows; the ids of the incomplete row behind them
+    const uint32_t *rowsent = nullptr;
+    if (total) {
+      B.cnt.grow((size_t)n);
+      B.ne.grow((size_t)n + 1);
+      B.info.grow(4);
+      launch_blk_flags(in, B.cnt, d.st);
+      (void)scan_counts(d, B.cnt, n, B.ne);  // (syncs)
+      if (p.mode == 1) {
+        const size_t nb = (size_t)((n + BLK_ORBIT - 1) / BLK_ORBIT);
+        B.nxt.grow((size_t)n);
+        B.hop.grow((size_t)n);
+        B.entry.grow(nb);
+        B.rowbase.grow(nb);
+        B.rowsent.grow((size_t)n + 1);
+        HIP_CHECK(hipMemsetAsync(B.entry, 0xff, nb * 4, d.st));
+        HIP_CHECK(hipMemsetAsync(B.info, 0, 24, d.st));
+        HIP_CHECK(hipMemsetAsync(B.info + 3, 0xff, 8, d.st));
+        launch_blk_orbit(in, L, B.nxt, B.hop, B.entry, B.rowbase, B.rowsent, B.info + 3, B.info, d.st);
+        unsigned long long info[4] = {0, 0, 0, 0};
+        HIP_CHECK(hipMemcpyAsync(info, B.info, 32, hipMemcpyDeviceToHost, d.st));
+        HIP_CHECK(hipStreamSynchronize(d.st));
+        if (info[3] != ~0ull) {  // (a sentence of the call: what the open row holds fitted a row of this L before)
+          const unsigned long long s = info[3] - m;
+          unsigned long long o2[2] = {0, 0};
+          HIP_CHECK(hipMemcpyAsync(o2, off + s, 16, hipMemcpyDeviceToHost, d.st));
+          HIP_CHECK(hipStreamSynchronize(d.st));
+          return Status(1, "seq_len is smaller than " + std::string(what) + " " + std::to_string(first_index + s) + ": whole mode places every sentence whole. Current value: seq_len = " +
+                               std::to_string(L) + "; length = " + std::to_string(o2[1] - o2[0]) + ";");
+        }
+        rows = info[0];
+        if (info[1] != L && info[1] != 0) {
+          rows--;
+          rest = info[1];
+        }
+        rowsent = B.rowsent;
+      } else {
+        rows = total / L;
+        rest = total % L;
+      }
+    }
+    const unsigned long long n_rows = rows + (rest && p.tail == 0 ? 1 : 0);
+    if (n_rows > 0x7fffffffull / L)
+      return Status(1, "blocks: " + std::to_string(n_rows) + " rows of " + std::to_string(L) + " ids exceed 2^31 - 1 elements: pack fewer sentences per call");
+    // ---- from here on the call succeeds
+    B.valid = false;
+    const size_t n_out = (size_t)(n_rows * L);
+    unsigned long long n_frags = 0;
+    if (n_rows) {
+      B.rows.grow(n_out + 4);
+      B.seg.grow(n_out + 4);
+      B.pos.grow(n_out + 4);
+      B.rowsrc.grow((size_t)n_rows + 1);
+      const Status s = two_pass_on_lane(
+          d, n_rows, B.rowcnt, B.row_frags, nullptr, &n_frags,
+          [&](bool write) {
+            if (!write) launch_blk_measure(in, B.ne, L, n_rows, rowsent, B.rowcnt, B.rowsrc, d.st);
+            else launch_blk_write(in, B.ne, L, n_rows, B.rowsrc, B.row_frags, p.pad, B.rows, B.seg, B.pos, B.frags, d.st);
+          },
+          no_check, [&](unsigned long long need) { B.frags.grow((size_t)need * 2 + 2); });
+      if (!s.ok()) return s;
+    } else {
+      B.row_frags.grow(1);
+      HIP_CHECK(hipMemsetAsync(B.row_frags, 0, 8, d.st));
+    }
+    if (rest && p.tail == 1) {  // the incomplete row into the other generation, which then is the open row
+      const int g = B.gen ^ 1;
+      B.open_ids[g].grow((size_t)rest);
+      B.open_off[g].grow((size_t)rest + 1);
+      launch_blk_keep(in, B.ne, total - rest, B.open_ids[g], B.open_off[g], B.info, d.st);
+      unsigned long long m_new = 0;
+      HIP_CHECK(hipMemcpyAsync(&m_new, B.info + 2, 8, hipMemcpyDeviceToHost, d.st));
+      HIP_CHECK(hipStreamSynchronize(d.st));
+      B.gen = g;
+      B.open_f = rest;
+      B.open_m = m_new;
+      B.open_L = L;
+      B.open_mode = p.mode;
+    } else {
+      B.open_f = B.open_m = 0;
+    }
+    ev.stop();
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    if (kernel_ms) *kernel_ms = ev.elapsed_ms();
+    B.n_rows = n_rows;
+    B.n_frags = n_frags;
+    B.L = L;
+    B.valid = true;
+    if (n_rows_out) *n_rows_out = n_rows;
+    if (n_frags_out) *n_frags_out = n_frags;
+    return Status();
+  });
+}
+
+Status BaseEncoder::blocks_device(unsigned long long n_sent, unsigned long long seq_len, int mode, int32_t pad_value, int tail, unsigned long long *n_rows,
+                                  unsigned long long *n_frags, double *kernel_ms) const {
+  if (n_rows) *n_rows = 0;
+  if (n_frags) *n_frags = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  if (!dev_) return Status(1, "blocks_device: no matching encode result");
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
+  if (!d.res.made || n_sent != d.res.n_sent) return Status(1, "blocks_device: no matching encode result");  // (before any work: the slot stays)
+  return blocks_on_lane(*dev_, d, device_, d.res.ids, d.res.off, n_sent, n_sent ? d.res.n_ids : 0, BlkParams{seq_len, mode, pad_value, tail}, "sentence", 0,
+                        n_rows, n_frags, kernel_ms);
+}
+
+Status BaseEncoder::blocks_ids_device(const void *d_ids, const void *d_offsets, unsigned long long n_sent, unsigned long long n_ids, unsigned long long seq_len,
+                                      int mode, int32_t pad_value, int tail, unsigned long long *n_rows, unsigned long long *n_frags, double *kernel_ms) const {
+  if (n_rows) *n_rows = 0;
+  if (n_frags) *n_frags = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (((uintptr_t)d_ids & 3u) != 0) return Status(2, "blocks_ids_device: the ids must be 4-byte aligned");
+  if (((uintptr_t)d_offsets & 7u) != 0) return Status(2, "blocks_ids_device: the offsets must be 8-byte aligned");
+  const Lane0 l(*dev_);
+  return blocks_on_lane(*dev_, l.d, device_, (const int32_t *)d_ids, (const unsigned long long *)d_offsets, n_sent, n_sent ? n_ids : 0,
+                        BlkParams{seq_len, mode, pad_value, tail}, "sentence", 0, n_rows, n_frags, kernel_ms);
+}
+
+// the open row as a result of 0 or 1 rows: a call without sentences under the open row's own (L, mode), its tail padded
+Status BaseEncoder::blocks_flush(int32_t pad_value, unsigned long long *n_rows, unsigned long long *n_frags, double *kernel_ms) const {
+  if (n_rows) *n_rows = 0;
+  if (n_frags) *n_frags = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  if (!dev_) return Status(2, "encoder has no device state");
+  const Lane0 l(*dev_);
+  const auto &B = dev_->blk;
+  const BlkParams p{B.open_f ? B.open_L : (B.valid && B.L ? B.L : 1), B.open_f ? B.open_mode : 0, pad_value, 0};
+  return blocks_on_lane(*dev_, l.d, device_, nullptr, nullptr, 0, 0, p, "sentence", 0, n_rows, n_frags, kernel_ms);
+}
+
+void BaseEncoder::blocks_open(unsigned long long out[3]) const {
+  out[0] = out[1] = out[2] = 0;
+  if (!dev_) return;
+  const Lane0 l(*dev_);
+  const auto &B = dev_->blk;
+  if (!B.open_f) return;
+  out[0] = B.open_f;
+  out[1] = B.open_L;
+  out[2] = (unsigned long long)B.open_mode;
+}
+
+void BaseEncoder::blocks_discard() const {
+  if (!dev_) return;
+  const Lane0 l(*dev_);
+  dev_->blk.open_f = dev_->blk.open_m = 0;
+}
+
+Status BaseEncoder::take_blocks(void *rows, void *seg, void *pos, void *frags, void *row_frags, unsigned long long n_rows, unsigned long long n_frags,
+                                bool to_device) const {
+  const char *who = to_device ? "copy_blocks: no matching blocks" : "fetch_blocks: no matching blocks";
+  if (!dev_) return Status(1, who);
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
+  const auto &B = dev_->blk;
+  if (!B.valid || n_rows != B.n_rows || n_frags != B.n_frags) return Status(1, who);
+  return on_device(device_, [&]() -> Status {
+    const size_t mat = (size_t)(B.n_rows * B.L) * 4;
+    auto take = [&](void *dst, const void *src, size_t bytes) {
+      if (!dst || !bytes) return;
+      if (to_device) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, d.st));
+      else copy_down(device_, dst, src, bytes, d.st);
+    };
+    take(rows, B.rows, mat);
+    take(seg, B.seg, mat);
+    take(pos, B.pos, mat);
+    take(frags, B.frags, (size_t)B.n_frags * 8);
+    take(row_frags, B.row_frags, ((size_t)B.n_rows + 1) * 8);
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    return Status();
+  });
+}
+
 Status BaseEncoder::subword_device(const void *d_bytes, const void *d_offsets, unsigned long long n_sent, unsigned long long total_bytes,
                                    unsigned long long max_sentence_bytes, bool bos, bool eos, bool reverse, double dropout_prob,
                                    unsigned long long *n_ids, unsigned long long *n_text_bytes, double *kernel_ms) const {

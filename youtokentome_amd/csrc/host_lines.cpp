@@ -716,4 +716,119 @@ Status BaseEncoder::decode_file(const std::string &path, const std::string &out_
                       n_text_out, report);
 }
 
+// ---- a text file to training blocks --------------------------------------------------------------------------------------------------------
+// The pipeline of encode_file_counts: piece k is split, encoded and packed (k_blocks.h) with tail = keep while piece k + 1 is read and uploaded, so
+// the rows do not depend on the cuts; behind the last piece the open row is flushed (tail = pad) or discarded (drop).  The blocks slot is the
+// encoder's one, not a lane's, so a piece's rows and fragments are written to PREFIX.rows / PREFIX.frags inside `work`, before the next piece
+// replaces them; there is no download leg.  PREFIX.frags holds uint64 (start, length) pairs, the starts flat over the whole file.
+Status BaseEncoder::encode_file_blocks(const std::string &path, const std::string &out_prefix, bool bos, bool eos, bool reverse, double dropout_prob,
+                                       unsigned long long piece_bytes, unsigned long long seq_len, int mode, int32_t pad_value, int tail,
+                                       unsigned long long *n_rows_out, unsigned long long *n_frags_out, unsigned long long *n_lines_out,
+                                       unsigned long long *n_ids_out, std::string *report) const {
+  if (n_rows_out) *n_rows_out = 0;
+  if (n_frags_out) *n_frags_out = 0;
+  if (n_lines_out) *n_lines_out = 0;
+  if (n_ids_out) *n_ids_out = 0;
+  const Status tokens = check_bos_eos(*this, bos, eos);
+  if (!tokens.ok()) return tokens;
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (seq_len < 1 || seq_len > (1ull << 24)) return Status(1, "blocks: seq_len must be within 1 .. 2^24 (" + std::to_string(seq_len) + ")");
+  if (mode != 0 && mode != 1) return Status(1, "blocks: mode must be 0 (stream) or 1 (whole)");
+  if (tail != 0 && tail != 2) return Status(1, "encode_file_blocks: tail must be 0 (pad) or 2 (drop)");
+  if (out_prefix.empty()) return Status(1, "Failed to open file for writing: no output prefix");
+  FilePieces fp(path, dev_, device_, piece_bytes);
+  const Status opened = fp.open_input();
+  if (!opened.ok()) return opened;
+  const std::string rows_path = out_prefix + ".rows", frags_path = out_prefix + ".frags";
+  Fd out_rows, out_frags;
+  out_rows.fd = open(rows_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+  if (out_rows.fd < 0) return Status(1, "Failed to open file for writing: " + rows_path + " (" + strerror(errno) + ")");
+  out_frags.fd = open(frags_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+  if (out_frags.fd < 0) return Status(1, "Failed to open file for writing: " + frags_path + " (" + strerror(errno) + ")");
+  const std::shared_ptr<const Config> C = dev_->cfg;
+  const CfgBind bind(C);
+  const int device = device_;
+  EncoderDevice *dev = dev_;
+  std::lock_guard<std::mutex> lk0(dev->lane[0].mu), lk1(dev->lane[1].mu);  // (lane 0 first, always: nobody else waits for two lanes)
+  dev->blk.open_f = dev->blk.open_m = 0;  // the file starts from an empty open row
+
+  double s_split = 0, s_enc = 0, s_blocks = 0, s_down = 0;
+  unsigned long long lines_total = 0, ids_total = 0, rows_total = 0, frags_total = 0;
+  // the slot's rows and fragments behind what the file holds so far
+  auto write_slot = [&](unsigned long long nr, unsigned long long nf) -> Status {
+    const auto t0 = std::chrono::steady_clock::now();
+    const unsigned long long flat_base = rows_total * seq_len;
+    std::atomic<bool> write_ok{true};
+    try {
+      if (nr)
+        staged_transfer(device, (uint8_t *)dev->blk.rows.p, nr * seq_len * 4, false, [&](void *chunk, unsigned long long o, size_t len) {
+          if (!pwrite_all(out_rows.fd, chunk, len, flat_base * 4 + o)) { write_ok.store(false); return false; }
+          return true;
+        }, nullptr, ENC_CHUNK);
+      if (nf)
+        staged_transfer(device, (uint8_t *)dev->blk.frags.p, nf * 8, false, [&](void *chunk, unsigned long long o, size_t len) {
+          const int32_t *v = (const int32_t *)chunk;
+          std::vector<unsigned long long> wide(len / 4);
+          for (size_t j = 0; j < len / 8; j++) {
+            wide[2 * j] = flat_base + (unsigned long long)(uint32_t)v[2 * j];
+            wide[2 * j + 1] = (unsigned long long)(uint32_t)v[2 * j + 1];
+          }
+          if (!pwrite_all(out_frags.fd, wide.data(), wide.size() * 8, frags_total * 16 + o * 2)) { write_ok.store(false); return false; }
+          return true;
+        }, nullptr, ENC_CHUNK);
+    } catch (const GpuError &) {
+      if (!write_ok.load()) return Status(1, "Failed to write file: " + out_prefix + ".rows / .frags");
+      throw;
+    }
+    rows_total += nr;
+    frags_total += nf;
+    s_down += secs_since(t0);
+    return Status();
+  };
+  auto upload = [&](size_t i, bool *exhausted) { return fp.upload(i, exhausted); };
+  auto work = [&](size_t i) {
+    FilePieces::Piece &p = fp.piece[i & 1];
+    EncodeLane &d = dev->lane[i & 1];
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned long long nr = 0, nf = 0;
+    Status st = encode_text_on_lane(*this, *dev, d, device, d.in.bytes, p.bytes, bos, eos, reverse, dropout_prob, &p.n_lines, &p.n_ids, &p.ms_split, nullptr);
+    if (st.ok())
+      st = blocks_on_lane(*dev, d, device, d.res.ids, d.res.off, p.n_lines, p.n_lines ? p.n_ids : 0, BlkParams{seq_len, mode, pad_value, 1}, "line", lines_total + 1,
+                          &nr, &nf, &p.ms_a);
+    s_split += p.ms_split * 1e-3;
+    s_blocks += p.ms_a * 1e-3;
+    s_enc += secs_since(t0) - (p.ms_split + p.ms_a) * 1e-3;
+    if (st.ok()) st = on_device(device, [&]() -> Status { return write_slot(nr, nf); });
+    lines_total += p.n_lines;
+    ids_total += p.n_ids;
+    return st;
+  };
+  auto download = [&](size_t) { return Status(); };
+  size_t n_pieces = 0;
+  Status piped = run_two_lanes("encode_file_blocks", C, device, PIPE_UNTIL_EXHAUSTED, upload, work, download, &n_pieces);
+  if (piped.ok() && tail == 0) {
+    unsigned long long nr = 0, nf = 0;
+    double ms = 0;
+    const BlkParams flush{dev->blk.open_f ? dev->blk.open_L : seq_len, dev->blk.open_f ? dev->blk.open_mode : mode, pad_value, 0};
+    piped = blocks_on_lane(*dev, dev->lane[0], device, nullptr, nullptr, 0, 0, flush, "line", 0, &nr, &nf, &ms);
+    s_blocks += ms * 1e-3;
+    if (piped.ok()) piped = on_device(device, [&]() -> Status { return write_slot(nr, nf); });
+  }
+  dev->blk.open_f = dev->blk.open_m = 0;  // (drop, or a call that failed on its way: the open row is empty afterwards)
+  if (!piped.ok()) return piped;
+  const int fd_a = out_rows.fd, fd_b = out_frags.fd;
+  out_rows.fd = out_frags.fd = -1;
+  const bool ok_a = close(fd_a) == 0, ok_b = close(fd_b) == 0;
+  if (!ok_a || !ok_b) return Status(1, "Failed to write file: " + (ok_a ? frags_path : rows_path));
+  if (n_rows_out) *n_rows_out = rows_total;
+  if (n_frags_out) *n_frags_out = frags_total;
+  if (n_lines_out) *n_lines_out = lines_total;
+  if (n_ids_out) *n_ids_out = ids_total;
+  if (report) {
+    const std::string r = fp.report(n_pieces, lines_total, ids_total, nullptr, s_split, s_enc, {{"seconds_blocks", s_blocks}}, s_down);
+    *report = "{\"rows\": " + std::to_string(rows_total) + ", \"frags\": " + std::to_string(frags_total) + ", " + r.substr(1);
+  }
+  return Status();
+}
+
 }  // namespace yttm

@@ -475,4 +475,36 @@ struct RestrictTable {
 void launch_restrict(bool write, const int32_t *ids, const unsigned long long *off, unsigned long long n_sent, unsigned long long n_ids,
                      const RestrictTable &tb, uint32_t *out_len, const unsigned long long *out_off, int32_t *out, hipStream_t st);
 
+// ---- training blocks (k_blocks.h, compiled with k_encode.hip): flags -> scan -> (whole: orbit) -> measure -> scan -> write (-> keep) ----
+// The sequence a call packs: the open row's m sentences (f ids, open_off[m + 1]) followed by the call's S sentences (off[S + 1], off[0] = 0), as one
+// stream of `total` = f + K ids in which sentence i starts at voff(i).  Only read.
+struct BlkIn {
+  const int32_t *open_ids;
+  const unsigned long long *open_off;
+  unsigned long long m, f;
+  const int32_t *ids;
+  const unsigned long long *off;
+  unsigned long long S, total;
+  __host__ __device__ unsigned long long n() const { return m + S; }
+  __host__ __device__ unsigned long long voff(unsigned long long i) const { return i < m ? open_off[i] : i >= m + S ? total : f + off[i - m]; }
+  __host__ __device__ int32_t id(unsigned long long p) const { return p < f ? open_ids[p] : ids[p - f]; }
+};
+constexpr unsigned int BLK_ORBIT = 1024;        // sentences a workgroup of the orbit pass resolves
+constexpr uint32_t BLK_NONE = 0xffffffffu;      // entry[] of a block of sentences the orbit does not visit
+// cnt[n] = 1 per non-empty sentence (its exclusive scan is `ne` below, [n + 1]); n = in.n() < 2^32 - 1
+void launch_blk_flags(const BlkIn &in, uint32_t *cnt, hipStream_t st);
+// whole mode's rows: nxt[n], hop[n], entry / rowbase[ceil(n / BLK_ORBIT)] (entry holds BLK_NONE before), rowsent[rows + 1] (at most n + 1), *bad (holds ~0
+// before) = the smallest index of a sentence longer than L, info[0] = the rows of the orbit, info[1] = the ids of its last row.  n >= 1.
+void launch_blk_orbit(const BlkIn &in, unsigned long long L, uint32_t *nxt, unsigned long long *hop, uint32_t *entry, uint32_t *rowbase, uint32_t *rowsent,
+                      unsigned long long *bad, unsigned long long *info, hipStream_t st);
+// rowsrc[n_rows + 1] and cnt[n_rows], the fragments per row; rowsent == nullptr: stream mode
+void launch_blk_measure(const BlkIn &in, const unsigned long long *ne, unsigned long long L, unsigned long long n_rows, const uint32_t *rowsent, uint32_t *cnt,
+                        unsigned long long *rowsrc, hipStream_t st);
+// rows / seg / pos: 16-byte aligned, n_rows * L elements rounded up to a multiple of 4; frags: 8-byte aligned; 1 <= n_rows * L < 2^31
+void launch_blk_write(const BlkIn &in, const unsigned long long *ne, unsigned long long L, unsigned long long n_rows, const unsigned long long *rowsrc,
+                      const unsigned long long *row_frags, int32_t pad, int32_t *rows, int32_t *seg, int32_t *pos, int32_t *frags, hipStream_t st);
+// the stream from p0 < total on as the next open row: new_ids[total - p0], new_off[m' + 1], info[2] = m'
+void launch_blk_keep(const BlkIn &in, const unsigned long long *ne, unsigned long long p0, int32_t *new_ids, unsigned long long *new_off,
+                     unsigned long long *info, hipStream_t st);
+
 }  // namespace yttm

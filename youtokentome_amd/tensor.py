@@ -1,5 +1,5 @@
 """Device tensors in, device tensors out: `BPE.encode_tensor` / `BPE.encode_text_tensor` / `BPE.text_lines_tensor` / `BPE.decode_tensor` /
-`BPE.encode_subword_tensor` / `BPE.encode_text_subword_tensor` / `BPE.encode_spans_tensor` / `BPE.encode_text_spans_tensor` / `BPE.decode_text_tensor` / `BPE.parse_ids_tensor` / `BPE.id_counts_tensor` on top
+`BPE.encode_subword_tensor` / `BPE.encode_text_subword_tensor` / `BPE.encode_spans_tensor` / `BPE.encode_text_spans_tensor` / `BPE.decode_text_tensor` / `BPE.parse_ids_tensor` / `BPE.id_counts_tensor` / `BPE.*blocks*_tensor` on top
 of the raw device layer of `bpe._Core` (include/yttm_mi355x.h: yttm_encode_device, yttm_encode_text_device, yttm_lines_*, yttm_encode_copy_*,
 yttm_decode_device*, yttm_decode_copy_device).  torch is imported at call
 time; the rest of the package does not need it.
@@ -7,6 +7,8 @@ time; the rest of the package does not need it.
 The library works on a non-blocking stream of its own and returns after that stream has synchronised.  So the hand-over is: synchronise
 torch's current stream (whatever produced the input tensors is done), call the library, and let it fill output tensors that torch
 allocated -- torch owns all memory it sees."""
+import collections
+
 import numpy as np
 
 from .bpe import _check_dropout
@@ -353,3 +355,110 @@ def id_counts_tensor(bpe, ids=None, n_bins=None, accumulate=False):
     counts = torch.empty(n_bins + 1, dtype=torch.int64, device=dev)
     _synced(torch, dev, core.copy_id_counts_device, counts.data_ptr(), n_bins)
     return counts
+
+
+# ---- training blocks (include/yttm_mi355x.h "Training blocks") ---------------------------------------------------------------------------------
+Blocks = collections.namedtuple("Blocks", "rows seg pos frags row_frags")
+
+
+def _blocks_args(bpe, seq_len, mode, pad_id, tail):
+    core = bpe.bpe_cython
+    if mode not in core.MODES:
+        raise ValueError('mode must be "stream" or "whole"')
+    if tail not in core.TAILS:
+        raise ValueError('tail must be "pad", "keep" or "drop"')
+    if int(seq_len) < 1:
+        raise ValueError("seq_len must be positive")
+    pad_id = _pad_id(bpe, tail == "pad", pad_id)
+    return int(seq_len), core.MODES[mode], 0 if pad_id is None else int(pad_id), core.TAILS[tail]
+
+
+def _take_blocks(torch, core, dev, n_rows, n_frags, seq_len):
+    """the blocks slot as tensors that torch owns"""
+    rows, seg, pos = (torch.empty((n_rows, seq_len), dtype=torch.int32, device=dev) for _ in range(3))
+    frags = torch.empty((n_frags, 2), dtype=torch.int32, device=dev)
+    row_frags = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
+    _synced(torch, dev, core.copy_blocks_device, rows.data_ptr(), seg.data_ptr(), pos.data_ptr(), frags.data_ptr(), row_frags.data_ptr(), n_rows, n_frags)
+    return Blocks(rows, seg, pos, frags, row_frags)
+
+
+def encode_blocks_tensor(bpe, sentences, seq_len, mode="stream", bos=False, eos=False, reverse=False, dropout_prob=0, pad_id=None, tail="pad", device=None):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, device)
+    _check_dropout(dropout_prob)
+    L, m, pad, t = _blocks_args(bpe, seq_len, mode, pad_id, tail)
+    d_bytes, d_off, n, total, longest_in = _sentences_on(torch, sentences, dev)
+    _synced(torch, dev, core.encode_device_raw, d_bytes.data_ptr(), d_off.data_ptr(), n, total, longest_in, bos, eos, reverse, dropout_prob)
+    core.pending_n_sent = n
+    n_rows, n_frags, _ = core.blocks_device_raw(n, L, m, pad, t)
+    return _take_blocks(torch, core, dev, n_rows, n_frags, L)
+
+
+def encode_text_blocks_tensor(bpe, text, seq_len, mode="stream", bos=False, eos=False, reverse=False, dropout_prob=0, pad_id=None, tail="pad"):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    _check_dropout(dropout_prob)
+    L, m, pad, t = _blocks_args(bpe, seq_len, mode, pad_id, tail)
+    d_text, n_bytes = _text_on(torch, text, dev)
+    n, _, _ = _synced(torch, dev, core.encode_text_device_raw, d_text.data_ptr(), n_bytes, bos, eos, reverse, dropout_prob)
+    core.pending_n_sent = n
+    n_rows, n_frags, _ = core.blocks_device_raw(n, L, m, pad, t)
+    return _take_blocks(torch, core, dev, n_rows, n_frags, L)
+
+
+def blocks_tensor(bpe, ids=None, lengths=None, offsets=None, seq_len=0, mode="stream", pad_id=None, tail="pad"):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    L, m, pad, t = _blocks_args(bpe, seq_len, mode, pad_id, tail)
+    if ids is None:
+        n = getattr(core, "pending_n_sent", None)
+        if n is None:
+            raise ValueError("blocks_tensor: no *_tensor encode or parse call has left a result to pack")
+        n_rows, n_frags, _ = _synced(torch, dev, core.blocks_device_raw, n, L, m, pad, t)
+        return _take_blocks(torch, core, dev, n_rows, n_frags, L)
+    if not hasattr(ids, "data_ptr") or ids.dtype != torch.int32:
+        raise ValueError("ids must be an int32 tensor")
+    _check_on(ids, dev, "ids")
+    if ids.dim() == 2:
+        if offsets is not None:
+            raise ValueError("offsets go with 1-D ids; a 2-D matrix takes lengths")
+        n, w = ids.shape
+        if lengths is None:
+            lens = torch.full((n,), w, dtype=torch.int64, device=dev)
+        else:
+            _check_on(lengths, dev, "lengths")
+            if lengths.dim() != 1 or lengths.numel() != n:
+                raise ValueError("lengths must have one entry per row")
+            lens = lengths.to(torch.int64).clamp(0, w)
+        keep = torch.arange(w, device=dev).unsqueeze(0) < lens.unsqueeze(1)  # the rows' ids back to back (the library's pass takes the ragged form)
+        ids = ids[keep].contiguous()
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(lens, 0, out=offsets[1:])
+    elif ids.dim() == 1:
+        if offsets is None or lengths is not None:
+            raise ValueError("1-D ids take offsets [n + 1] (and no lengths)")
+        offsets = _offsets_u64(torch, offsets, dev)
+        ids = ids.contiguous()
+        n = offsets.numel() - 1
+        if n < 0:
+            raise ValueError("offsets must have at least one entry")
+        if n and (int(offsets[-1]) > ids.numel() or int(offsets[0]) != 0 or bool((offsets[1:] < offsets[:-1]).any())):
+            raise ValueError("offsets must start at 0, be non-decreasing and end inside ids")
+    else:
+        raise ValueError("ids must be 1-D (with offsets) or 2-D (padded)")
+    n_in = int(offsets[-1]) if n else 0
+    n_rows, n_frags, _ = _synced(torch, dev, core.blocks_ids_device_raw, ids.data_ptr(), offsets.data_ptr(), n, n_in, L, m, pad, t)
+    return _take_blocks(torch, core, dev, n_rows, n_frags, L)
+
+
+def blocks_flush_tensor(bpe, pad_id=None):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    f, L, _ = core.blocks_open()
+    pad_id = _pad_id(bpe, f > 0, pad_id)
+    n_rows, n_frags, _ = _synced(torch, dev, core.blocks_flush_raw, 0 if pad_id is None else int(pad_id))
+    return _take_blocks(torch, core, dev, n_rows, n_frags, L if n_rows else max(L, 1))

@@ -171,6 +171,32 @@ def count_file(model, input_path, output, bos, eos, dropout_prob, vocabulary, vo
             f.write(text)
 
 
+@main.command(name="blocks_file")
+@click.option("--model", type=click.Path(exists=True), required=True, help="Path to file with learned model.")
+@click.option("--input", "input_path", type=click.Path(exists=True, dir_okay=False), required=True, help="Text file, one sentence per line.")
+@click.option("--output", type=click.Path(), required=True, help="Prefix of the files to write: PREFIX.rows (int32 [rows, seq_len]) and PREFIX.frags (uint64 [frags, 2]).")
+@click.option("--seq_len", type=click.INT, required=True, help="Ids per row.")
+@click.option("--mode", type=click.Choice(["stream", "whole"]), default="stream", show_default=True,
+              help="stream: concatenate the sentences and cut every seq_len ids; whole: place sentences whole, several to a row.")
+@click.option("--bos", is_flag=True, help="Add tab begin of sentence.")
+@click.option("--eos", is_flag=True, help="Add tab end of sentence.")
+@click.option("--reverse", is_flag=True, help="Reverse output sequence of tokens.")
+@click.option("--dropout_prob", type=click.FLOAT, default=0, show_default=True,
+              help="BPE-dropout probability (the probability of a merge being dropped)")
+@click.option("--drop_last", is_flag=True, help="Discard the incomplete last row instead of padding it with <PAD>.")
+@_vocabulary_options
+def blocks_file(model, input_path, output, seq_len, mode, bos, eos, reverse, dropout_prob, drop_last, vocabulary, vocabulary_threshold):
+    """Encode a text file and pack it into fixed-length training rows."""
+    core = _Core(model)
+    _set_vocabulary(core, vocabulary, vocabulary_threshold)
+    pad = core.subword_to_id("<PAD>")
+    if not drop_last and (pad == -1 or core.id_to_subword(pad) != "<PAD>"):
+        raise click.UsageError("the model was trained without <PAD>: use --drop_last")
+    # the C++ pipeline: yttm_encode_file_blocks (host_lines.cpp)
+    core.encode_file_blocks(input_path, output, seq_len, core.MODES[mode], bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, pad_value=pad,
+                            tail=2 if drop_last else 0)
+
+
 @main.command()
 @click.option("--model", type=click.Path(exists=True), required=True, help="Path to file with learned model.")
 @click.option("--verbose", is_flag=True, help="Add merging rules.")
