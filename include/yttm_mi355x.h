@@ -294,6 +294,55 @@ int yttm_encode_file_blocks(yttm_encoder *enc, const char *path, const char *out
                             uint64_t chunk_bytes, uint64_t seq_len, int mode, int32_t pad_value, int tail, uint64_t *n_rows, uint64_t *n_frags,
                             uint64_t *n_lines, uint64_t *n_ids, char *report_json, int report_len, char *err, int errlen);
 
+/* Batches by length under a token budget: sentences sorted by length and cut into batches, each a padded matrix as narrow as its longest
+ * sentence (fairseq's --max-tokens / --max-sentences, OpenNMT's batch_type tokens; the reference has no counterpart).
+ * Input: n sentences with lengths l(0) .. l(n - 1) >= 0; n < 2^32 - 2, as for the training blocks.
+ * Parameters: max_tokens T, 1 .. 2^31 - 1; max_sentences M, 0 = no limit, else 1 .. 2^31 - 1; min_len >= 0; max_len, 0 = none.  Anything outside
+ * those ranges: code 1, and nothing is changed.
+ * Kept and left out: sentence i is kept iff min_len <= l(i) and (max_len == 0 or l(i) <= max_len).  Every other sentence is left out and appears
+ * in no batch.  A kept sentence with l(i) > T fits no batch: code 1, the message naming the smallest such i and its length; the slot, the pending
+ * result and any earlier plan are unchanged.  (A negative length -- yttm_batches_plan_lengths_device -- is refused the same way; of the sentences
+ * the rule refuses for either reason the message names the one of the smallest index.)
+ * Order: uint32 order[n] holds the kept sentences by (l, i) ascending -- a stable sort by length --, then the left-out ones by i ascending.
+ * n_kept is returned.
+ * Batches: ranges of positions of order[0 .. n_kept).  A batch that starts at position a ends at the largest b <= n_kept with both
+ *   b - a <= M (when M != 0)   and   (b - a) * l(order[b - 1]) <= T.
+ * The order ascends, so the last sentence of a batch is its longest and the product its padded size; b >= a + 1 always holds.  The next batch
+ * starts at b.  uint64 batch_first[n_batches + 1], the last entry = n_kept; n_kept == 0 gives n_batches == 0.
+ * Consequences: every batch is within both limits; every batch but the last is maximal (its next sentence would break a limit); a batch of
+ * empty sentences has width 0 and is bounded by M alone.
+ * Gather: the batches of one side -- int32 ids[K] + uint64 offsets[n + 1] with the plan's n: the planned side, or another one with lengths of
+ * its own:
+ *   uint32 widths[n_batches]          the largest length of this side among the batch's sentences
+ *   uint64 batch_off[n_batches + 1]   the exclusive sum of rows_b * widths_b
+ *   int32  out[batch_off[n_batches]]  batch b as a row-major matrix [rows_b][widths_b] at batch_off[b]; row k is sentence
+ *                                     order[batch_first[b] + k], its ids at the left with pad_value behind them -- with left_pad != 0 at the right
+ *                                     with pad_value in front
+ * More than 2^31 - 1 elements: code 1, and nothing is changed.
+ * Two sides: plan with lengths = max(len_src, len_tgt) (yttm_batches_plan_lengths_device) and gather each side with that plan; the budget then
+ * holds for the wider side of every batch.
+ *
+ * yttm_batches_plan_device plans from the offsets of the pending encode result, whichever call left it (n_sent must be its); the result stays
+ * pending and unchanged.  yttm_batches_plan_lengths_device: from int32 d_lengths[n_sent] in HBM (4-byte aligned; the caller synchronises the
+ * stream that wrote them first).  yttm_batches_gather_device gathers the pending result, yttm_batches_gather_ids_device int32 d_ids[n_ids] + uint64
+ * d_offsets[n_sent + 1] in HBM (offsets[0] = 0; 4-byte aligned ids, 8-byte aligned offsets, the conventions of yttm_blocks_ids_device).  Both
+ * return code 1 where there is no plan or n_sent is not the plan's.  kernel_ms (optional) = HIP-event time of all passes.
+ * The plan and the gathered arrays live in a slot of the encoder's own: no encode, decode, parse, count, blocks or file call empties it; a plan
+ * call replaces the plan and empties the gathered part; a gather replaces the gathered part only.
+ * yttm_batches_fetch / yttm_batches_copy_device: the five arrays to host memory / to device memory the caller owns; any null pointer is skipped;
+ * n_sent, n_batches and n_elems must be the slot's (n_elems = 0 and no widths, batch_off or out while nothing is gathered), else code 1. */
+int yttm_batches_plan_device(yttm_encoder *enc, uint64_t n_sent, uint64_t max_tokens, uint64_t max_sentences, uint64_t min_len, uint64_t max_len,
+                             uint64_t *n_kept, uint64_t *n_batches, double *kernel_ms, char *err, int errlen);
+int yttm_batches_plan_lengths_device(yttm_encoder *enc, const void *d_lengths, uint64_t n_sent, uint64_t max_tokens, uint64_t max_sentences, uint64_t min_len,
+                                     uint64_t max_len, uint64_t *n_kept, uint64_t *n_batches, double *kernel_ms, char *err, int errlen);
+int yttm_batches_gather_device(yttm_encoder *enc, uint64_t n_sent, int32_t pad_value, int left_pad, uint64_t *n_elems, double *kernel_ms, char *err, int errlen);
+int yttm_batches_gather_ids_device(yttm_encoder *enc, const void *d_ids, const void *d_offsets, uint64_t n_sent, uint64_t n_ids, int32_t pad_value, int left_pad,
+                                   uint64_t *n_elems, double *kernel_ms, char *err, int errlen);
+int yttm_batches_fetch(yttm_encoder *enc, uint32_t *order, uint64_t *batch_first, uint32_t *widths, uint64_t *batch_off, int32_t *out, uint64_t n_sent,
+                       uint64_t n_batches, uint64_t n_elems, char *err, int errlen);
+int yttm_batches_copy_device(yttm_encoder *enc, void *d_order, void *d_batch_first, void *d_widths, void *d_batch_off, void *d_out, uint64_t n_sent,
+                             uint64_t n_batches, uint64_t n_elems, char *err, int errlen);
+
 /* Encode under a restricted vocabulary (subword-nmt's --vocabulary / --vocabulary-threshold, SentencePiece's SetVocabulary; the reference has no
  * counterpart).  A model has rules (x, y, z) with distinct z, as written in the model file behind the char section.  Let V = yttm_vocab_size(enc)
  * and A, a subset of [0, V), the allowed set.  The expansion E(v) of an id:

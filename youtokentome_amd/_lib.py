@@ -31,6 +31,8 @@ EXPORTS = [
     "yttm_encoder_set_vocabulary", "yttm_encoder_vocabulary_stats", "yttm_restrict_ids_device",
     "yttm_blocks_device", "yttm_blocks_ids_device", "yttm_blocks_flush", "yttm_blocks_open", "yttm_blocks_discard", "yttm_blocks_fetch", "yttm_blocks_copy_device",
     "yttm_encode_file_blocks",
+    "yttm_batches_plan_device", "yttm_batches_plan_lengths_device", "yttm_batches_gather_device", "yttm_batches_gather_ids_device", "yttm_batches_fetch",
+    "yttm_batches_copy_device",
     "yttm_device_info", "yttm_comm_rccl_unique_id", "yttm_comm_rccl_create", "yttm_comm_callback_create",
     "yttm_comm_destroy", "yttm_train_bpe_comm", "yttm_train_bpe_from_device_comm", "yttm_train_bpe_from_memory_comm",
     # include/yttm_gpu.h
@@ -108,6 +110,12 @@ def load():
     L.yttm_blocks_fetch.argtypes = [cvp, i32p, i32p, i32p, i32p, u64p, C.c_uint64, C.c_uint64, cs, ci]
     L.yttm_blocks_copy_device.argtypes = [cvp, cvp, cvp, cvp, cvp, cvp, C.c_uint64, C.c_uint64, cs, ci]
     L.yttm_encode_file_blocks.argtypes = [cvp, cs, cs, ci, ci, ci, cd, C.c_uint64, C.c_uint64, ci, C.c_int32, ci, u64p, u64p, u64p, u64p, cs, ci, cs, ci]
+    L.yttm_batches_plan_device.argtypes = [cvp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, u64p, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_batches_plan_lengths_device.argtypes = [cvp, cvp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, u64p, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_batches_gather_device.argtypes = [cvp, C.c_uint64, C.c_int32, ci, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_batches_gather_ids_device.argtypes = [cvp, cvp, cvp, C.c_uint64, C.c_uint64, C.c_int32, ci, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_batches_fetch.argtypes = [cvp, cvp, cvp, cvp, cvp, cvp, C.c_uint64, C.c_uint64, C.c_uint64, cs, ci]
+    L.yttm_batches_copy_device.argtypes = [cvp, cvp, cvp, cvp, cvp, cvp, C.c_uint64, C.c_uint64, C.c_uint64, cs, ci]
     L.yttm_encoder_set_cache.argtypes = [cvp, ci, C.c_uint64]
     L.yttm_encode_cache_words.argtypes = [cvp]
     L.yttm_encode_cache_words.restype = C.c_uint64

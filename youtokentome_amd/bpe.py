@@ -452,6 +452,54 @@ class _Core:
             return json.loads(rep.value.decode())
         return nr.value, nf.value, nl.value, ni.value
 
+    # ---- batches by length under a token budget (include/yttm_mi355x.h "Batches by length"): the plan and the gathered batches in a slot of the encoder's own
+    def batches_plan_device_raw(self, n_sent, max_tokens, max_sentences=0, min_len=0, max_len=0):
+        """plans from the pending encode result of n_sent sentences -> (n_kept, n_batches, kernel_ms); the result stays pending"""
+        nk, nb, ms, err = C.c_uint64(), C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_batches_plan_device(self._h, n_sent, int(max_tokens), int(max_sentences), int(min_len), int(max_len), C.byref(nk), C.byref(nb),
+                                                         C.byref(ms), err, _lib.ERRLEN), err)
+        self.batches_last_plan = (n_sent, nk.value, nb.value)  # (the tensor layer sizes a later gather's tensors from it)
+        return nk.value, nb.value, ms.value
+
+    def batches_plan_lengths_device_raw(self, d_lengths, n_sent, max_tokens, max_sentences=0, min_len=0, max_len=0):
+        """plans from int32 lengths[n_sent] in device memory -> (n_kept, n_batches, kernel_ms)"""
+        nk, nb, ms, err = C.c_uint64(), C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_batches_plan_lengths_device(self._h, C.c_void_p(d_lengths), n_sent, int(max_tokens), int(max_sentences), int(min_len),
+                                                                 int(max_len), C.byref(nk), C.byref(nb), C.byref(ms), err, _lib.ERRLEN), err)
+        self.batches_last_plan = (n_sent, nk.value, nb.value)
+        return nk.value, nb.value, ms.value
+
+    def batches_gather_device_raw(self, n_sent, pad_value=0, left_pad=False):
+        """the planned batches of the pending encode result -> (n_elems, kernel_ms)"""
+        ne, ms, err = C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_batches_gather_device(self._h, n_sent, int(pad_value), int(bool(left_pad)), C.byref(ne), C.byref(ms), err, _lib.ERRLEN), err)
+        return ne.value, ms.value
+
+    def batches_gather_ids_device_raw(self, d_ids, d_offsets, n_sent, n_ids, pad_value=0, left_pad=False):
+        """the planned batches of int32 ids[n_ids] + uint64 offsets[n_sent + 1] in device memory -> (n_elems, kernel_ms)"""
+        ne, ms, err = C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_batches_gather_ids_device(self._h, C.c_void_p(d_ids), C.c_void_p(d_offsets), n_sent, n_ids, int(pad_value), int(bool(left_pad)),
+                                                               C.byref(ne), C.byref(ms), err, _lib.ERRLEN), err)
+        return ne.value, ms.value
+
+    def fetch_batches(self, n_sent, n_batches, n_elems=None):
+        """the batches slot -> (order uint32 [n_sent], batch_first uint64 [n_batches + 1]) and, with n_elems (a gather has run), widths uint32
+        [n_batches], batch_off uint64 [n_batches + 1], out int32 [n_elems]"""
+        order, first, err = np.zeros(n_sent, np.uint32), np.zeros(n_batches + 1, np.uint64), _err()
+        if n_elems is None:
+            self._check(_lib.load().yttm_batches_fetch(self._h, order.ctypes.data, first.ctypes.data, None, None, None, n_sent, n_batches, 0, err,
+                                                       _lib.ERRLEN), err)
+            return order, first
+        widths, off, out = np.zeros(n_batches, np.uint32), np.zeros(n_batches + 1, np.uint64), np.zeros(n_elems, np.int32)
+        self._check(_lib.load().yttm_batches_fetch(self._h, order.ctypes.data, first.ctypes.data, widths.ctypes.data, off.ctypes.data, out.ctypes.data,
+                                                   n_sent, n_batches, n_elems, err, _lib.ERRLEN), err)
+        return order, first, widths, off, out
+
+    def copy_batches_device(self, d_order, d_batch_first, d_widths, d_batch_off, d_out, n_sent, n_batches, n_elems):
+        err = _err()
+        self._check(_lib.load().yttm_batches_copy_device(self._h, C.c_void_p(d_order), C.c_void_p(d_batch_first), C.c_void_p(d_widths), C.c_void_p(d_batch_off),
+                                                         C.c_void_p(d_out), n_sent, n_batches, n_elems, err, _lib.ERRLEN), err)
+
     # ---- decimal id text on the device (include/yttm_mi355x.h): the format `yttm encode --output_type id` prints and `yttm decode` reads
     def ids_parse_device_raw(self, d_text, n_bytes):
         """-> (n_lines, n_ids, kernel_ms); the ids `while (ss >> x)` reads from every line are pending as after encode_device_raw with n_sent = n_lines"""
@@ -809,6 +857,37 @@ class BPE:
                 raise ValueError("the model was trained without <PAD> (pad_id=-1): pass pad_id")
         return core.encode_file_blocks(path, out, seq_len, core.MODES[mode], bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob, pad_value=pad_id,
                                        tail=2 if drop_last else 0, chunk_bytes=chunk_bytes, report=report)
+
+    # ---- sentences sorted by length and cut into batches under a token budget (include/yttm_mi355x.h "Batches by length"; the reference has no counterpart)
+    def encode_batches_tensor(self, sentences, max_tokens: int, max_sentences: int = 0, min_len: int = 0, max_len: int = 0, left_pad: bool = False,
+                              bos: bool = False, eos: bool = False, reverse: bool = False, dropout_prob: float = 0, pad_id: Optional[int] = None, device=None):
+        """encode_tensor's sentences sorted by length on the device and cut into batches of at most max_tokens padded ids (and max_sentences rows;
+        0: no limit) -> Batches(order, batch_first, widths, batch_off, ids, n_kept), tensors on the encoder's device.  len(b) is the number of
+        batches, b[k] = (sentence indices [rows], matrix [rows, width]): the matrix is a view of b.ids, its rows padded with pad_id (default: the
+        model's <PAD>) on the right, with left_pad on the left.  Sentences shorter than min_len or longer than max_len (0: none) are left out; a
+        kept sentence longer than max_tokens raises.  Two sides: plan with batches_plan_tensor(torch.maximum(len_src, len_tgt), ...) and
+        gather each side with batches_gather_tensor."""
+        from . import tensor
+        return tensor.encode_batches_tensor(self, sentences, max_tokens, max_sentences=max_sentences, min_len=min_len, max_len=max_len, left_pad=left_pad, bos=bos,
+                                            eos=eos, reverse=reverse, dropout_prob=dropout_prob, pad_id=pad_id, device=device)
+
+    def encode_text_batches_tensor(self, text, max_tokens: int, max_sentences: int = 0, min_len: int = 0, max_len: int = 0, left_pad: bool = False,
+                                   bos: bool = False, eos: bool = False, reverse: bool = False, dropout_prob: float = 0, pad_id: Optional[int] = None):
+        """the same for `text` as encode_text_tensor takes it, one sentence per line"""
+        from . import tensor
+        return tensor.encode_text_batches_tensor(self, text, max_tokens, max_sentences=max_sentences, min_len=min_len, max_len=max_len, left_pad=left_pad, bos=bos,
+                                                 eos=eos, reverse=reverse, dropout_prob=dropout_prob, pad_id=pad_id)
+
+    def batches_plan_tensor(self, lengths, max_tokens: int, max_sentences: int = 0, min_len: int = 0, max_len: int = 0):
+        """the plan alone from an int32 tensor of lengths on the encoder's device -> Batches whose widths, batch_off and ids are None"""
+        from . import tensor
+        return tensor.batches_plan_tensor(self, lengths, max_tokens, max_sentences=max_sentences, min_len=min_len, max_len=max_len)
+
+    def batches_gather_tensor(self, ids, lengths=None, offsets=None, pad_id: Optional[int] = None, left_pad: bool = False):
+        """the batches of the last plan for one side: `ids`, `lengths`, `offsets` as blocks_tensor takes them (a 2-D padded matrix with lengths, or
+        1-D int32 ids with offsets [n + 1]) -> Batches"""
+        from . import tensor
+        return tensor.batches_gather_tensor(self, ids, lengths=lengths, offsets=offsets, pad_id=pad_id, left_pad=left_pad)
 
     # ---- encode with only the tokens a corpus uses often enough (include/yttm_mi355x.h "Encode under a restricted vocabulary")
     def set_vocabulary(self, allowed=None, counts=None, threshold: int = 1):

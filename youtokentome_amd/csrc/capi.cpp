@@ -431,6 +431,45 @@ int yttm_encode_file_blocks(yttm_encoder *h, const char *path, const char *out_p
   return blocks_done(s, nr, nf, n_rows, n_frags, err, errlen);
 }
 
+static int batches_planned(const Status &s, unsigned long long nk, unsigned long long nb, uint64_t *n_kept, uint64_t *n_batches, char *err, int errlen) {
+  if (n_kept) *n_kept = nk;
+  if (n_batches) *n_batches = nb;
+  return finish(s, err, errlen);
+}
+int yttm_batches_plan_device(yttm_encoder *h, uint64_t n_sent, uint64_t max_tokens, uint64_t max_sentences, uint64_t min_len, uint64_t max_len, uint64_t *n_kept,
+                             uint64_t *n_batches, double *kernel_ms, char *err, int errlen) {
+  unsigned long long nk = 0, nb = 0;
+  const Status s = h->enc->batches_plan_device(n_sent, max_tokens, max_sentences, min_len, max_len, &nk, &nb, kernel_ms);
+  return batches_planned(s, nk, nb, n_kept, n_batches, err, errlen);
+}
+int yttm_batches_plan_lengths_device(yttm_encoder *h, const void *d_lengths, uint64_t n_sent, uint64_t max_tokens, uint64_t max_sentences, uint64_t min_len,
+                                     uint64_t max_len, uint64_t *n_kept, uint64_t *n_batches, double *kernel_ms, char *err, int errlen) {
+  unsigned long long nk = 0, nb = 0;
+  const Status s = h->enc->batches_plan_lengths_device(d_lengths, n_sent, max_tokens, max_sentences, min_len, max_len, &nk, &nb, kernel_ms);
+  return batches_planned(s, nk, nb, n_kept, n_batches, err, errlen);
+}
+int yttm_batches_gather_device(yttm_encoder *h, uint64_t n_sent, int32_t pad_value, int left_pad, uint64_t *n_elems, double *kernel_ms, char *err, int errlen) {
+  unsigned long long ne = 0;
+  const Status s = h->enc->batches_gather_device(n_sent, pad_value, left_pad != 0, &ne, kernel_ms);
+  if (n_elems) *n_elems = ne;
+  return finish(s, err, errlen);
+}
+int yttm_batches_gather_ids_device(yttm_encoder *h, const void *d_ids, const void *d_offsets, uint64_t n_sent, uint64_t n_ids, int32_t pad_value, int left_pad,
+                                   uint64_t *n_elems, double *kernel_ms, char *err, int errlen) {
+  unsigned long long ne = 0;
+  const Status s = h->enc->batches_gather_ids_device(d_ids, d_offsets, n_sent, n_ids, pad_value, left_pad != 0, &ne, kernel_ms);
+  if (n_elems) *n_elems = ne;
+  return finish(s, err, errlen);
+}
+int yttm_batches_fetch(yttm_encoder *h, uint32_t *order, uint64_t *batch_first, uint32_t *widths, uint64_t *batch_off, int32_t *out, uint64_t n_sent,
+                       uint64_t n_batches, uint64_t n_elems, char *err, int errlen) {
+  return finish(h->enc->take_batches(order, batch_first, widths, batch_off, out, n_sent, n_batches, n_elems, false), err, errlen);
+}
+int yttm_batches_copy_device(yttm_encoder *h, void *d_order, void *d_batch_first, void *d_widths, void *d_batch_off, void *d_out, uint64_t n_sent,
+                             uint64_t n_batches, uint64_t n_elems, char *err, int errlen) {
+  return finish(h->enc->take_batches(d_order, d_batch_first, d_widths, d_batch_off, d_out, n_sent, n_batches, n_elems, true), err, errlen);
+}
+
 int yttm_encoder_set_vocabulary(yttm_encoder *h, const uint8_t *allowed, uint64_t n, uint64_t *info, char *err, int errlen) {
   unsigned long long i3[3] = {0, 0, 0};
   Status s = h->enc->set_vocabulary(allowed, n, i3);

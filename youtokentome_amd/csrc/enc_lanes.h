@@ -158,6 +158,23 @@ struct EncoderDevice {
     DevBuf<uint32_t> cnt, nxt, entry, rowbase, rowsent, rowcnt;
     DevBuf<unsigned long long> ne, hop, rowsrc, info;  // info[0 .. 2] (k_blocks.h), info[3]: a sentence longer than L
   } blk;
+  // batches by length under a token budget (host_decode.cpp, k_batches.h), the encoder's own like the blocks' slot and under lane 0's mutex: the
+  // plan (order [n], batch_first [n_batches + 1]) of the last plan call, the gathered part (widths [n_batches], batch_off [n_batches + 1], out
+  // [n_elems] rounded up to a multiple of 4) of the last gather under that plan, and the passes' working arrays.  A gather measures into
+  // w_widths / w_off and exchanges them with the gathered part once nothing can refuse the call any more.
+  struct {
+    DevBuf<uint32_t> order;
+    DevBuf<unsigned long long> batch_first;
+    unsigned long long n = 0, n_kept = 0, n_batches = 0;
+    bool planned = false;
+    DevBuf<uint32_t> widths;
+    DevBuf<unsigned long long> batch_off;
+    DevBuf<int32_t> out;
+    unsigned long long n_elems = 0;
+    bool gathered = false;
+    DevBuf<uint32_t> key, key1, key2, idx1, idx2, skey, hist, nxt, entry, base, cnt, w_widths;
+    DevBuf<unsigned long long> hist_off, hop, w_off, info;  // info[0]: a sentence the rule refuses, [1]: n_kept, [2]: n_batches, [3]: the elements
+  } bat;
   // the restricted vocabulary (host_encoder.cpp set_vocabulary, k_restrict.h): exp_ids[exp_off[v] .. exp_off[v + 1]) = E(v), and the same with every
   // expansion back to front.  Written with every lane locked, read by a call that holds its lane: a call never sees half a table.
   struct {
@@ -295,6 +312,17 @@ struct BlkParams {
 Status blocks_on_lane(EncoderDevice &D, EncodeLane &d, int device, const int32_t *ids, const unsigned long long *off, unsigned long long n_sent,
                       unsigned long long n_ids, const BlkParams &p, const char *what, unsigned long long first_index, unsigned long long *n_rows,
                       unsigned long long *n_frags, double *kernel_ms);
+
+// Batches by length under a token budget (k_batches.h; D.bat, lane 0 locked by the caller) on lane d's stream, which ends synchronised.
+// plan_on_lane: the plan of `in`'s lengths; gather_on_lane: the planned batches of the side ids / off[n_sent + 1].  Every error is found before
+// anything of the slot is changed.
+struct BatParams {
+  unsigned long long T, M, min_len, max_len;
+};
+Status plan_on_lane(EncoderDevice &D, EncodeLane &d, int device, const BatIn &in, const BatParams &p, unsigned long long *n_kept,
+                    unsigned long long *n_batches, double *kernel_ms);
+Status gather_on_lane(EncoderDevice &D, EncodeLane &d, int device, const int32_t *ids, const unsigned long long *off, unsigned long long n_sent,
+                      int32_t pad, bool left_pad, unsigned long long *n_elems, double *kernel_ms);
 
 // The vocabulary restriction of ids[n_ids] / off[n_sent + 1] in HBM on the lane (locked by the caller; a vocabulary is set): measure -> scan ->
 // write (k_restrict.h) into the lane's second pair of buffers, which then becomes the lane's encode result.  pending: the input IS that result

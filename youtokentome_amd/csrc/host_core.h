@@ -204,6 +204,21 @@ class BaseEncoder {  // bpe.h:22-82
   Status encode_file_blocks(const std::string &path, const std::string &out_prefix, bool bos, bool eos, bool reverse, double dropout_prob,
                             unsigned long long piece_bytes, unsigned long long seq_len, int mode, int32_t pad_value, int tail, unsigned long long *n_rows,
                             unsigned long long *n_frags, unsigned long long *n_lines, unsigned long long *n_ids, std::string *report) const;
+  // Batches by length under a token budget on the device (host_decode.cpp, k_batches.h; the rule is in include/yttm_mi355x.h): the plan (a stable
+  // order of the sentences by length and its greedy cuts) from the pending encode result's offsets or from int32 lengths in HBM, and the gather of
+  // the planned batches of one side (the pending result, or any ids + offsets in HBM) into padded matrices, both in a slot of the encoder's own:
+  // a plan call replaces the plan and empties the gathered part, a gather replaces the gathered part.  take_batches: the five arrays to host
+  // arrays or device to device, a null pointer is skipped.
+  Status batches_plan_device(unsigned long long n_sent, unsigned long long max_tokens, unsigned long long max_sentences, unsigned long long min_len,
+                             unsigned long long max_len, unsigned long long *n_kept, unsigned long long *n_batches, double *kernel_ms) const;
+  Status batches_plan_lengths_device(const void *d_lengths, unsigned long long n_sent, unsigned long long max_tokens, unsigned long long max_sentences,
+                                     unsigned long long min_len, unsigned long long max_len, unsigned long long *n_kept, unsigned long long *n_batches,
+                                     double *kernel_ms) const;
+  Status batches_gather_device(unsigned long long n_sent, int32_t pad_value, bool left_pad, unsigned long long *n_elems, double *kernel_ms) const;
+  Status batches_gather_ids_device(const void *d_ids, const void *d_offsets, unsigned long long n_sent, unsigned long long n_ids, int32_t pad_value,
+                                   bool left_pad, unsigned long long *n_elems, double *kernel_ms) const;
+  Status take_batches(void *order, void *batch_first, void *widths, void *batch_off, void *out, unsigned long long n_sent, unsigned long long n_batches,
+                      unsigned long long n_elems, bool to_device) const;
   // Encode under a restricted vocabulary (host_encoder.cpp, k_restrict.h; the rule is in include/yttm_mi355x.h): allowed[vocab_size()] (null:
   // clears it) -> the expansion tables in HBM; from then on every encode on this encoder leaves restricted ids.  info (optional): allowed ids,
   // ids that split, the longest expansion.  vocabulary_stats: restricted calls, calls where nothing split, ids in, ids out.

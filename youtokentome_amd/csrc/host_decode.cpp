@@ -554,6 +554,229 @@ Status BaseEncoder::take_blocks(void *rows, void *seg, void *pos, void *frags, v
   });
 }
 
+// ---- batches by length under a token budget (k_batches.h) ------------------------------------------------------------------------------------
+// The plan: keys -> the passes of the sort -> the cuts.  What can refuse the call (the parameters, a negative length, a kept sentence longer than
+// max_tokens) is known after the key pass, which writes a working array only; from there on the call succeeds and the slot is rewritten.
+Status plan_on_lane(EncoderDevice &D, EncodeLane &d, int device, const BatIn &in, const BatParams &p, unsigned long long *n_kept_out,
+                    unsigned long long *n_batches_out, double *kernel_ms) {
+  if (n_kept_out) *n_kept_out = 0;
+  if (n_batches_out) *n_batches_out = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  auto &B = D.bat;
+  const unsigned long long n = in.n, lim = 0x7fffffffull;
+  if (p.T < 1 || p.T > lim) return Status(1, "batches: max_tokens must be within 1 .. 2^31 - 1 (" + std::to_string(p.T) + ")");
+  if (p.M > lim) return Status(1, "batches: max_sentences must be 0 (no limit) or within 1 .. 2^31 - 1 (" + std::to_string(p.M) + ")");
+  if (n >= 0xfffffffeull) return Status(1, "batches: too many sentences for one call");
+  if (n && !in.off && !in.len) return Status(2, "batches: no lengths");
+  const BatRule r{p.T, p.M, p.min_len, p.max_len, p.max_len && p.max_len < p.T ? p.max_len : p.T};
+  return on_device(device, [&]() -> Status {
+    EventPair ev(d.st, kernel_ms != nullptr);
+    ev.start();
+    unsigned long long info[3] = {~0ull, 0, 0};
+    if (n) {
+      B.key.grow((size_t)n);
+      B.info.grow(4);
+      HIP_CHECK(hipMemsetAsync(B.info, 0xff, 8, d.st));
+      HIP_CHECK(hipMemsetAsync(B.info + 1, 0, 24, d.st));
+      launch_bat_keys(in, r, B.key, B.info, d.st);
+      HIP_CHECK(hipMemcpyAsync(info, B.info, 16, hipMemcpyDeviceToHost, d.st));
+      HIP_CHECK(hipStreamSynchronize(d.st));
+      if (info[0] != ~0ull) {
+        const unsigned long long i = info[0];
+        if (in.off) {
+          unsigned long long o2[2] = {0, 0};
+          HIP_CHECK(hipMemcpyAsync(o2, in.off + i, 16, hipMemcpyDeviceToHost, d.st));
+          HIP_CHECK(hipStreamSynchronize(d.st));
+          info[2] = o2[1] - o2[0];
+        } else {
+          int32_t l = 0;
+          HIP_CHECK(hipMemcpyAsync(&l, in.len + i, 4, hipMemcpyDeviceToHost, d.st));
+          HIP_CHECK(hipStreamSynchronize(d.st));
+          if (l < 0) return Status(1, "batches: sentence " + std::to_string(i) + " has a negative length (" + std::to_string(l) + ")");
+          info[2] = (unsigned long long)l;
+        }
+        return Status(1, "max_tokens is smaller than sentence " + std::to_string(i) + ": no batch holds it. Current value: max_tokens = " + std::to_string(p.T) +
+                             "; length = " + std::to_string(info[2]) + ";");
+      }
+    }
+    // ---- from here on the call succeeds
+    const unsigned long long n_kept = info[1];
+    unsigned long long n_batches = 0;
+    B.planned = B.gathered = false;
+    B.order.grow((size_t)n);
+    if (n) {
+      const unsigned int passes = bat_passes(r.cap);
+      const size_t nh = (size_t)(256 * bat_tiles(n));
+      B.hist.grow(nh);
+      B.hist_off.grow(nh);
+      d.k5.scan_tmp.grow((size_t)scan_scratch_blocks(nh));
+      if (passes > 1) {
+        B.key1.grow((size_t)n);
+        B.idx1.grow((size_t)n);
+      }
+      if (passes > 2) {
+        B.key2.grow((size_t)n);
+        B.idx2.grow((size_t)n);
+      }
+      const uint32_t *key_in = B.key, *idx_in = nullptr;  // (the keys of the key pass stay: the cuts read them through the order)
+      for (unsigned int k = 0; k < passes; k++) {
+        const bool last = k + 1 == passes;
+        uint32_t *key_out = last ? nullptr : (k & 1) ? B.key2.p : B.key1.p, *idx_out = last ? B.order.p : (k & 1) ? B.idx2.p : B.idx1.p;
+        launch_bat_sort_pass(key_in, idx_in, n, 8 * k, B.hist, B.hist_off, d.k5.scan_tmp, d.k5.total, key_out, idx_out, d.st);
+        key_in = key_out;
+        idx_in = idx_out;
+      }
+    }
+    if (n_kept) {
+      const unsigned int orbit = bat_orbit_positions();
+      const size_t nb = (size_t)((n_kept + orbit - 1) / orbit);
+      B.skey.grow((size_t)n_kept);
+      B.nxt.grow((size_t)n_kept);
+      B.hop.grow((size_t)n_kept);
+      B.entry.grow(nb);
+      B.base.grow(nb);
+      B.batch_first.grow((size_t)n_kept + 1);
+      HIP_CHECK(hipMemsetAsync(B.entry, 0xff, nb * 4, d.st));
+      launch_bat_cuts(B.key, B.order, n_kept, r, orbit, B.skey, B.nxt, B.hop, B.entry, B.base, B.batch_first, B.info, d.st);
+      HIP_CHECK(hipMemcpyAsync(&n_batches, B.info + 2, 8, hipMemcpyDeviceToHost, d.st));
+    } else {
+      B.batch_first.grow(1);
+      HIP_CHECK(hipMemsetAsync(B.batch_first, 0, 8, d.st));
+    }
+    ev.stop();
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    if (kernel_ms) *kernel_ms = ev.elapsed_ms();
+    B.n = n;
+    B.n_kept = n_kept;
+    B.n_batches = n_batches;
+    B.n_elems = 0;
+    B.planned = true;
+    if (n_kept_out) *n_kept_out = n_kept;
+    if (n_batches_out) *n_batches_out = n_batches;
+    return Status();
+  });
+}
+
+// The gather: measure -> scan -> write.  The measure pass writes working arrays; they become the gathered part once the size limit has passed.
+Status gather_on_lane(EncoderDevice &D, EncodeLane &d, int device, const int32_t *ids, const unsigned long long *off, unsigned long long n_sent,
+                      int32_t pad, bool left_pad, unsigned long long *n_elems_out, double *kernel_ms) {
+  if (n_elems_out) *n_elems_out = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  auto &B = D.bat;
+  if (!B.planned) return Status(1, "batches: no plan (call yttm_batches_plan_device or yttm_batches_plan_lengths_device first)");
+  if (n_sent != B.n) return Status(1, "batches: the plan is of " + std::to_string(B.n) + " sentences, not of " + std::to_string(n_sent));
+  if (B.n_kept && !off) return Status(2, "batches: no offsets");
+  return on_device(device, [&]() -> Status {
+    const BatPlan plan{B.order, B.batch_first, B.n_batches};
+    unsigned long long total = 0;
+    if (B.n_batches) {
+      B.info.grow(4);
+      B.w_widths.grow((size_t)B.n_batches);
+      HIP_CHECK(hipMemsetAsync(B.info + 3, 0, 8, d.st));
+      const Status s = two_pass_on_lane(
+          d, B.n_batches, B.cnt, B.w_off, kernel_ms, &total,
+          [&](bool write) {
+            if (!write) launch_bat_measure(plan, off, B.w_widths, B.cnt, B.info + 3, d.st);
+            else if (total) launch_bat_write(plan, ids, off, B.w_widths, B.w_off, total, pad, left_pad, B.out, d.st);
+          },
+          [&]() -> Status {
+            HIP_CHECK(hipMemcpyAsync(&total, B.info + 3, 8, hipMemcpyDeviceToHost, d.st));  // (exact; the scan's counts saturate)
+            HIP_CHECK(hipStreamSynchronize(d.st));
+            if (total > 0x7fffffffull)
+              return Status(1, "batches: the gathered batches exceed 2^31 - 1 elements (" + std::to_string(total) + "): plan fewer sentences per call");
+            B.gathered = false;  // ---- from here on the call succeeds
+            return Status();
+          },
+          [&](unsigned long long need) { B.out.grow((size_t)need + 4); });
+      if (!s.ok()) return s;
+      std::swap(B.widths, B.w_widths);
+      std::swap(B.batch_off, B.w_off);
+    } else {
+      B.gathered = false;
+      B.batch_off.grow(1);
+      HIP_CHECK(hipMemsetAsync(B.batch_off, 0, 8, d.st));
+      HIP_CHECK(hipStreamSynchronize(d.st));
+    }
+    B.n_elems = total;
+    B.gathered = true;
+    if (n_elems_out) *n_elems_out = total;
+    return Status();
+  });
+}
+
+Status BaseEncoder::batches_plan_device(unsigned long long n_sent, unsigned long long max_tokens, unsigned long long max_sentences, unsigned long long min_len,
+                                        unsigned long long max_len, unsigned long long *n_kept, unsigned long long *n_batches, double *kernel_ms) const {
+  if (n_kept) *n_kept = 0;
+  if (n_batches) *n_batches = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  if (!dev_) return Status(1, "batches_plan_device: no matching encode result");
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
+  if (!d.res.made || n_sent != d.res.n_sent) return Status(1, "batches_plan_device: no matching encode result");
+  return plan_on_lane(*dev_, d, device_, BatIn{n_sent ? d.res.off.p : nullptr, nullptr, n_sent}, BatParams{max_tokens, max_sentences, min_len, max_len}, n_kept,
+                      n_batches, kernel_ms);
+}
+
+Status BaseEncoder::batches_plan_lengths_device(const void *d_lengths, unsigned long long n_sent, unsigned long long max_tokens, unsigned long long max_sentences,
+                                                unsigned long long min_len, unsigned long long max_len, unsigned long long *n_kept,
+                                                unsigned long long *n_batches, double *kernel_ms) const {
+  if (n_kept) *n_kept = 0;
+  if (n_batches) *n_batches = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (((uintptr_t)d_lengths & 3u) != 0) return Status(2, "batches_plan_lengths_device: the lengths must be 4-byte aligned");
+  const Lane0 l(*dev_);
+  return plan_on_lane(*dev_, l.d, device_, BatIn{nullptr, (const int32_t *)d_lengths, n_sent}, BatParams{max_tokens, max_sentences, min_len, max_len}, n_kept,
+                      n_batches, kernel_ms);
+}
+
+Status BaseEncoder::batches_gather_device(unsigned long long n_sent, int32_t pad_value, bool left_pad, unsigned long long *n_elems, double *kernel_ms) const {
+  if (n_elems) *n_elems = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  if (!dev_) return Status(1, "batches_gather_device: no matching encode result");
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
+  if (!d.res.made || n_sent != d.res.n_sent) return Status(1, "batches_gather_device: no matching encode result");
+  return gather_on_lane(*dev_, d, device_, d.res.ids, n_sent ? d.res.off.p : nullptr, n_sent, pad_value, left_pad, n_elems, kernel_ms);
+}
+
+Status BaseEncoder::batches_gather_ids_device(const void *d_ids, const void *d_offsets, unsigned long long n_sent, unsigned long long n_ids, int32_t pad_value,
+                                              bool left_pad, unsigned long long *n_elems, double *kernel_ms) const {
+  if (n_elems) *n_elems = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (((uintptr_t)d_ids & 3u) != 0) return Status(2, "batches_gather_ids_device: the ids must be 4-byte aligned");
+  if (((uintptr_t)d_offsets & 7u) != 0) return Status(2, "batches_gather_ids_device: the offsets must be 8-byte aligned");
+  if (n_ids && !d_ids) return Status(2, "batches: no ids");
+  const Lane0 l(*dev_);
+  return gather_on_lane(*dev_, l.d, device_, (const int32_t *)d_ids, (const unsigned long long *)d_offsets, n_sent, pad_value, left_pad, n_elems, kernel_ms);
+}
+
+Status BaseEncoder::take_batches(void *order, void *batch_first, void *widths, void *batch_off, void *out, unsigned long long n_sent, unsigned long long n_batches,
+                                 unsigned long long n_elems, bool to_device) const {
+  const char *who = to_device ? "copy_batches: no matching batches" : "fetch_batches: no matching batches";
+  if (!dev_) return Status(1, who);
+  const Lane0 l(*dev_);
+  EncodeLane &d = l.d;
+  const auto &B = dev_->bat;
+  if (!B.planned || n_sent != B.n || n_batches != B.n_batches || n_elems != B.n_elems) return Status(1, who);
+  if (!B.gathered && (widths || batch_off || out)) return Status(1, who);
+  return on_device(device_, [&]() -> Status {
+    auto take = [&](void *dst, const void *src, size_t bytes) {
+      if (!dst || !bytes) return;
+      if (to_device) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, d.st));
+      else copy_down(device_, dst, src, bytes, d.st);
+    };
+    take(order, B.order, (size_t)B.n * 4);
+    take(batch_first, B.batch_first, ((size_t)B.n_batches + 1) * 8);
+    take(widths, B.widths, (size_t)B.n_batches * 4);
+    take(batch_off, B.batch_off, ((size_t)B.n_batches + 1) * 8);
+    take(out, B.out, (size_t)B.n_elems * 4);
+    HIP_CHECK(hipStreamSynchronize(d.st));
+    return Status();
+  });
+}
+
 Status BaseEncoder::subword_device(const void *d_bytes, const void *d_offsets, unsigned long long n_sent, unsigned long long total_bytes,
                                    unsigned long long max_sentence_bytes, bool bos, bool eos, bool reverse, double dropout_prob,
                                    unsigned long long *n_ids, unsigned long long *n_text_bytes, double *kernel_ms) const {

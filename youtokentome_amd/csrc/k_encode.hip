@@ -1166,3 +1166,4 @@ void launch_encode_gather(const int32_t *scratch_ids, const unsigned long long *
 #include "k_idcount.h"  // token frequencies of an id array: kernel and launcher of this translation unit
 #include "k_restrict.h"  // the vocabulary restriction of an id array: kernel and launcher of this translation unit
 #include "k_blocks.h"    // training blocks of an id array: kernels and launchers of this translation unit
+#include "k_batches.h"   // batches by length under a token budget: kernels and launchers of this translation unit

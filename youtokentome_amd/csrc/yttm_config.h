@@ -117,7 +117,8 @@ struct Hook {
   X(enc_sub_kb, "YTTM_ENC_SUB_KB", "", "test", "the same in KB")                                                                             \
   X(enc_pipe_from, "YTTM_ENC_PIPE_FROM", "536870912", "tune", "host -> host batches of at least this many bytes are pipelined in sub-batches") \
   X(cli_batch_bytes, "YTTM_CLI_BATCH_BYTES", "0", "test", "`yttm encode` batch size in bytes (0: the reference's 10 MiB)")                  \
-  X(idcount_window, "YTTM_IDCOUNT_WINDOW", YTTM_STR(YTTM_IDCOUNT_WINDOW_BUILT), "path", "id counts: bins a workgroup of k_idcount keeps in LDS (default: the largest built window; more clamps to it; 0: every id by global atomics)")
+  X(idcount_window, "YTTM_IDCOUNT_WINDOW", YTTM_STR(YTTM_IDCOUNT_WINDOW_BUILT), "path", "id counts: bins a workgroup of k_idcount keeps in LDS (default: the largest built window; more clamps to it; 0: every id by global atomics)") \
+  X(batches_orbit, "YTTM_BATCHES_ORBIT", "8192", "path", "batches: positions a workgroup of the cuts resolves in LDS (rounded down to a multiple of 64 within 64 .. 8192; tests: many blocks of a small plan)")
 
 struct Config {
 #define X(field, name, dflt, kind, doc) Hook field;

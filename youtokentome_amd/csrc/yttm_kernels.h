@@ -507,4 +507,53 @@ void launch_blk_write(const BlkIn &in, const unsigned long long *ne, unsigned lo
 void launch_blk_keep(const BlkIn &in, const unsigned long long *ne, unsigned long long p0, int32_t *new_ids, unsigned long long *new_off,
                      unsigned long long *info, hipStream_t st);
 
+// ---- batches by length under a token budget (k_batches.h, compiled with k_encode.hip): keys -> radix sort -> cuts; measure -> scan -> write ----
+// The lengths a plan sorts: l(i) = off[i + 1] - off[i] (off != nullptr) or len[i], which may be negative.  Only read.
+struct BatIn {
+  const unsigned long long *off;
+  const int32_t *len;
+  unsigned long long n;
+  __host__ __device__ bool negative(unsigned long long i) const { return !off && len[i] < 0; }
+  __host__ __device__ unsigned long long l(unsigned long long i) const { return off ? off[i + 1] - off[i] : (unsigned long long)(uint32_t)len[i]; }
+};
+struct BatRule {  // the parameters of the rule (include/yttm_mi355x.h), checked by the host; cap = min(T, max_len or T)
+  unsigned long long T, M, min_len, max_len, cap;
+};
+// the plan as the gather reads it
+struct BatPlan {
+  const uint32_t *order;
+  const unsigned long long *batch_first;
+  unsigned long long n_batches;
+};
+constexpr unsigned int BAT_TILE = 4096;    // sentences a workgroup of the sort ranks per pass
+constexpr unsigned int BAT_ORBIT = 8192;   // positions a workgroup of the cuts resolves in LDS
+constexpr unsigned int BAT_CHUNK = 2048;   // elements a wavefront of the gather writes
+constexpr uint32_t BAT_NONE = 0xffffffffu;  // entry[] of a block of positions the orbit does not visit
+// the 8-bit passes that sort keys of 0 .. cap + 1
+inline unsigned int bat_passes(unsigned long long cap) {
+  unsigned int bits = 0;
+  for (unsigned long long v = cap + 1; v; v >>= 1) bits++;
+  return (bits + 7) / 8;
+}
+inline unsigned long long bat_tiles(unsigned long long n) { return (n + BAT_TILE - 1) / BAT_TILE; }
+// key[n]; info[0] (holds ~0 before) = the smallest index of a negative length or of a kept sentence longer than T; info[1] (0 before) = n_kept
+void launch_bat_keys(const BatIn &in, const BatRule &r, uint32_t *key, unsigned long long *info, hipStream_t st);
+// one pass of the stable sort by the digit at `shift`: (key_in, idx_in) -> (key_out, idx_out).  idx_in == nullptr: the index is the position;
+// key_out == nullptr: the last pass.  hist[256 * tiles] and hist_off[the same] are working arrays, scan_tmp / scan_total those of the scan.
+void launch_bat_sort_pass(const uint32_t *key_in, const uint32_t *idx_in, unsigned long long n, unsigned int shift, uint32_t *hist,
+                          unsigned long long *hist_off, unsigned long long *scan_tmp, unsigned long long *scan_total, uint32_t *key_out,
+                          uint32_t *idx_out, hipStream_t st);
+unsigned int bat_orbit_positions();  // the hook YTTM_BATCHES_ORBIT as launch_bat_cuts takes it
+// skey[n_kept] = key[order[p]], then the cuts: nxt / hop[n_kept], entry / base[ceil(n_kept / orbit)] (entry holds BAT_NONE before),
+// batch_first[n_batches + 1], info[2] = n_batches.  n_kept >= 1.  orbit: the positions a workgroup resolves, 64 .. BAT_ORBIT, a multiple of 64.
+void launch_bat_cuts(const uint32_t *key, const uint32_t *order, unsigned long long n_kept, const BatRule &r, unsigned int orbit, uint32_t *skey,
+                     uint32_t *nxt, unsigned long long *hop, uint32_t *entry, uint32_t *base, unsigned long long *batch_first,
+                     unsigned long long *info, hipStream_t st);
+// the gather of one side (ids, off[n + 1]): cnt[n_batches] = rows * width and widths[n_batches], both saturating at 2^32 - 1; *total (0 before) += the
+// sum of the counts, exact
+void launch_bat_measure(const BatPlan &p, const unsigned long long *off, uint32_t *widths, uint32_t *cnt, unsigned long long *total, hipStream_t st);
+// out: 16-byte aligned, n_elems rounded up to a multiple of 4; 1 <= n_elems < 2^31
+void launch_bat_write(const BatPlan &p, const int32_t *ids, const unsigned long long *off, const uint32_t *widths,
+                      const unsigned long long *batch_off, unsigned long long n_elems, int32_t pad, bool left_pad, int32_t *out, hipStream_t st);
+
 }  // namespace yttm

@@ -1,5 +1,5 @@
 """Device tensors in, device tensors out: `BPE.encode_tensor` / `BPE.encode_text_tensor` / `BPE.text_lines_tensor` / `BPE.decode_tensor` /
-`BPE.encode_subword_tensor` / `BPE.encode_text_subword_tensor` / `BPE.encode_spans_tensor` / `BPE.encode_text_spans_tensor` / `BPE.decode_text_tensor` / `BPE.parse_ids_tensor` / `BPE.id_counts_tensor` / `BPE.*blocks*_tensor` on top
+`BPE.encode_subword_tensor` / `BPE.encode_text_subword_tensor` / `BPE.encode_spans_tensor` / `BPE.encode_text_spans_tensor` / `BPE.decode_text_tensor` / `BPE.parse_ids_tensor` / `BPE.id_counts_tensor` / `BPE.*blocks*_tensor` / `BPE.*batches*_tensor` on top
 of the raw device layer of `bpe._Core` (include/yttm_mi355x.h: yttm_encode_device, yttm_encode_text_device, yttm_lines_*, yttm_encode_copy_*,
 yttm_decode_device*, yttm_decode_copy_device).  torch is imported at call
 time; the rest of the package does not need it.
@@ -462,3 +462,138 @@ def blocks_flush_tensor(bpe, pad_id=None):
     pad_id = _pad_id(bpe, f > 0, pad_id)
     n_rows, n_frags, _ = _synced(torch, dev, core.blocks_flush_raw, 0 if pad_id is None else int(pad_id))
     return _take_blocks(torch, core, dev, n_rows, n_frags, L if n_rows else max(L, 1))
+
+
+# ---- batches by length under a token budget (include/yttm_mi355x.h "Batches by length") ---------------------------------------------------------
+class Batches:
+    """order int32 [n] (the kept sentences by (length, index), then the left-out ones), batch_first int64 [n_batches + 1], n_kept; after a gather
+    widths int32 [n_batches], batch_off int64 [n_batches + 1], ids int32 [n_elems].  len(b): the batches; b[k] = (sentence indices, matrix), the
+    matrix a view of ids."""
+
+    def __init__(self, order, batch_first, n_kept, widths=None, batch_off=None, ids=None):
+        self.order, self.batch_first, self.n_kept, self.widths, self.batch_off, self.ids = order, batch_first, n_kept, widths, batch_off, ids
+        self._first = self._off = self._w = None
+
+    def __len__(self):
+        return self.batch_first.numel() - 1
+
+    def __getitem__(self, k):
+        n = len(self)
+        if not -n <= k < n:
+            raise IndexError("batch %d of %d" % (k, n))
+        k %= n
+        if self._first is None:  # (one download of the three small arrays, at the first index)
+            self._first = self.batch_first.tolist()
+            self._off = self.batch_off.tolist() if self.batch_off is not None else None
+            self._w = self.widths.tolist() if self.widths is not None else None
+        a, b = self._first[k], self._first[k + 1]
+        sentences = self.order[a:b]
+        if self.ids is None:
+            return sentences, None
+        return sentences, self.ids[self._off[k]:self._off[k + 1]].view(b - a, self._w[k])
+
+    def __iter__(self):
+        return (self[k] for k in range(len(self)))
+
+
+def _take_batches(torch, core, dev, n, n_kept, n_batches, n_elems):
+    """the batches slot as tensors that torch owns"""
+    order = torch.empty(n, dtype=torch.int32, device=dev)
+    first = torch.zeros(n_batches + 1, dtype=torch.int64, device=dev)
+    if n_elems is None:
+        _synced(torch, dev, core.copy_batches_device, order.data_ptr(), first.data_ptr(), None, None, None, n, n_batches, 0)
+        return Batches(order, first, n_kept)
+    widths = torch.empty(n_batches, dtype=torch.int32, device=dev)
+    off = torch.zeros(n_batches + 1, dtype=torch.int64, device=dev)
+    out = torch.empty(n_elems, dtype=torch.int32, device=dev)
+    _synced(torch, dev, core.copy_batches_device, order.data_ptr(), first.data_ptr(), widths.data_ptr(), off.data_ptr(), out.data_ptr(), n, n_batches, n_elems)
+    return Batches(order, first, n_kept, widths, off, out)
+
+
+def _pending_batches(torch, bpe, core, dev, n, max_tokens, max_sentences, min_len, max_len, left_pad, pad_id):
+    pad_id = _pad_id(bpe, True, pad_id)
+    core.pending_n_sent = n
+    n_kept, n_batches, _ = core.batches_plan_device_raw(n, max_tokens, max_sentences, min_len, max_len)
+    n_elems, _ = core.batches_gather_device_raw(n, int(pad_id), left_pad)
+    return _take_batches(torch, core, dev, n, n_kept, n_batches, n_elems)
+
+
+def encode_batches_tensor(bpe, sentences, max_tokens, max_sentences=0, min_len=0, max_len=0, left_pad=False, bos=False, eos=False, reverse=False,
+                          dropout_prob=0, pad_id=None, device=None):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, device)
+    _check_dropout(dropout_prob)
+    _pad_id(bpe, True, pad_id)
+    d_bytes, d_off, n, total, longest_in = _sentences_on(torch, sentences, dev)
+    _synced(torch, dev, core.encode_device_raw, d_bytes.data_ptr(), d_off.data_ptr(), n, total, longest_in, bos, eos, reverse, dropout_prob)
+    return _pending_batches(torch, bpe, core, dev, n, max_tokens, max_sentences, min_len, max_len, left_pad, pad_id)
+
+
+def encode_text_batches_tensor(bpe, text, max_tokens, max_sentences=0, min_len=0, max_len=0, left_pad=False, bos=False, eos=False, reverse=False,
+                               dropout_prob=0, pad_id=None):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    _check_dropout(dropout_prob)
+    _pad_id(bpe, True, pad_id)
+    d_text, n_bytes = _text_on(torch, text, dev)
+    n, _, _ = _synced(torch, dev, core.encode_text_device_raw, d_text.data_ptr(), n_bytes, bos, eos, reverse, dropout_prob)
+    return _pending_batches(torch, bpe, core, dev, n, max_tokens, max_sentences, min_len, max_len, left_pad, pad_id)
+
+
+def batches_plan_tensor(bpe, lengths, max_tokens, max_sentences=0, min_len=0, max_len=0):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    if not hasattr(lengths, "data_ptr") or lengths.dtype != torch.int32 or lengths.dim() != 1:
+        raise ValueError("lengths must be a 1-D int32 tensor")
+    _check_on(lengths, dev, "lengths")
+    lengths = lengths.contiguous()
+    n = lengths.numel()
+    n_kept, n_batches, _ = _synced(torch, dev, core.batches_plan_lengths_device_raw, lengths.data_ptr(), n, max_tokens, max_sentences, min_len, max_len)
+    return _take_batches(torch, core, dev, n, n_kept, n_batches, None)
+
+
+def batches_gather_tensor(bpe, ids, lengths=None, offsets=None, pad_id=None, left_pad=False):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    pad_id = _pad_id(bpe, True, pad_id)
+    if not hasattr(ids, "data_ptr") or ids.dtype != torch.int32:
+        raise ValueError("ids must be an int32 tensor")
+    _check_on(ids, dev, "ids")
+    if ids.dim() == 2:
+        if offsets is not None:
+            raise ValueError("offsets go with 1-D ids; a 2-D matrix takes lengths")
+        n, w = ids.shape
+        if lengths is None:
+            lens = torch.full((n,), w, dtype=torch.int64, device=dev)
+        else:
+            _check_on(lengths, dev, "lengths")
+            if lengths.dim() != 1 or lengths.numel() != n:
+                raise ValueError("lengths must have one entry per row")
+            lens = lengths.to(torch.int64).clamp(0, w)
+        keep = torch.arange(w, device=dev).unsqueeze(0) < lens.unsqueeze(1)  # the rows' ids back to back (the library's pass takes the ragged form)
+        ids = ids[keep].contiguous()
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(lens, 0, out=offsets[1:])
+    elif ids.dim() == 1:
+        if offsets is None or lengths is not None:
+            raise ValueError("1-D ids take offsets [n + 1] (and no lengths)")
+        offsets = _offsets_u64(torch, offsets, dev)
+        ids = ids.contiguous()
+        n = offsets.numel() - 1
+        if n < 0:
+            raise ValueError("offsets must have at least one entry")
+        if n and (int(offsets[-1]) > ids.numel() or int(offsets[0]) != 0 or bool((offsets[1:] < offsets[:-1]).any())):
+            raise ValueError("offsets must start at 0, be non-decreasing and end inside ids")
+    else:
+        raise ValueError("ids must be 1-D (with offsets) or 2-D (padded)")
+    n_in = int(offsets[-1]) if n else 0
+    plan = getattr(core, "batches_last_plan", None)
+    if plan is None:
+        raise ValueError("batches_gather_tensor: no plan (batches_plan_tensor or encode_batches_tensor first)")
+    n_elems, _ = _synced(torch, dev, core.batches_gather_ids_device_raw, ids.data_ptr(), offsets.data_ptr(), n, n_in, int(pad_id), left_pad)
+    _, n_kept, n_batches = plan
+    return _take_batches(torch, core, dev, n, n_kept, n_batches, n_elems)
