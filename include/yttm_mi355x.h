@@ -373,6 +373,43 @@ int yttm_encoder_vocabulary_stats(yttm_encoder *enc, uint64_t out[4]);
 int yttm_restrict_ids_device(yttm_encoder *enc, const void *d_ids, const void *d_offsets, uint64_t n_sent, uint64_t n_ids, int reverse,
                              uint64_t *n_out, double *kernel_ms, char *err, int errlen);
 
+/* Byte fallback (SentencePiece's byte_fallback; the reference has no counterpart: a maximal run of valid, non-space code points outside the
+ * model's alphabet becomes ONE unk_id, SURVEY.md A.7, and the run's text is gone from the ids).  A setting of an encoder, as the restricted
+ * vocabulary is; the model file does not change.  Let V = yttm_vocab_size(enc).  The byte id of byte b is V + b, 0 <= b <= 255.
+ * Encode, setting on: take the ids the encoder makes with the setting off, in forward order.  The k-th unk_id of a sentence stands for the
+ *   sentence's k-th unknown run (a maximal run of valid non-space code points outside the alphabet; invalid bytes inside it are dropped and do
+ *   not end it).  That one id is replaced by V + b for every byte b of the run's valid characters, in text order.  Every other id stays: bos_id,
+ *   eos_id, the space token and merged tokens.  A sentence stored back to front (reverse) holds the reverse of the forward result as a whole:
+ *   a run's bytes are back to front, and the k-th stored unk_id of a sentence with n of them is run n - 1 - k.  Dropout does not change the
+ *   correspondence (rules never match placeholders).  A restricted vocabulary commutes with it: byte ids lie outside [0, V) and pass through E,
+ *   unk_id is a leaf.  n_ids and kernel_ms of every encode include the pass (k_bytefb.h: measure, scan, write; the write pass is skipped only
+ *   where the measure pass met no unk_id -- a run of one ASCII char keeps the number of ids and still changes one).
+ * The stand-alone entry takes ids that did not come from this call: an unk_id whose sentence has no such run stays unk_id, runs beyond the
+ *   sentence's unk_ids are ignored, no id is ever lost.
+ * Decode, setting on: an id in [V, V + 256) is valid, its piece is the single raw byte, no strip rule applies to it, and it can be named in
+ *   ignore_ids.  Ids >= V + 256 or < 0 keep the error and its message.  The bytes come out verbatim: ids the caller made up may form invalid
+ *   UTF-8, and the byte and tensor routes return them as they are.  (The device decode strips a leading V + 0x20 of a sentence as it strips
+ *   the space of a first piece; no encode makes that id, a space is never part of a run.)
+ * Names, setting on: yttm_id_to_subword(V + b) is <0xNN>, two upper-case hex digits; yttm_subword_to_id("<0xNN>") is V + b; SUBWORD text
+ *   prints a byte id as that one piece followed by a space.  yttm_vocab_size and yttm_vocabulary do not change.
+ * Counts, setting on: n_bins == 0 means V + 256, and yttm_encode_file_counts writes V + 256 + 1 integers: the caller's counts hold that many.
+ * Spans are not defined under byte fallback (several ids would share one unit): yttm_spans_device, yttm_spans_text_device and
+ *   yttm_encode_as_ids_spans return code 1 with a message before any work, and what was pending stays.
+ * Setting off: every call behaves as if the setting did not exist.
+ *
+ * yttm_encoder_set_byte_fallback waits for both of the encoder's lanes; a result already pending is not changed.  yttm_encoder_byte_fallback:
+ * 0 or 1.  yttm_encoder_byte_fallback_stats: {calls of the pass, calls whose write pass was skipped, ids in, ids out} since the encoder was made. */
+int yttm_encoder_set_byte_fallback(yttm_encoder *enc, int on, char *err, int errlen);
+int yttm_encoder_byte_fallback(yttm_encoder *enc);
+int yttm_encoder_byte_fallback_stats(yttm_encoder *enc, uint64_t out[4]);
+/* The pass over ids the encoder did not make and the text they were made from, all in HBM: int32 d_ids[n_ids] + uint64 d_id_offsets[n_sent + 1]
+ * (the conventions of yttm_restrict_ids_device), sentence s = d_bytes[d_text_offsets[s] .. d_text_offsets[s + 1]), total_bytes in all.  It leaves
+ * a pending encode result of n_sent sentences and *n_out ids, exactly as after yttm_encode_device; the spans slot is emptied.  All inputs are
+ * only read.  Setting off: code 1, and nothing pending is replaced.  kernel_ms (optional) = measure + scan + write. */
+int yttm_byte_fallback_ids_device(yttm_encoder *enc, const void *d_ids, const void *d_id_offsets, const void *d_bytes, const void *d_text_offsets,
+                                  uint64_t n_sent, uint64_t n_ids, uint64_t total_bytes, int reverse, uint64_t *n_out, double *kernel_ms, char *err,
+                                  int errlen);
+
 /* Word-level encode cache (SURVEY.md 8f "N4"; the reference has no counterpart: bpe.cpp:1497-1632 encodes every word occurrence).
  * mode 0: every batch goes straight through the encode kernel; 1: distinct words are encoded once whenever that is possible
  * (dropout_prob == 0); 2 (default): the same for batches of at least min_bytes.  The ids are identical either way.

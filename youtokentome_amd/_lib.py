@@ -29,6 +29,7 @@ EXPORTS = [
     "yttm_spans_device", "yttm_spans_text_device", "yttm_spans_fetch", "yttm_spans_copy_device", "yttm_spans_copy_padded", "yttm_encode_as_ids_spans",
     "yttm_id_counts_device", "yttm_id_counts_ids_device", "yttm_id_counts_fetch", "yttm_id_counts_copy_device", "yttm_encode_file_counts",
     "yttm_encoder_set_vocabulary", "yttm_encoder_vocabulary_stats", "yttm_restrict_ids_device",
+    "yttm_encoder_set_byte_fallback", "yttm_encoder_byte_fallback", "yttm_encoder_byte_fallback_stats", "yttm_byte_fallback_ids_device",
     "yttm_blocks_device", "yttm_blocks_ids_device", "yttm_blocks_flush", "yttm_blocks_open", "yttm_blocks_discard", "yttm_blocks_fetch", "yttm_blocks_copy_device",
     "yttm_encode_file_blocks",
     "yttm_batches_plan_device", "yttm_batches_plan_lengths_device", "yttm_batches_gather_device", "yttm_batches_gather_ids_device", "yttm_batches_fetch",
@@ -102,6 +103,10 @@ def load():
     L.yttm_encoder_set_vocabulary.argtypes = [cvp, u8p, C.c_uint64, u64p, cs, ci]
     L.yttm_encoder_vocabulary_stats.argtypes = [cvp, u64p]
     L.yttm_restrict_ids_device.argtypes = [cvp, cvp, cvp, C.c_uint64, C.c_uint64, ci, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_encoder_set_byte_fallback.argtypes = [cvp, ci, cs, ci]
+    L.yttm_encoder_byte_fallback.argtypes = [cvp]
+    L.yttm_encoder_byte_fallback_stats.argtypes = [cvp, u64p]
+    L.yttm_byte_fallback_ids_device.argtypes = [cvp, cvp, cvp, cvp, cvp, C.c_uint64, C.c_uint64, C.c_uint64, ci, u64p, C.POINTER(cd), cs, ci]
     L.yttm_blocks_device.argtypes = [cvp, C.c_uint64, C.c_uint64, ci, C.c_int32, ci, u64p, u64p, C.POINTER(cd), cs, ci]
     L.yttm_blocks_ids_device.argtypes = [cvp, cvp, cvp, C.c_uint64, C.c_uint64, C.c_uint64, ci, C.c_int32, ci, u64p, u64p, C.POINTER(cd), cs, ci]
     L.yttm_blocks_flush.argtypes = [cvp, C.c_int32, u64p, u64p, C.POINTER(cd), cs, ci]

@@ -137,6 +137,31 @@ class _Core:
                                                          C.byref(ms), err, _lib.ERRLEN), err)
         return n.value, ms.value
 
+    # ---- byte fallback (include/yttm_mi355x.h "Byte fallback"): the bytes of an unknown run as the ids vocab_size() + b in place of one <UNK>
+    def set_byte_fallback(self, on=True):
+        err = _err()
+        self._check(_lib.load().yttm_encoder_set_byte_fallback(self._h, int(bool(on)), err, _lib.ERRLEN), err)
+
+    def byte_fallback(self):
+        return bool(_lib.load().yttm_encoder_byte_fallback(self._h))
+
+    def id_bound(self):
+        """the ids the decode, the names and the counts know: vocab_size(), with the byte fallback on 256 more"""
+        return self.vocab_size() + (256 if self.byte_fallback() else 0)
+
+    def byte_fallback_stats(self):
+        """-> (calls of the pass, calls whose write pass was skipped, ids in, ids out)"""
+        out = (C.c_uint64 * 4)()
+        _lib.load().yttm_encoder_byte_fallback_stats(self._h, out)
+        return tuple(int(v) for v in out)
+
+    def byte_fallback_ids_device_raw(self, d_ids, d_id_offsets, d_bytes, d_text_offsets, n_sent, n_ids, total_bytes, reverse=False):
+        """-> (n_out, kernel_ms); the ids are pending as after encode_device_raw"""
+        n, ms, err = C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_byte_fallback_ids_device(self._h, C.c_void_p(d_ids), C.c_void_p(d_id_offsets), C.c_void_p(d_bytes), C.c_void_p(d_text_offsets),
+                                                              n_sent, n_ids, total_bytes, int(bool(reverse)), C.byref(n), C.byref(ms), err, _lib.ERRLEN), err)
+        return n.value, ms.value
+
     # ---- packed fast path (SURVEY.md N2): bytes + offsets -> numpy ids + offsets
     def encode_packed(self, blob: bytes, offsets, bos=False, eos=False, reverse=False, dropout_prob=0.0):
         L = _lib.load()
@@ -365,7 +390,7 @@ class _Core:
 
     def fetch_id_counts(self, n_bins=0):
         """the counts -> np.uint64 [n_bins + 1]"""
-        counts, err = np.zeros(int(n_bins or self.vocab_size()) + 1, np.uint64), _err()
+        counts, err = np.zeros(int(n_bins or self.id_bound()) + 1, np.uint64), _err()
         self._check(_lib.load().yttm_id_counts_fetch(self._h, counts.ctypes.data_as(_lib.u64p), int(n_bins), err, _lib.ERRLEN), err)
         return counts
 
@@ -374,10 +399,10 @@ class _Core:
         self._check(_lib.load().yttm_id_counts_copy_device(self._h, C.c_void_p(d_counts), int(n_bins), err, _lib.ERRLEN), err)
 
     def encode_file_counts(self, path, bos=False, eos=False, reverse=False, dropout_prob=0.0, chunk_bytes=None, report=False):
-        """a text file -> np.uint64 counts[vocab_size + 1] of its ids (and with report=True the call's report, a dict); report["lines"] and
-        report["ids"] are the file's"""
+        """a text file -> np.uint64 counts[vocab_size + 1] of its ids (with the byte fallback on: [vocab_size + 256 + 1]; and with report=True the
+        call's report, a dict); report["lines"] and report["ids"] are the file's"""
         _check_dropout(dropout_prob)
-        counts = np.zeros(self.vocab_size() + 1, np.uint64)
+        counts = np.zeros(self.id_bound() + 1, np.uint64)
         nl, ni, err = C.c_uint64(), C.c_uint64(), _err()
         rep = C.create_string_buffer(1024)
         rc = _lib.load().yttm_encode_file_counts(self._h, os.fsencode(path), int(bos), int(eos), int(reverse), float(dropout_prob), int(chunk_bytes or 0),
@@ -614,7 +639,8 @@ class _Core:
         oo = _take(ooff, len(ids) + 1, C.c_uint64, np.uint64)
         raw = C.string_at(blob_p, int(oo[-1]))
         L.yttm_free(blob_p)
-        return [raw[int(oo[i]):int(oo[i + 1])].decode() for i in range(len(ids))]
+        errors = "replace" if self.byte_fallback() else "strict"  # (byte ids the caller made up may form invalid UTF-8)
+        return [raw[int(oo[i]):int(oo[i + 1])].decode(errors=errors) for i in range(len(ids))]
 
     def vocab_size(self):
         return _lib.load().yttm_vocab_size(self._h)
@@ -918,6 +944,30 @@ class BPE:
     def vocabulary_stats(self):
         """(restricted calls, calls where nothing split, ids in, ids out) since this object was made"""
         return self.bpe_cython.vocabulary_stats()
+
+    # ---- unknown characters as UTF-8 byte ids (include/yttm_mi355x.h "Byte fallback"; SentencePiece's byte_fallback)
+    def set_byte_fallback(self, on: bool = True):
+        """On: every encode of this object -- ids, tensors, SUBWORD text, id text, counts, blocks, batches, files -- gives the bytes of a run of
+        characters outside the model's alphabet as the ids vocab_size() + b in place of the run's one <UNK>, so that decode(encode(s)) gives the
+        text back; decode, id_to_subword ("<0xNN>"), subword_to_id and the counts know those 256 ids.  The model file and vocab_size() do not
+        change.  Spans are not defined while it is on.  Off (the default): nothing changes."""
+        self.bpe_cython.set_byte_fallback(on)
+
+    def byte_fallback(self):
+        """the first byte id (vocab_size()) while the byte fallback is on, else None"""
+        return self.vocab_size() if self.bpe_cython.byte_fallback() else None
+
+    def byte_fallback_stats(self):
+        """(calls of the pass, calls whose write pass was skipped, ids in, ids out) since this object was made"""
+        return self.bpe_cython.byte_fallback_stats()
+
+    def byte_fallback_tensor(self, ids, text, lengths=None, offsets=None, reverse: bool = False, padded: Optional[bool] = None,
+                             width: Optional[int] = None, pad_id: Optional[int] = None):
+        """The pass alone, on ids this object did not encode and the text they were made from: ids as restrict_tensor takes them, text a list of
+        str or a pair (uint8 bytes, offsets) on the device, one sentence per row of ids.  Every <UNK> that stands for an unknown run of its sentence
+        becomes the run's byte ids; an <UNK> without a run stays.  Needs the setting on.  The result as restrict_tensor gives it."""
+        from . import tensor
+        return tensor.byte_fallback_tensor(self, ids, text, lengths=lengths, offsets=offsets, reverse=reverse, padded=padded, width=width, pad_id=pad_id)
 
     def restrict_tensor(self, ids, lengths=None, offsets=None, reverse: bool = False, padded: Optional[bool] = None, width: Optional[int] = None,
                         pad_id: Optional[int] = None):

@@ -490,6 +490,23 @@ int yttm_restrict_ids_device(yttm_encoder *h, const void *d_ids, const void *d_o
   return finish(s, err, errlen);
 }
 
+int yttm_encoder_set_byte_fallback(yttm_encoder *h, int on, char *err, int errlen) { return finish(h->enc->set_byte_fallback(on != 0), err, errlen); }
+int yttm_encoder_byte_fallback(yttm_encoder *h) { return h->enc->byte_fallback() ? 1 : 0; }
+int yttm_encoder_byte_fallback_stats(yttm_encoder *h, uint64_t out[4]) {
+  unsigned long long o4[4] = {0, 0, 0, 0};
+  h->enc->byte_fallback_stats(o4);
+  for (int i = 0; i < 4; i++) out[i] = o4[i];
+  return 0;
+}
+int yttm_byte_fallback_ids_device(yttm_encoder *h, const void *d_ids, const void *d_id_offsets, const void *d_bytes, const void *d_text_offsets,
+                                  uint64_t n_sent, uint64_t n_ids, uint64_t total_bytes, int reverse, uint64_t *n_out, double *kernel_ms, char *err,
+                                  int errlen) {
+  unsigned long long no = 0;
+  Status s = h->enc->byte_fallback_ids_device(d_ids, d_id_offsets, d_bytes, d_text_offsets, n_sent, n_ids, total_bytes, reverse != 0, &no, kernel_ms);
+  if (n_out) *n_out = no;
+  return finish(s, err, errlen);
+}
+
 int yttm_encoder_set_cache(yttm_encoder *h, int mode, uint64_t min_bytes) {
   h->enc->set_cache(mode, min_bytes);
   return 0;

@@ -7,6 +7,7 @@
 #include <mutex>
 #include <string>
 
+#include "bytefb_plan.h"
 #include "gpu_ctx.h"
 #include "host_core.h"
 
@@ -67,6 +68,9 @@ struct EncodeLane {
     DevBuf<unsigned long long> off;
     DevBuf<uint32_t> len;
   } rs;
+  struct {  // the byte fallback (k_bytefb.h) writes into rs's buffers too, one pass after the other; saw[0]: the measure pass met an unk_id
+    DevBuf<uint32_t> saw;
+  } fb;
   struct {  // word cache (k_wcache.hip): the batch's table of distinct words, the slot of every occurrence, the list K5 encodes, its ids
     DevBuf<unsigned long long> slot, pos, extra, blk_off, ustart, uend;
     DevBuf<uint32_t> occ, blk, uslot, ucounts;
@@ -97,6 +101,7 @@ struct EncodeLane {
     k5.total.alloc(2);
     wc.misc.alloc(2);
     res.misc.alloc(1);
+    fb.saw.alloc(1);
     dec.misc.alloc(1);
     sp.misc.alloc(1);
     ln.misc.alloc(1);
@@ -185,6 +190,13 @@ struct EncoderDevice {
     unsigned long long info[3] = {0, 0, 0};               // allowed ids, ids that split, the longest expansion
     std::atomic<unsigned long long> stats[4] = {{0}, {0}, {0}, {0}};  // restricted calls, calls where nothing split, ids in, ids out
   } voc;
+  // the byte fallback (host_encoder.cpp set_byte_fallback, k_bytefb.h): a setting of the encoder like the vocabulary, switched with every lane locked.
+  // id_bound(V): the ids the decode, the SUBWORD formatter and the ignore bitmap accept (bytefb_plan.h); their tables always hold V + 256 entries.
+  struct {
+    std::atomic<bool> on{false};
+    std::atomic<unsigned long long> stats[4] = {{0}, {0}, {0}, {0}};  // calls, calls whose write pass was skipped, ids in, ids out
+  } bfb;
+  uint32_t id_bound(uint32_t V) const { return bytefb_bound(V, bfb.on.load()); }
   // a free lane, locked (falls back to waiting for the caller's turn-based choice)
   // (Lane 0 last: the device-resident pair encode_device / fetch_device_result keeps its result there, unlocked, between the two
   // calls -- a host-to-host encode from another thread in between takes another lane while one is free.)
@@ -268,6 +280,8 @@ Status on_device(int device, F &&body) {
   }
 }
 
+// what every spans entry answers while the byte fallback is on, before any work (several ids would share one unit)
+constexpr const char *SPANS_UNDER_BYTE_FALLBACK = "spans are not defined under byte fallback: switch it off (set_byte_fallback) for this call";
 Status check_bos_eos(const BaseEncoder &enc, bool bos, bool eos);  // bpe.cpp:1702-1707: the reference's two messages, before any work
 
 // K5 on one lane (locked by the caller): input already in HBM, ids + offsets left in the lane's result buffers

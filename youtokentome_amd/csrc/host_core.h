@@ -227,6 +227,16 @@ class BaseEncoder {  // bpe.h:22-82
   void vocabulary_stats(unsigned long long out[4]) const;
   Status restrict_ids_device(const void *d_ids, const void *d_offsets, unsigned long long n_sent, unsigned long long n_ids, bool reverse,
                              unsigned long long *n_out, double *kernel_ms) const;
+  // Byte fallback (host_encoder.cpp, k_bytefb.h; the rule is in include/yttm_mi355x.h): a setting of the encoder.  On: every encode leaves the
+  // bytes of an unknown run as the ids vocab_size() + b in place of the run's unk_id, and the decode, the names, the SUBWORD pieces and the
+  // counts know the ids [vocab_size(), vocab_size() + 256).  byte_fallback_stats: calls of the pass, calls whose write pass was skipped, ids in,
+  // ids out.  byte_fallback_ids_device: the pass over ids + offsets and the text they were made from, all in HBM, that the encoder did not make;
+  // the result is pending as after encode_device.
+  Status set_byte_fallback(bool on) const;
+  bool byte_fallback() const;
+  void byte_fallback_stats(unsigned long long out[4]) const;
+  Status byte_fallback_ids_device(const void *d_ids, const void *d_id_offsets, const void *d_bytes, const void *d_text_offsets, unsigned long long n_sent,
+                                  unsigned long long n_ids, unsigned long long total_bytes, bool reverse, unsigned long long *n_out, double *kernel_ms) const;
   // the YTTM_* hooks as they stood when THIS encoder was made: every entry point binds them to its thread (yttm_config.h CfgBind), so that a
   // later encoder or training never changes the paths of this one
   std::shared_ptr<const Config> config() const;

@@ -12,7 +12,7 @@
 namespace yttm {
 
 // A piece table, once per encoder (under dec_mu; `ready` is the table's own flag): build(blob, off, per_id) fills the text of every id back to
-// back, off[V + 1] and -- where the table has a third array, dst_per_id -- a word per id, by the table's own per-id rules.  All are allocated,
+// back, off[V + 256 + 1] (the byte ids' entries are always there; the bound handed to the kernels says whether they count) and -- where the table has a third array, dst_per_id -- a word per id, by the table's own per-id rules.  All are allocated,
 // then copied, and handed to the encoder together once every copy is there: a failure on the way leaves the encoder as it was.
 template <class Build>
 static void table_once(const BaseEncoder &enc, EncoderDevice &D, bool &ready, DevBuf<uint8_t> &dst_blob, DevBuf<uint32_t> &dst_off,
@@ -20,7 +20,7 @@ static void table_once(const BaseEncoder &enc, EncoderDevice &D, bool &ready, De
   std::lock_guard<std::mutex> lk(D.dec_mu);
   if (ready) return;
   std::string blob;
-  std::vector<uint32_t> off((size_t)enc.vocab_size() + 1, 0), per_id(dst_per_id ? (size_t)enc.vocab_size() : 0, 0);
+  std::vector<uint32_t> off(bytefb_table_offsets((uint32_t)enc.vocab_size()), 0), per_id(dst_per_id ? (size_t)enc.vocab_size() : 0, 0);
   build(blob, off, per_id);
   DevBuf<uint8_t> d_blob;
   DevBuf<uint32_t> d_off, d_per_id;
@@ -54,8 +54,9 @@ static void decode_table(const BaseEncoder &enc, EncoderDevice &D) {
       if (ok) blob += piece;
       else off[(size_t)id] |= DEC_INVALID;
     }
-    if (blob.size() >= (size_t)DEC_INVALID) throw GpuError{"decode: the vocabulary's text does not fit 2 GB"};
-    off[(size_t)V] = (uint32_t)blob.size();
+    if (blob.size() + BYTE_IDS >= (size_t)DEC_INVALID) throw GpuError{"decode: the vocabulary's text does not fit 2 GB"};
+    for (uint32_t b = 0; b <= BYTE_IDS; b++) off[(size_t)V + b] = (uint32_t)blob.size() + b;  // a byte id's piece is the raw byte
+    for (uint32_t b = 0; b < BYTE_IDS; b++) blob += (char)b;
     D.dec_vocab = (uint32_t)V;
   });
 }
@@ -100,14 +101,15 @@ Status decode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, i
       d, device, "decode", in.n_sent, n_bytes, kernel_ms,
       [&] {
         decode_table(enc, D);
-        tb = DecTable{D.piece_blob, D.piece_off, D.dec_vocab};
+        const uint32_t bound = D.id_bound(D.dec_vocab);
+        tb = DecTable{D.piece_blob, D.piece_off, bound};
         if (!n_ignore) return;
-        const size_t words = ((size_t)D.dec_vocab + 31) / 32 + 1;
+        const size_t words = bytefb_bitmap_words(bound);
         std::vector<uint32_t> host(words, 0);
         std::vector<int32_t> extra;
         for (unsigned long long i = 0; i < n_ignore; i++) {
           const int32_t id = ignore_ids[i];
-          if ((uint32_t)id < D.dec_vocab) host[(uint32_t)id >> 5] |= 1u << ((uint32_t)id & 31u);
+          if ((uint32_t)id < bound) host[(uint32_t)id >> 5] |= 1u << ((uint32_t)id & 31u);
           else extra.push_back(id);
         }
         std::sort(extra.begin(), extra.end());
@@ -248,7 +250,11 @@ static void subword_table(const BaseEncoder &enc, EncoderDevice &D) {
         units[(size_t)id] = n;
       }
     }
-    off[(size_t)V] = (uint32_t)blob.size();
+    for (uint32_t b = 0; b < BYTE_IDS; b++) {  // a byte id prints as its name, <0xNN>
+      off[(size_t)V + b] = (uint32_t)blob.size();
+      blob += bytefb_name(b);
+    }
+    off[(size_t)V + BYTE_IDS] = (uint32_t)blob.size();
   });
 }
 
@@ -263,7 +269,7 @@ Status format_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, i
   return text_on_lane(
       d, device, "subword", in.n_sent, n_text_bytes, kernel_ms, [&] { subword_table(enc, D); },
       [&](bool write) {
-        launch_subword(write, D.m, in, DecTable{D.sub_blob, D.sub_off, (uint32_t)enc.vocab_size()}, d.res.n_ids, d.dec.len, d.dec.off, d.dec.bytes, d.st);
+        launch_subword(write, D.m, in, DecTable{D.sub_blob, D.sub_off, D.id_bound((uint32_t)enc.vocab_size())}, d.res.n_ids, d.dec.len, d.dec.off, d.dec.bytes, d.st);
       },
       no_check);
 }
@@ -324,7 +330,7 @@ Status BaseEncoder::id_counts_device(unsigned long long n_sent, unsigned long lo
   const Lane0 l(*dev_);
   EncodeLane &d = l.d;
   if (!d.res.made || n_sent != d.res.n_sent) return Status(1, "id_counts_device: no matching encode result");  // (before any work: the counts stay)
-  const Status s = count_on_lane(*dev_, d, device_, d.res.ids, d.res.n_ids, n_bins ? n_bins : (unsigned long long)vocab_size(), accumulate, ms.next());
+  const Status s = count_on_lane(*dev_, d, device_, d.res.ids, d.res.n_ids, n_bins ? n_bins : bytefb_default_bins((uint32_t)vocab_size(), byte_fallback()), accumulate, ms.next());
   if (s.ok() && n_counted) *n_counted = d.res.n_ids;
   return s;
 }
@@ -334,7 +340,7 @@ Status BaseEncoder::id_counts_ids_device(const void *d_ids, unsigned long long n
   if (!dev_) return Status(2, "encoder has no device state");
   if (((uintptr_t)d_ids & 3u) != 0) return Status(2, "id_counts_ids_device: the ids must be 4-byte aligned");
   const Lane0 l(*dev_);
-  return count_on_lane(*dev_, l.d, device_, (const int32_t *)d_ids, n_ids, n_bins ? n_bins : (unsigned long long)vocab_size(), accumulate, ms.next());
+  return count_on_lane(*dev_, l.d, device_, (const int32_t *)d_ids, n_ids, n_bins ? n_bins : bytefb_default_bins((uint32_t)vocab_size(), byte_fallback()), accumulate, ms.next());
 }
 
 Status BaseEncoder::take_id_counts(void *counts, unsigned long long n_bins, bool to_device) const {
@@ -342,7 +348,7 @@ Status BaseEncoder::take_id_counts(void *counts, unsigned long long n_bins, bool
   if (!dev_) return Status(1, who);
   const Lane0 l(*dev_);
   EncodeLane &d = l.d;
-  if (!dev_->idc.valid || (n_bins ? n_bins : (unsigned long long)vocab_size()) != dev_->idc.n_bins) return Status(1, who);
+  if (!dev_->idc.valid || (n_bins ? n_bins : bytefb_default_bins((uint32_t)vocab_size(), byte_fallback())) != dev_->idc.n_bins) return Status(1, who);
   if (!counts) return Status(2, "id_counts: no output");
   const size_t bytes = ((size_t)dev_->idc.n_bins + 1) * 8;
   return on_device(device_, [&]() -> Status {
@@ -834,6 +840,7 @@ Status BaseEncoder::spans_device(const void *d_bytes, const void *d_offsets, uns
                                  double *kernel_ms) const {
   if (n_ids) *n_ids = 0;
   StageClock ms(kernel_ms);
+  if (byte_fallback()) return Status(1, SPANS_UNDER_BYTE_FALLBACK);
   const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work, and before the device check: nothing that was pending is touched)
   if (!tokens.ok()) return tokens;
   if (!dev_) return Status(2, "encoder has no device state");
@@ -889,6 +896,7 @@ Status BaseEncoder::encode_as_ids_spans(const uint8_t *bytes, const unsigned lon
   *out_off = nullptr;
   *spans = nullptr;
   const CfgBind bind(config());
+  if (byte_fallback()) return Status(1, SPANS_UNDER_BYTE_FALLBACK);
   Status s = check_bos_eos(*this, bos, eos);
   if (!s.ok()) return s;
   if (n_sent && !dev_) return Status(2, "encoder has no device state");

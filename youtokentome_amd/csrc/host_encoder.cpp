@@ -328,6 +328,101 @@ static Status restrict_tail(EncoderDevice &D, EncodeLane &d, int device, bool re
   return Status();
 }
 
+// ---- the byte fallback (k_bytefb.h; the rule is in include/yttm_mi355x.h) -----------------------------------------------------------------
+// measure -> scan -> write into the lane's second pair of buffers (rs, the restriction's: the two passes run one after the other), which then
+// becomes the lane's encode result.  pending: the input IS that result; where the measure pass met no unk_id the write pass is skipped and the
+// result stays where it is.  Otherwise the input is the caller's and the result is installed as after an encode of n_sent sentences.
+static Status bytefb_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const int32_t *ids, const unsigned long long *off,
+                             const void *d_text, const void *d_soff, unsigned long long n_sent, unsigned long long n_ids, bool reverse, bool pending,
+                             unsigned long long *n_out, double *kernel_ms) {
+  return on_device(device, [&]() -> Status {
+    if (kernel_ms) *kernel_ms = 0;
+    if (n_out) *n_out = 0;
+    unsigned long long total = 0;
+    bool skip = false;
+    if (n_sent) {
+      const SubInput in{(const uint8_t *)d_text, (const unsigned long long *)d_soff, ids, off, n_sent, (int32_t)enc.bpe_state.special_tokens.unk_id, reverse ? 1 : 0};
+      const int32_t first = (int32_t)enc.vocab_size();
+      uint32_t saw = 0;
+      const Status s = two_pass_on_lane(
+          d, n_sent, d.rs.len, d.rs.off, kernel_ms, &total,
+          [&](bool write) {
+            if (write && skip) return;
+            if (!write) HIP_CHECK(hipMemsetAsync(d.fb.saw, 0, 4, d.st));
+            launch_bytefb(write, D.m, in, first, n_ids, d.rs.len, d.fb.saw, d.rs.off, d.rs.ids, d.st);
+            if (!write) HIP_CHECK(hipMemcpyAsync(&saw, d.fb.saw, 4, hipMemcpyDeviceToHost, d.st));  // (here once the scan has synchronised)
+          },
+          [] { return Status(); },
+          [&](unsigned long long need) {
+            skip = pending && !saw;  // (NOT need == n_ids: a run of one ASCII char keeps the total and changes the id)
+            if (skip) return;
+            d.rs.ids.grow((size_t)need + 4);
+            if (((uintptr_t)d.rs.ids.p & 15u) != 0) throw GpuError{"byte fallback: the output is not 16-byte aligned"};
+          });
+      if (!s.ok()) return s;
+      if (!skip) {
+        std::swap(d.res.ids, d.rs.ids);
+        std::swap(d.res.off, d.rs.off);
+      }
+    }
+    if (!pending) {
+      d.res.n_sent = n_sent;
+      d.res.made = true;
+    }
+    d.sp.valid = false;  // (spans belong to the ids they were made from)
+    d.res.n_ids = total;
+    if (n_out) *n_out = total;
+    D.bfb.stats[0] += 1;
+    if (skip) D.bfb.stats[1] += 1;
+    D.bfb.stats[2] += n_ids;
+    D.bfb.stats[3] += total;
+    return Status();
+  });
+}
+
+// The tail of encode_on_lane, behind the restriction's: with the setting on, the pass over the ids the encode has just left on the lane.  (The two
+// commute -- byte ids lie outside [0, V) and pass through E, unk_id is a leaf --, and the restriction first walks the shorter array.)
+static Status bytefb_tail(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_text, const void *d_soff, bool reverse,
+                          unsigned long long *n_ids_out, double *kernel_ms) {
+  if (!D.bfb.on.load()) return Status();
+  double ms = 0;
+  unsigned long long n = 0;
+  const Status s = bytefb_on_lane(enc, D, d, device, d.res.ids, d.res.off, d_text, d_soff, d.res.n_sent, d.res.n_ids, reverse, true, &n, kernel_ms ? &ms : nullptr);
+  if (!s.ok()) return s;
+  if (n_ids_out) *n_ids_out = n;
+  if (kernel_ms) *kernel_ms += ms;
+  return Status();
+}
+
+Status BaseEncoder::set_byte_fallback(bool on) const {
+  if (!dev_) return Status(2, "encoder has no device state");
+  if ((unsigned long long)vocab_size() > BFB_VOCAB_MAX) return Status(1, "set_byte_fallback: the vocabulary leaves no room for 256 byte ids");
+  EncoderDevice &D = *dev_;
+  std::lock_guard<std::mutex> lk0(D.lane[0].mu), lk1(D.lane[1].mu);  // (always in this order; a result already pending stays as it is)
+  D.bfb.on.store(on);
+  return Status();
+}
+bool BaseEncoder::byte_fallback() const { return dev_ && dev_->bfb.on.load(); }
+void BaseEncoder::byte_fallback_stats(unsigned long long out[4]) const {
+  for (int i = 0; i < 4; i++) out[i] = dev_ ? dev_->bfb.stats[i].load() : 0ull;
+}
+
+Status BaseEncoder::byte_fallback_ids_device(const void *d_ids, const void *d_id_offsets, const void *d_bytes, const void *d_text_offsets,
+                                             unsigned long long n_sent, unsigned long long n_ids, unsigned long long total_bytes, bool reverse,
+                                             unsigned long long *n_out, double *kernel_ms) const {
+  if (n_out) *n_out = 0;
+  StageClock ms(kernel_ms);
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (n_sent && (!d_id_offsets || !d_text_offsets)) return Status(2, "byte_fallback_ids_device: no offsets");
+  if (n_ids && !d_ids) return Status(2, "byte_fallback_ids_device: no ids");
+  if (total_bytes && !d_bytes) return Status(2, "byte_fallback_ids_device: no text");
+  if (((uintptr_t)d_ids & 3u) != 0) return Status(2, "byte_fallback_ids_device: the ids must be 4-byte aligned");
+  const Lane0 l(*dev_);
+  if (!dev_->bfb.on.load()) return Status(1, "byte_fallback_ids_device: byte fallback is not set");  // (before any work: what was pending stays)
+  return bytefb_on_lane(*this, *dev_, l.d, device_, (const int32_t *)d_ids, (const unsigned long long *)d_id_offsets, d_bytes, d_text_offsets, n_sent, n_ids,
+                        reverse, false, n_out, ms.next());
+}
+
 Status BaseEncoder::set_vocabulary(const uint8_t *allowed, unsigned long long n, unsigned long long *info) const {
   if (info) info[0] = info[1] = info[2] = 0;
   if (!dev_) return Status(2, "encoder has no device state");
@@ -424,6 +519,10 @@ Status encode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, i
     if (n_sent == 0) return Status();
     d.k5.counts.grow((size_t)n_sent);
     d.res.off.grow((size_t)n_sent + 1);
+    const auto tails = [&]() -> Status {  // both exits: the passes over the ids the encode has left, with the lane's own text and offsets
+      const Status r = restrict_tail(D, d, device, reverse, n_ids_out, kernel_ms);
+      return r.ok() ? bytefb_tail(enc, D, d, device, d_bytes, d_offsets, reverse, n_ids_out, kernel_ms) : r;
+    };
     EventPair ev(d.st, kernel_ms != nullptr);
     ev.start();
     // the word cache: no dropout (its draws are per occurrence), a batch worth the extra passes, a buffer the 8-byte loads can walk
@@ -435,7 +534,7 @@ Status encode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, i
       encode_cached(D, d, d_bytes, (const unsigned long long *)d_offsets, n_sent, total_bytes, max_sentence_bytes, bos, eos, reverse, n_ids_out);
       ev.stop(true);
       if (kernel_ms) *kernel_ms = ev.elapsed_ms();
-      return restrict_tail(D, d, device, reverse, n_ids_out, kernel_ms);
+      return tails();
     }
     k5_pass(D, d, d_bytes, (const unsigned long long *)d_offsets, nullptr, n_sent, total_bytes, max_sentence_bytes, bos, eos, reverse, dropout_prob,
             d.k5.counts);
@@ -447,7 +546,7 @@ Status encode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, i
     if (kernel_ms) *kernel_ms = ev.elapsed_ms();
     d.res.n_ids = total;
     if (n_ids_out) *n_ids_out = total;
-    return restrict_tail(D, d, device, reverse, n_ids_out, kernel_ms);
+    return tails();
   });
 }
 
@@ -846,6 +945,10 @@ Status BaseEncoder::encode_as_subwords(const uint8_t *bytes, const unsigned long
 }
 
 Status BaseEncoder::id_to_subword(int id, std::string *subword, bool replace_space) const {  // bpe.cpp:1774-1807
+  if (bytefb_is_byte_id(id, (uint32_t)vocab_size(), byte_fallback())) {  // (the name; decode() and the decode table put the raw byte)
+    *subword = bytefb_name((uint32_t)(id - vocab_size()));
+    return Status();
+  }
   if (id < 0 || vocab_size() <= id)
     return Status(1, "id must be in the range [0, vocab_size - 1]. Current value: vocab_size = " + std::to_string(vocab_size()) +
                          "; id=" + std::to_string(id) + ";");
@@ -872,6 +975,7 @@ int BaseEncoder::subword_to_id(const std::string &token) const {  // bpe.cpp:180
   if (PAD_TOKEN == token) return sp.pad_id;
   if (BOS_TOKEN == token) return sp.bos_id;
   if (EOS_TOKEN == token) return sp.eos_id;
+  if (byte_fallback() && bytefb_parse_name(token) >= 0) return vocab_size() + bytefb_parse_name(token);
   auto it = reversed_recipe.find(token);
   if (it != reversed_recipe.end()) return (int)it->second;
   return sp.unk_id;
@@ -883,6 +987,11 @@ Status BaseEncoder::decode(const std::vector<int> &ids, std::string *sentence, c
   for (int id : ids) {
     std::string subword;
     if (!ignore_ids || ignore_ids->count(id) == 0) {
+      if (bytefb_is_byte_id(id, (uint32_t)vocab_size(), byte_fallback())) {  // the raw byte, and no strip rule
+        *sentence += (char)(id - vocab_size());
+        first_iter = false;
+        continue;
+      }
       Status status = id_to_subword(id, &subword, true);
       if (!status.ok()) return status;
       *sentence += subword;

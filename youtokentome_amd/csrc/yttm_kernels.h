@@ -475,6 +475,13 @@ struct RestrictTable {
 void launch_restrict(bool write, const int32_t *ids, const unsigned long long *off, unsigned long long n_sent, unsigned long long n_ids,
                      const RestrictTable &tb, uint32_t *out_len, const unsigned long long *out_off, int32_t *out, hipStream_t st);
 
+// ---- the byte fallback (k_bytefb.h, compiled with k_encode.hip): measure -> launch_exclusive_scan -> write ----
+// in: the ids and the text they were made from (SubInput).  Every unk_id that stands for an unknown run of its sentence -> the ids first + b of the
+// run's valid bytes; out_len[n_sent], then the ids at out[out_off[s] ..), out_off the exclusive scan of out_len.  *saw (holds 0 before the measure
+// pass) becomes 1 where the ids hold an unk_id at all: only where it stayed 0 may the write pass be skipped.  out: 16-byte aligned.  n_ids sizes the groups.
+void launch_bytefb(bool write, const EncModel &m, const SubInput &in, int32_t first, unsigned long long n_ids, uint32_t *out_len, uint32_t *saw,
+                   const unsigned long long *out_off, int32_t *out, hipStream_t st);
+
 // ---- training blocks (k_blocks.h, compiled with k_encode.hip): flags -> scan -> (whole: orbit) -> measure -> scan -> write (-> keep) ----
 // The sequence a call packs: the open row's m sentences (f ids, open_off[m + 1]) followed by the call's S sentences (off[S + 1], off[0] = 0), as one
 // stream of `total` = f + K ids in which sentence i starts at voff(i).  Only read.

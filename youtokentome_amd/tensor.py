@@ -285,10 +285,8 @@ def decode_text_tensor(bpe, text, ignore_ids=None, as_str=True):
     return _take_text(torch, core, dev, n, n_text, False)
 
 
-def restrict_tensor(bpe, ids, lengths=None, offsets=None, reverse=False, padded=None, width=None, pad_id=None):
-    torch = _torch()
-    core = bpe.bpe_cython
-    dev = _device_of(bpe, None)
+def _ragged_ids(torch, dev, ids, lengths, offsets, padded):
+    """ids as a 2-D matrix (with lengths) or 1-D with offsets -> (int32 ids back to back, offsets [n + 1], n, padded: the form the result takes)"""
     _check_on(ids, dev, "ids")
     if ids.dtype == torch.int64:
         ids = ids.to(torch.int32)
@@ -327,9 +325,32 @@ def restrict_tensor(bpe, ids, lengths=None, offsets=None, reverse=False, padded=
             padded = False
     else:
         raise ValueError("ids must be 1-D (with offsets) or 2-D (padded)")
+    return ids, offsets, n, padded
+
+
+def restrict_tensor(bpe, ids, lengths=None, offsets=None, reverse=False, padded=None, width=None, pad_id=None):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    ids, offsets, n, padded = _ragged_ids(torch, dev, ids, lengths, offsets, padded)
     pad_id = _pad_id(bpe, padded, pad_id)
     n_in = int(offsets[-1]) if n else 0
     n_out, _ = _synced(torch, dev, core.restrict_ids_device_raw, ids.data_ptr(), offsets.data_ptr(), n, n_in, reverse)
+    return _take_encoded(torch, core, dev, n, n_out, padded, width, pad_id)
+
+
+def byte_fallback_tensor(bpe, ids, text, lengths=None, offsets=None, reverse=False, padded=None, width=None, pad_id=None):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    ids, offsets, n, padded = _ragged_ids(torch, dev, ids, lengths, offsets, padded)
+    d_bytes, d_soff, n_text, total, _ = _sentences_on(torch, text, dev)
+    if n_text != n:
+        raise ValueError("text holds %d sentences, ids %d" % (n_text, n))
+    pad_id = _pad_id(bpe, padded, pad_id)
+    n_in = int(offsets[-1]) if n else 0
+    n_out, _ = _synced(torch, dev, core.byte_fallback_ids_device_raw, ids.data_ptr(), offsets.data_ptr(), d_bytes.data_ptr(), d_soff.data_ptr(), n, n_in,
+                       total, reverse)
     return _take_encoded(torch, core, dev, n, n_out, padded, width, pad_id)
 
 
@@ -337,7 +358,7 @@ def id_counts_tensor(bpe, ids=None, n_bins=None, accumulate=False):
     torch = _torch()
     core = bpe.bpe_cython
     dev = _device_of(bpe, None)
-    n_bins = int(n_bins) if n_bins is not None else bpe.vocab_size()
+    n_bins = int(n_bins) if n_bins is not None else core.id_bound()
     if n_bins < 1:
         raise ValueError("n_bins must be positive")
     if ids is None:

@@ -6,7 +6,9 @@ Two more commands work file to file through the device, with the same bytes as t
 PREFIX.ids / PREFIX.off; subword and id_text: the text `encode --output_type subword` / `id` prints) and `decode_file` (a file of decimal ids
 -> the text `decode` prints).  `count_file` prints how often a text file uses every token, counted on the device: the lines of `vocab` with a
 third column.  `encode`, `encode_file` and `count_file` take `--vocabulary FILE --vocabulary_threshold N`: FILE is what `count_file` wrote, and tokens
-it counts fewer than N times are split back into smaller pieces (subword-nmt's --vocabulary / --vocabulary-threshold).
+it counts fewer than N times are split back into smaller pieces (subword-nmt's --vocabulary / --vocabulary-threshold).  `encode`, `encode_file`,
+`count_file`, `blocks_file`, `decode` and `decode_file` take `--byte_fallback`: characters outside the model's alphabet are the ids of their UTF-8
+bytes, vocab_size + b, printed as <0xNN>, instead of one <UNK> per run (SentencePiece's byte_fallback).
 
 The loops themselves are C++ (youtokentome_amd/csrc/host_cli.cpp, behind yttm_encode_cli / yttm_decode_cli / yttm_vocab_cli):
 stdin and stdout stay bytes end to end, invalid UTF-8 included."""
@@ -28,6 +30,11 @@ def _vocabulary_options(f):
                         help="A file `count_file` wrote (id<TAB>subword<TAB>count): encode with the tokens it counts often enough only.")(f)
 
 
+def _byte_fallback_option(f):
+    return click.option("--byte_fallback", is_flag=True,
+                        help="Characters outside the model's alphabet as the ids of their UTF-8 bytes (vocab_size + byte, <0xNN>) instead of <UNK>.")(f)
+
+
 def _set_vocabulary(core, path, threshold):
     """the vocabulary file -> the allowed set of the encoder; ids missing from the file count 0"""
     if path is None:
@@ -45,6 +52,8 @@ def _set_vocabulary(core, path, threshold):
                 i, n = int(cols[0]), int(cols[2])
             except ValueError:
                 raise click.ClickException("%s:%d: expected id<TAB>subword<TAB>count" % (path, no))
+            if len(vocab) <= i < len(vocab) + 256 and cols[1] == b"<0x%02X>" % (i - len(vocab)):
+                continue  # (a file `count_file --byte_fallback` wrote: a byte id is no token of the vocabulary, it is neither allowed nor split)
             if not 0 <= i < len(vocab) or vocab[i].encode() != cols[1]:
                 raise click.ClickException("%s:%d: id %d is not this model's %r: the vocabulary belongs to another model" % (
                     path, no, i, cols[1].decode(errors="replace")))
@@ -79,11 +88,13 @@ def bpe(data, model, vocab_size, coverage, n_threads, pad_id, unk_id, bos_id, eo
 @click.option("--dropout_prob", type=click.FLOAT, default=0, show_default=True,
               help="BPE-dropout probability (the probability of a merge being dropped)")
 @_vocabulary_options
-def encode(model, output_type, n_threads, bos, eos, reverse, stream, dropout_prob, vocabulary, vocabulary_threshold):
+@_byte_fallback_option
+def encode(model, output_type, n_threads, bos, eos, reverse, stream, dropout_prob, vocabulary, vocabulary_threshold, byte_fallback):
     """Encode text to ids or subwords."""
     if n_threads < -1 or n_threads == 0:  # yttm_cli.py:110-114
         raise ValueError('Invalid value for "--n_threads": must be -1 or positive integer, not "%d"' % n_threads)
     core = _Core(model, n_threads)
+    core.set_byte_fallback(byte_fallback)
     _set_vocabulary(core, vocabulary, vocabulary_threshold)
     core.encode_cli(output_type, stream, bos, eos, reverse, dropout_prob)  # the C++ loop: yttm_encode_cli (host_cli.cpp)
 
@@ -101,9 +112,11 @@ def encode(model, output_type, n_threads, bos, eos, reverse, stream, dropout_pro
 @click.option("--dropout_prob", type=click.FLOAT, default=0, show_default=True,
               help="BPE-dropout probability (the probability of a merge being dropped)")
 @_vocabulary_options
-def encode_file(model, input_path, output, output_type, bos, eos, reverse, dropout_prob, vocabulary, vocabulary_threshold):
+@_byte_fallback_option
+def encode_file(model, input_path, output, output_type, bos, eos, reverse, dropout_prob, vocabulary, vocabulary_threshold, byte_fallback):
     """Encode a text file to binary ids and line offsets, or to a text file of subwords."""
     core = _Core(model)
+    core.set_byte_fallback(byte_fallback)
     _set_vocabulary(core, vocabulary, vocabulary_threshold)
     if output_type == "subword":  # the same pipeline with the formatter behind the encode: yttm_encode_file_subword (host_lines.cpp)
         core.encode_file_subword(input_path, output, bos=bos, eos=eos, reverse=reverse, dropout_prob=dropout_prob)
@@ -127,9 +140,11 @@ def _parse_ignore_ids(ctx, param, value):
 @click.option("--model", type=click.Path(exists=True), required=True, help="Path to file with learned model.")
 @click.option("--ignore_ids", type=click.STRING, callback=_parse_ignore_ids, required=False,
               help="List of indices to ignore for decoding. Example: --ignore_ids=1,2,3")
-def decode(model, ignore_ids):
+@_byte_fallback_option
+def decode(model, ignore_ids, byte_fallback):
     """Decode ids to text."""
     core = _Core(model)
+    core.set_byte_fallback(byte_fallback)
     core.decode_cli(ignore_ids)
 
 
@@ -139,9 +154,11 @@ def decode(model, ignore_ids):
 @click.option("--output", type=click.Path(), required=True, help="The text file to write: what `decode` prints for the input.")
 @click.option("--ignore_ids", type=click.STRING, callback=_parse_ignore_ids, required=False,
               help="List of indices to ignore for decoding. Example: --ignore_ids=1,2,3")
-def decode_file(model, input_path, output, ignore_ids):
+@_byte_fallback_option
+def decode_file(model, input_path, output, ignore_ids, byte_fallback):
     """Decode a text file of ids to a text file."""
     core = _Core(model)
+    core.set_byte_fallback(byte_fallback)
     core.decode_file(input_path, output, ignore_ids=ignore_ids)  # the C++ pipeline: yttm_decode_file (host_lines.cpp)
 
 
@@ -154,14 +171,17 @@ def decode_file(model, input_path, output, ignore_ids):
 @click.option("--dropout_prob", type=click.FLOAT, default=0, show_default=True,
               help="BPE-dropout probability (the probability of a merge being dropped)")
 @_vocabulary_options
-def count_file(model, input_path, output, bos, eos, dropout_prob, vocabulary, vocabulary_threshold):
+@_byte_fallback_option
+def count_file(model, input_path, output, bos, eos, dropout_prob, vocabulary, vocabulary_threshold, byte_fallback):
     """Print how often the file uses every token: id<TAB>subword<TAB>count, in id order."""
     import sys
     core = _Core(model)
+    core.set_byte_fallback(byte_fallback)
     _set_vocabulary(core, vocabulary, vocabulary_threshold)
     counts = core.encode_file_counts(input_path, bos=bos, eos=eos, dropout_prob=dropout_prob)  # the C++ pipeline: yttm_encode_file_counts (host_lines.cpp)
     # (the first two columns are those of `vocab`: the id and id_to_subword(id) as it stands)
-    text = b"".join(b"%d\t%s\t%d\n" % (i, piece.encode(), int(counts[i])) for i, piece in enumerate(core.vocab()))
+    pieces = core.vocab() + [core.id_to_subword(i) for i in range(core.vocab_size(), core.id_bound())]  # (with --byte_fallback: 256 rows <0xNN> more)
+    text = b"".join(b"%d\t%s\t%d\n" % (i, piece.encode(), int(counts[i])) for i, piece in enumerate(pieces))
     if output is None:
         sys.stdout.flush()
         sys.stdout.buffer.write(text)
@@ -185,9 +205,11 @@ def count_file(model, input_path, output, bos, eos, dropout_prob, vocabulary, vo
               help="BPE-dropout probability (the probability of a merge being dropped)")
 @click.option("--drop_last", is_flag=True, help="Discard the incomplete last row instead of padding it with <PAD>.")
 @_vocabulary_options
-def blocks_file(model, input_path, output, seq_len, mode, bos, eos, reverse, dropout_prob, drop_last, vocabulary, vocabulary_threshold):
+@_byte_fallback_option
+def blocks_file(model, input_path, output, seq_len, mode, bos, eos, reverse, dropout_prob, drop_last, vocabulary, vocabulary_threshold, byte_fallback):
     """Encode a text file and pack it into fixed-length training rows."""
     core = _Core(model)
+    core.set_byte_fallback(byte_fallback)
     _set_vocabulary(core, vocabulary, vocabulary_threshold)
     pad = core.subword_to_id("<PAD>")
     if not drop_last and (pad == -1 or core.id_to_subword(pad) != "<PAD>"):
