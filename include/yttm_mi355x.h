@@ -410,6 +410,62 @@ int yttm_byte_fallback_ids_device(yttm_encoder *enc, const void *d_ids, const vo
                                   uint64_t n_sent, uint64_t n_ids, uint64_t total_bytes, int reverse, uint64_t *n_out, double *kernel_ms, char *err,
                                   int errlen);
 
+/* Added tokens (SentencePiece's user_defined_symbols, Hugging Face's added tokens; the reference has no counterpart): literal byte strings --
+ * language tags, separators, <mask>, sentinels, chat markers -- that are one id each and never split.  A setting of an encoder, as the restricted
+ * vocabulary and the byte fallback are; the model file does not change.  Let V = yttm_vocab_size(enc) and A = V + 256.
+ * The setting: yttm_encoder_set_added_tokens takes n byte strings t_0 .. t_{n-1} as a blob plus tok_offsets[n + 1], in the caller's order.
+ *   1 <= n <= 4096; each string is 1 .. 255 bytes of valid UTF-8 without a code point the encoder treats as white space (0x0A included) and
+ *   without U+2581; the strings are pairwise different; A + n lies within the encoder's id limit.  A string may be a prefix or a substring of
+ *   another.  Anything else: code 1 with a message, and the setting stays as it was.  blob == NULL clears the setting.  The call waits for both
+ *   of the encoder's lanes, as yttm_encoder_set_vocabulary does; a result already pending is not changed.  The id of t_k is A + k, whether the
+ *   byte fallback is on or off.
+ * Matching is byte-wise and per sentence text[off[s] .. off[s + 1]): leftmost first, the longest at a position, non-overlapping.
+ *   p = off[s]; while p < off[s + 1]: among the t_k with text[p .. p + len_k) == t_k and p + len_k <= off[s + 1] take the longest; if there is
+ *   one it is a match (p, k) and p += len_k, otherwise p += 1.  A match never crosses a sentence boundary.  A sentence with the matches
+ *   m_1 .. m_j is cut into the segments g_0 .. g_j: the text in front of, between and behind the matches; a segment may be empty.
+ * Encode, setting on: the forward result of the sentence is
+ *     [bos_id]? ++ E(g_0) ++ [A + k(m_1)] ++ E(g_1) ++ ... ++ [A + k(m_j)] ++ E(g_j) ++ [eos_id]?
+ *   where E(g) is the ids the same encoder makes for g as a sentence of its own with bos = eos = reverse = false, under the encoder's other
+ *   settings (the restricted vocabulary, the byte fallback): E of an empty or all-space segment is [], a segment that starts inside a word gets
+ *   its own U+2581.  reverse stores the reverse of the forward result as a whole, bos and eos included.  Dropout: the segments
+ *   are encoded as ONE batch, the refined batch, whose sentences are g_0, m_1, g_1, .., m_j, g_j of every sentence in text order (2 j + 1 per
+ *   sentence), in one pass under the call's salt: with YTTM_DROPOUT_SEED pinned the ids are exactly the join of what yttm_encode_device returns
+ *   for that refined batch with the setting off.  Where no sentence of a call holds a match the refined batch is the batch and the ids are the
+ *   setting-off ids.  n_ids and kernel_ms include all passes (k_added.h: the split, the encode of the refined batch, the join).
+ * Restricted vocabulary: an added id lies outside [0, V) and passes through the restriction.
+ * Decode: an id in [A, A + n) is valid, its piece is t_k verbatim, no strip rule applies to it, and it can be named in ignore_ids.  Ids >= A + n
+ *   or < 0 keep the error and its message; [V, A) stays an error while the byte fallback is off.
+ * Names: yttm_id_to_subword(A + k) is t_k, yttm_subword_to_id(t_k) is A + k.  yttm_vocab_size and yttm_vocabulary do not change.
+ * Counts: n_bins == 0 means A + n, and yttm_encode_file_counts writes A + n + 1 integers.
+ * Id text, blocks, batches, padded copies, tensors, the sub-batches of a large host batch and file pieces read the pending result or encode
+ *   through the same path: they get the setting without code of their own (file pieces are cut at newlines, and no token holds one).
+ * Spans are not defined with the setting on: yttm_spans_device, yttm_spans_text_device and yttm_encode_as_ids_spans return code 1 with a message
+ *   before any work, and what was pending stays.
+ * SUBWORD text (yttm_subword_device, yttm_subword_text_device, yttm_encode_file_subword, yttm_encode_as_subwords, yttm_encode_cli) maps the k-th
+ *   unk_id of a sentence to the k-th unknown run of its ORIGINAL text, and a match's text can add to a run or join two: these routes are defined
+ *   only with the byte fallback on as well (then no unk_id is left and the text is never consulted); an added id prints as t_k and a space.
+ *   With the byte fallback off they return code 1 before any work.
+ * Setting off: every call behaves as if the setting did not exist.
+ *
+ * yttm_encoder_added_tokens: the set as a blob and tok_offsets[n + 1] (both released with yttm_free) and n; n == 0 while nothing is set.
+ * yttm_encoder_added_tokens_stats: {calls with the setting on, calls without a match (the split's write pass and the join were skipped),
+ * matches, sub-sentences encoded} since the encoder was made. */
+int yttm_encoder_set_added_tokens(yttm_encoder *enc, const uint8_t *blob, const uint64_t *tok_offsets, uint64_t n, char *err, int errlen);
+int yttm_encoder_added_tokens(yttm_encoder *enc, char **blob, uint64_t **tok_offsets, uint64_t *n);
+int yttm_encoder_added_tokens_stats(yttm_encoder *enc, uint64_t out[4]);
+/* The split alone, of a text in HBM: sentence s = d_bytes[d_offsets[s] .. d_offsets[s + 1]), total_bytes in all -> the refined batch.  It lives
+ * in a slot of the encoder's own that the next split replaces: uint64 sub_first[n_sent + 1] (the first sub-sentence of sentence s; sub_first[n_sent]
+ * = *n_sub = n_sent + 2 * *n_matches), uint64 sub_offsets[n_sub + 1] (sub-sentence i = d_bytes[sub_offsets[i] .. sub_offsets[i + 1])) and int32
+ * tok[n_sub] (the token's index for a match, -1 for a segment).  The inputs are only read.  Setting off: code 1, and nothing is replaced.
+ * _fetch copies the arrays to host memory, _copy_device into device memory the caller owns; n_sent and n_sub must be the slot's (code 1
+ * otherwise); a null pointer is skipped.  kernel_ms (optional) = measure + scan + write. */
+int yttm_added_split_device(yttm_encoder *enc, const void *d_bytes, const void *d_offsets, uint64_t n_sent, uint64_t total_bytes, uint64_t *n_sub,
+                            uint64_t *n_matches, double *kernel_ms, char *err, int errlen);
+int yttm_added_split_fetch(yttm_encoder *enc, uint64_t *sub_first, uint64_t *sub_offsets, int32_t *tok, uint64_t n_sent, uint64_t n_sub, char *err,
+                           int errlen);
+int yttm_added_split_copy_device(yttm_encoder *enc, void *d_sub_first, void *d_sub_offsets, void *d_tok, uint64_t n_sent, uint64_t n_sub, char *err,
+                                 int errlen);
+
 /* Word-level encode cache (SURVEY.md 8f "N4"; the reference has no counterpart: bpe.cpp:1497-1632 encodes every word occurrence).
  * mode 0: every batch goes straight through the encode kernel; 1: distinct words are encoded once whenever that is possible
  * (dropout_prob == 0); 2 (default): the same for batches of at least min_bytes.  The ids are identical either way.

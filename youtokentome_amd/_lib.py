@@ -30,6 +30,8 @@ EXPORTS = [
     "yttm_id_counts_device", "yttm_id_counts_ids_device", "yttm_id_counts_fetch", "yttm_id_counts_copy_device", "yttm_encode_file_counts",
     "yttm_encoder_set_vocabulary", "yttm_encoder_vocabulary_stats", "yttm_restrict_ids_device",
     "yttm_encoder_set_byte_fallback", "yttm_encoder_byte_fallback", "yttm_encoder_byte_fallback_stats", "yttm_byte_fallback_ids_device",
+    "yttm_encoder_set_added_tokens", "yttm_encoder_added_tokens", "yttm_encoder_added_tokens_stats", "yttm_added_split_device", "yttm_added_split_fetch",
+    "yttm_added_split_copy_device",
     "yttm_blocks_device", "yttm_blocks_ids_device", "yttm_blocks_flush", "yttm_blocks_open", "yttm_blocks_discard", "yttm_blocks_fetch", "yttm_blocks_copy_device",
     "yttm_encode_file_blocks",
     "yttm_batches_plan_device", "yttm_batches_plan_lengths_device", "yttm_batches_gather_device", "yttm_batches_gather_ids_device", "yttm_batches_fetch",
@@ -107,6 +109,12 @@ def load():
     L.yttm_encoder_byte_fallback.argtypes = [cvp]
     L.yttm_encoder_byte_fallback_stats.argtypes = [cvp, u64p]
     L.yttm_byte_fallback_ids_device.argtypes = [cvp, cvp, cvp, cvp, cvp, C.c_uint64, C.c_uint64, C.c_uint64, ci, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_encoder_set_added_tokens.argtypes = [cvp, u8p, u64p, C.c_uint64, cs, ci]
+    L.yttm_encoder_added_tokens.argtypes = [cvp, C.POINTER(cvp), C.POINTER(u64p), u64p]
+    L.yttm_encoder_added_tokens_stats.argtypes = [cvp, u64p]
+    L.yttm_added_split_device.argtypes = [cvp, cvp, cvp, C.c_uint64, C.c_uint64, u64p, u64p, C.POINTER(cd), cs, ci]
+    L.yttm_added_split_fetch.argtypes = [cvp, u64p, u64p, i32p, C.c_uint64, C.c_uint64, cs, ci]
+    L.yttm_added_split_copy_device.argtypes = [cvp, cvp, cvp, cvp, C.c_uint64, C.c_uint64, cs, ci]
     L.yttm_blocks_device.argtypes = [cvp, C.c_uint64, C.c_uint64, ci, C.c_int32, ci, u64p, u64p, C.POINTER(cd), cs, ci]
     L.yttm_blocks_ids_device.argtypes = [cvp, cvp, cvp, C.c_uint64, C.c_uint64, C.c_uint64, ci, C.c_int32, ci, u64p, u64p, C.POINTER(cd), cs, ci]
     L.yttm_blocks_flush.argtypes = [cvp, C.c_int32, u64p, u64p, C.POINTER(cd), cs, ci]

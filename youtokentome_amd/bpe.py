@@ -146,8 +146,10 @@ class _Core:
         return bool(_lib.load().yttm_encoder_byte_fallback(self._h))
 
     def id_bound(self):
-        """the ids the decode, the names and the counts know: vocab_size(), with the byte fallback on 256 more"""
-        return self.vocab_size() + (256 if self.byte_fallback() else 0)
+        """the ids the decode, the names and the counts know: vocab_size(), with the byte fallback on 256 more; with n added tokens
+        vocab_size() + 256 + n whether the byte fallback is on or not"""
+        n = self.n_added_tokens()
+        return self.vocab_size() + 256 + n if n else self.vocab_size() + (256 if self.byte_fallback() else 0)
 
     def byte_fallback_stats(self):
         """-> (calls of the pass, calls whose write pass was skipped, ids in, ids out)"""
@@ -161,6 +163,65 @@ class _Core:
         self._check(_lib.load().yttm_byte_fallback_ids_device(self._h, C.c_void_p(d_ids), C.c_void_p(d_id_offsets), C.c_void_p(d_bytes), C.c_void_p(d_text_offsets),
                                                               n_sent, n_ids, total_bytes, int(bool(reverse)), C.byref(n), C.byref(ms), err, _lib.ERRLEN), err)
         return n.value, ms.value
+
+    # ---- added tokens (include/yttm_mi355x.h "Added tokens"): literal strings that are one id each, vocab_size() + 256 + k, and never split
+    def set_added_tokens(self, tokens=None):
+        """tokens: a sequence of str or bytes in the order of their ids, or None to clear the setting"""
+        err = _err()
+        if tokens is None:
+            self._check(_lib.load().yttm_encoder_set_added_tokens(self._h, None, None, 0, err, _lib.ERRLEN), err)
+            return
+        if isinstance(tokens, (str, bytes)):
+            raise TypeError("tokens must be a sequence of strings, not one string")
+        raw = [t.encode() if isinstance(t, str) else bytes(t) for t in tokens]
+        off = np.zeros(len(raw) + 1, np.uint64)
+        off[1:] = np.cumsum([len(t) for t in raw], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(raw) + b"\0", np.uint8)  # (never empty: an empty token is the library's error, with its message)
+        self._check(_lib.load().yttm_encoder_set_added_tokens(self._h, blob.ctypes.data_as(_lib.u8p), off.ctypes.data_as(_lib.u64p), len(raw), err,
+                                                              _lib.ERRLEN), err)
+
+    def added_tokens_raw(self):
+        """the tokens as bytes, in the order of their ids ([] while nothing is set)"""
+        L = _lib.load()
+        blob_p, off, n = C.c_void_p(), _lib.u64p(), C.c_uint64()
+        L.yttm_encoder_added_tokens(self._h, C.byref(blob_p), C.byref(off), C.byref(n))
+        oo = _take(off, n.value + 1, C.c_uint64, np.uint64)
+        raw = C.string_at(blob_p, int(oo[-1]))
+        L.yttm_free(blob_p)
+        return [raw[int(oo[i]):int(oo[i + 1])] for i in range(n.value)]
+
+    def n_added_tokens(self):
+        L = _lib.load()
+        blob_p, off, n = C.c_void_p(), _lib.u64p(), C.c_uint64()
+        L.yttm_encoder_added_tokens(self._h, C.byref(blob_p), C.byref(off), C.byref(n))
+        L.yttm_free(blob_p)
+        L.yttm_free(C.cast(off, C.c_void_p))
+        return int(n.value)
+
+    def added_tokens_stats(self):
+        """-> (calls with the setting on, calls without a match, matches, sub-sentences encoded)"""
+        out = (C.c_uint64 * 4)()
+        _lib.load().yttm_encoder_added_tokens_stats(self._h, out)
+        return tuple(int(v) for v in out)
+
+    def added_split_device_raw(self, d_bytes, d_offsets, n_sent, total_bytes):
+        """-> (n_sub, n_matches, kernel_ms); the three arrays stay in the encoder until fetch_added_split / copy_added_split takes them"""
+        ns, nm, ms, err = C.c_uint64(), C.c_uint64(), C.c_double(), _err()
+        self._check(_lib.load().yttm_added_split_device(self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n_sent, total_bytes, C.byref(ns), C.byref(nm),
+                                                        C.byref(ms), err, _lib.ERRLEN), err)
+        return ns.value, nm.value, ms.value
+
+    def fetch_added_split(self, n_sent, n_sub):
+        """-> (sub_first uint64 [n_sent + 1], sub_offsets uint64 [n_sub + 1], tok int32 [n_sub])"""
+        first, off, tok, err = np.zeros(n_sent + 1, np.uint64), np.zeros(n_sub + 1, np.uint64), np.zeros(n_sub, np.int32), _err()
+        self._check(_lib.load().yttm_added_split_fetch(self._h, first.ctypes.data_as(_lib.u64p), off.ctypes.data_as(_lib.u64p), tok.ctypes.data_as(_lib.i32p),
+                                                       n_sent, n_sub, err, _lib.ERRLEN), err)
+        return first, off, tok
+
+    def copy_added_split(self, d_first, d_off, d_tok, n_sent, n_sub):
+        err = _err()
+        self._check(_lib.load().yttm_added_split_copy_device(self._h, C.c_void_p(d_first), C.c_void_p(d_off), C.c_void_p(d_tok), n_sent, n_sub, err,
+                                                             _lib.ERRLEN), err)
 
     # ---- packed fast path (SURVEY.md N2): bytes + offsets -> numpy ids + offsets
     def encode_packed(self, blob: bytes, offsets, bos=False, eos=False, reverse=False, dropout_prob=0.0):
@@ -968,6 +1029,34 @@ class BPE:
         becomes the run's byte ids; an <UNK> without a run stays.  Needs the setting on.  The result as restrict_tensor gives it."""
         from . import tensor
         return tensor.byte_fallback_tensor(self, ids, text, lengths=lengths, offsets=offsets, reverse=reverse, padded=padded, width=width, pad_id=pad_id)
+
+    # ---- added tokens: literal strings that are one id each and never split (include/yttm_mi355x.h "Added tokens"; SentencePiece's
+    # user_defined_symbols, Hugging Face's added tokens)
+    def set_added_tokens(self, tokens=None):
+        """tokens: up to 4096 different strings of 1 .. 255 bytes without white space or U+2581 -- language tags, separators, <mask>, sentinels,
+        chat markers.  Token k is the id vocab_size() + 256 + k (behind the byte fallback's ids, whether that is on or not).  Every later encode of
+        this object -- ids, tensors, id text, counts, blocks, batches, files -- matches them in the text (leftmost first, the longest at a
+        position, never across a sentence's end) and gives each match as its one id; the text between the matches is encoded as sentences of
+        its own.  decode, id_to_subword, subword_to_id and the counts know the ids.  The model file and vocab_size() do not change.  Spans are
+        not defined while tokens are set, SUBWORD output only with the byte fallback on as well.  None (the default) clears the setting."""
+        self.bpe_cython.set_added_tokens(tokens)
+
+    def added_tokens(self):
+        """a dict from token to id in the order of the ids, or None while nothing is set"""
+        raw = self.bpe_cython.added_tokens_raw()
+        first = self.vocab_size() + 256
+        return {t.decode(): first + k for k, t in enumerate(raw)} if raw else None
+
+    def added_tokens_stats(self):
+        """(calls with the setting on, calls without a match, matches, sub-sentences encoded) since this object was made"""
+        return self.bpe_cython.added_tokens_stats()
+
+    def split_added_tensor(self, text, offsets=None):
+        """The matcher alone: text a list of str, or a uint8 tensor on the device with int64 offsets [n + 1].  Returns three device tensors:
+        sub_first int64 [n + 1] (the first sub-sentence of every sentence), sub_offsets int64 [n_sub + 1] (byte offsets into the text) and tok
+        int32 [n_sub] (the token's index for a match, -1 for the text in front of, between and behind the matches).  Needs tokens set."""
+        from . import tensor
+        return tensor.split_added_tensor(self, text, offsets)
 
     def restrict_tensor(self, ids, lengths=None, offsets=None, reverse: bool = False, padded: Optional[bool] = None, width: Optional[int] = None,
                         pad_id: Optional[int] = None):

@@ -507,6 +507,37 @@ int yttm_byte_fallback_ids_device(yttm_encoder *h, const void *d_ids, const void
   return finish(s, err, errlen);
 }
 
+int yttm_encoder_set_added_tokens(yttm_encoder *h, const uint8_t *blob, const uint64_t *tok_offsets, uint64_t n, char *err, int errlen) {
+  return finish(h->enc->set_added_tokens(blob, (const unsigned long long *)tok_offsets, n), err, errlen);
+}
+int yttm_encoder_added_tokens(yttm_encoder *h, char **blob, uint64_t **tok_offsets, uint64_t *n) {
+  const std::vector<std::string> toks = h->enc->added_tokens();
+  pack_strings(toks, blob, tok_offsets);
+  if (n) *n = toks.size();
+  return 0;
+}
+int yttm_encoder_added_tokens_stats(yttm_encoder *h, uint64_t out[4]) {
+  unsigned long long o4[4] = {0, 0, 0, 0};
+  h->enc->added_tokens_stats(o4);
+  for (int i = 0; i < 4; i++) out[i] = o4[i];
+  return 0;
+}
+int yttm_added_split_device(yttm_encoder *h, const void *d_bytes, const void *d_offsets, uint64_t n_sent, uint64_t total_bytes, uint64_t *n_sub,
+                            uint64_t *n_matches, double *kernel_ms, char *err, int errlen) {
+  unsigned long long ns = 0, nm = 0;
+  Status s = h->enc->added_split_device(d_bytes, d_offsets, n_sent, total_bytes, &ns, &nm, kernel_ms);
+  if (n_sub) *n_sub = ns;
+  if (n_matches) *n_matches = nm;
+  return finish(s, err, errlen);
+}
+int yttm_added_split_fetch(yttm_encoder *h, uint64_t *sub_first, uint64_t *sub_offsets, int32_t *tok, uint64_t n_sent, uint64_t n_sub, char *err, int errlen) {
+  return finish(h->enc->take_added_split(sub_first, sub_offsets, tok, n_sent, n_sub, false), err, errlen);
+}
+int yttm_added_split_copy_device(yttm_encoder *h, void *d_sub_first, void *d_sub_offsets, void *d_tok, uint64_t n_sent, uint64_t n_sub, char *err,
+                                 int errlen) {
+  return finish(h->enc->take_added_split(d_sub_first, d_sub_offsets, d_tok, n_sent, n_sub, true), err, errlen);
+}
+
 int yttm_encoder_set_cache(yttm_encoder *h, int mode, uint64_t min_bytes) {
   h->enc->set_cache(mode, min_bytes);
   return 0;

@@ -6,7 +6,10 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <unordered_map>
+#include <vector>
 
+#include "added_plan.h"
 #include "bytefb_plan.h"
 #include "gpu_ctx.h"
 #include "host_core.h"
@@ -71,6 +74,11 @@ struct EncodeLane {
   struct {  // the byte fallback (k_bytefb.h) writes into rs's buffers too, one pass after the other; saw[0]: the measure pass met an unk_id
     DevBuf<uint32_t> saw;
   } fb;
+  struct {  // the added tokens (k_added.h): the split of the batch in flight -- cnt[n_sent], first[n_sent + 1], the refined off[n_sub + 1], tok[n_sub]
+    DevBuf<uint32_t> cnt;
+    DevBuf<unsigned long long> first, off;
+    DevBuf<int32_t> tok;
+  } ad;
   struct {  // word cache (k_wcache.hip): the batch's table of distinct words, the slot of every occurrence, the list K5 encodes, its ids
     DevBuf<unsigned long long> slot, pos, extra, blk_off, ustart, uend;
     DevBuf<uint32_t> occ, blk, uslot, ucounts;
@@ -196,7 +204,29 @@ struct EncoderDevice {
     std::atomic<bool> on{false};
     std::atomic<unsigned long long> stats[4] = {{0}, {0}, {0}, {0}};  // calls, calls whose write pass was skipped, ids in, ids out
   } bfb;
-  uint32_t id_bound(uint32_t V) const { return bytefb_bound(V, bfb.on.load()); }
+  // the added tokens (host_encoder.cpp set_added_tokens, k_added.h): a setting of the encoder like the two above, replaced with every lane locked.
+  // n == 0: off.  The host's copy (toks, index) serves the names and the host decode; the device tables are those of added_plan.h's added_tables.
+  // slot: the result of the last stand-alone split (yttm_added_split_device), the encoder's own and under lane 0's mutex like the counts.
+  struct {
+    std::atomic<uint32_t> n{0};
+    std::vector<std::string> toks;
+    std::unordered_map<std::string, uint32_t> index;
+    unsigned long long first[4] = {0, 0, 0, 0};
+    DevBuf<uint32_t> one, dir_off;
+    DevBuf<unsigned long long> list;
+    DevBuf<uint8_t> blob;
+    std::atomic<unsigned long long> stats[4] = {{0}, {0}, {0}, {0}};  // calls with the setting on, calls without a match, matches, sub-sentences encoded
+    struct {
+      DevBuf<uint32_t> cnt;
+      DevBuf<unsigned long long> first, off;
+      DevBuf<int32_t> tok;
+      unsigned long long n_sent = 0, n_sub = 0;
+      bool valid = false;
+    } slot;
+    AddedTable table() const { return AddedTable{{first[0], first[1], first[2], first[3]}, one, dir_off, list, blob}; }
+  } add;
+  // the ids the decode, the SUBWORD formatter, the ignore bitmap and the counts' default bins accept: [0, id_bound) (added_plan.h)
+  uint32_t id_bound(uint32_t V) const { return added_bound(V, bfb.on.load(), add.n.load()); }
   // a free lane, locked (falls back to waiting for the caller's turn-based choice)
   // (Lane 0 last: the device-resident pair encode_device / fetch_device_result keeps its result there, unlocked, between the two
   // calls -- a host-to-host encode from another thread in between takes another lane while one is free.)
@@ -282,6 +312,8 @@ Status on_device(int device, F &&body) {
 
 // what every spans entry answers while the byte fallback is on, before any work (several ids would share one unit)
 constexpr const char *SPANS_UNDER_BYTE_FALLBACK = "spans are not defined under byte fallback: switch it off (set_byte_fallback) for this call";
+constexpr const char *SPANS_UNDER_ADDED_TOKENS = "spans are not defined under added tokens: clear them (set_added_tokens) for this call";
+constexpr const char *SUBWORD_UNDER_ADDED_TOKENS = "SUBWORD output under added tokens needs byte fallback on as well (set_byte_fallback)";
 Status check_bos_eos(const BaseEncoder &enc, bool bos, bool eos);  // bpe.cpp:1702-1707: the reference's two messages, before any work
 
 // K5 on one lane (locked by the caller): input already in HBM, ids + offsets left in the lane's result buffers

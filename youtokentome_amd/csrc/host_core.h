@@ -237,6 +237,20 @@ class BaseEncoder {  // bpe.h:22-82
   void byte_fallback_stats(unsigned long long out[4]) const;
   Status byte_fallback_ids_device(const void *d_ids, const void *d_id_offsets, const void *d_bytes, const void *d_text_offsets, unsigned long long n_sent,
                                   unsigned long long n_ids, unsigned long long total_bytes, bool reverse, unsigned long long *n_out, double *kernel_ms) const;
+  // Added tokens (host_encoder.cpp, k_added.h; the rule is in include/yttm_mi355x.h): a setting of the encoder.  n byte strings as a blob plus
+  // offsets[n + 1]; token k is the id vocab_size() + 256 + k, matched in every batch's text, never split.  blob == nullptr clears the setting.
+  // added_tokens: a copy of the set in the caller's order.  added_tokens_stats: calls with the setting on, calls without a match, matches,
+  // sub-sentences encoded.  added_split_device: the stand-alone split of a text in HBM into the encoder's own slot, taken with take_added_split.
+  // id_bound / default_bins: the ids the decode, the names and the counts know under the settings as they stand.
+  Status set_added_tokens(const uint8_t *blob, const unsigned long long *tok_offsets, unsigned long long n) const;
+  unsigned long long n_added_tokens() const;
+  std::vector<std::string> added_tokens() const;
+  void added_tokens_stats(unsigned long long out[4]) const;
+  Status added_split_device(const void *d_bytes, const void *d_offsets, unsigned long long n_sent, unsigned long long total_bytes, unsigned long long *n_sub,
+                            unsigned long long *n_matches, double *kernel_ms) const;
+  Status take_added_split(void *sub_first, void *sub_off, void *tok, unsigned long long n_sent, unsigned long long n_sub, bool to_device) const;
+  unsigned long long id_bound() const;
+  unsigned long long default_bins() const { return id_bound(); }
   // the YTTM_* hooks as they stood when THIS encoder was made: every entry point binds them to its thread (yttm_config.h CfgBind), so that a
   // later encoder or training never changes the paths of this one
   std::shared_ptr<const Config> config() const;

@@ -20,7 +20,7 @@ static void table_once(const BaseEncoder &enc, EncoderDevice &D, bool &ready, De
   std::lock_guard<std::mutex> lk(D.dec_mu);
   if (ready) return;
   std::string blob;
-  std::vector<uint32_t> off(bytefb_table_offsets((uint32_t)enc.vocab_size()), 0), per_id(dst_per_id ? (size_t)enc.vocab_size() : 0, 0);
+  std::vector<uint32_t> off(added_table_offsets((uint32_t)enc.vocab_size(), D.add.n.load()), 0), per_id(dst_per_id ? (size_t)enc.vocab_size() : 0, 0);
   build(blob, off, per_id);
   DevBuf<uint8_t> d_blob;
   DevBuf<uint32_t> d_off, d_per_id;
@@ -57,6 +57,16 @@ static void decode_table(const BaseEncoder &enc, EncoderDevice &D) {
     if (blob.size() + BYTE_IDS >= (size_t)DEC_INVALID) throw GpuError{"decode: the vocabulary's text does not fit 2 GB"};
     for (uint32_t b = 0; b <= BYTE_IDS; b++) off[(size_t)V + b] = (uint32_t)blob.size() + b;  // a byte id's piece is the raw byte
     for (uint32_t b = 0; b < BYTE_IDS; b++) blob += (char)b;
+    // an added id's piece is the token verbatim.  With added tokens the bound lies behind the byte ids whether the byte fallback is on or not:
+    // while it is off they are marked as ids the host refuses (set_byte_fallback and set_added_tokens have this table made again)
+    const uint32_t n_added = D.add.n.load();
+    if (n_added && !D.bfb.on.load())
+      for (uint32_t b = 0; b < BYTE_IDS; b++) off[(size_t)V + b] |= DEC_INVALID;
+    for (uint32_t k = 0; k < n_added; k++) {
+      blob += D.add.toks[k];
+      off[(size_t)V + BYTE_IDS + k + 1] = (uint32_t)blob.size();
+    }
+    if (blob.size() >= (size_t)DEC_INVALID) throw GpuError{"decode: the vocabulary's text does not fit 2 GB"};
     D.dec_vocab = (uint32_t)V;
   });
 }
@@ -255,6 +265,10 @@ static void subword_table(const BaseEncoder &enc, EncoderDevice &D) {
       blob += bytefb_name(b);
     }
     off[(size_t)V + BYTE_IDS] = (uint32_t)blob.size();
+    for (uint32_t k = 0; k < D.add.n.load(); k++) {  // an added id prints as the token
+      blob += D.add.toks[k];
+      off[(size_t)V + BYTE_IDS + k + 1] = (uint32_t)blob.size();
+    }
   });
 }
 
@@ -330,7 +344,7 @@ Status BaseEncoder::id_counts_device(unsigned long long n_sent, unsigned long lo
   const Lane0 l(*dev_);
   EncodeLane &d = l.d;
   if (!d.res.made || n_sent != d.res.n_sent) return Status(1, "id_counts_device: no matching encode result");  // (before any work: the counts stay)
-  const Status s = count_on_lane(*dev_, d, device_, d.res.ids, d.res.n_ids, n_bins ? n_bins : bytefb_default_bins((uint32_t)vocab_size(), byte_fallback()), accumulate, ms.next());
+  const Status s = count_on_lane(*dev_, d, device_, d.res.ids, d.res.n_ids, n_bins ? n_bins : default_bins(), accumulate, ms.next());
   if (s.ok() && n_counted) *n_counted = d.res.n_ids;
   return s;
 }
@@ -340,7 +354,7 @@ Status BaseEncoder::id_counts_ids_device(const void *d_ids, unsigned long long n
   if (!dev_) return Status(2, "encoder has no device state");
   if (((uintptr_t)d_ids & 3u) != 0) return Status(2, "id_counts_ids_device: the ids must be 4-byte aligned");
   const Lane0 l(*dev_);
-  return count_on_lane(*dev_, l.d, device_, (const int32_t *)d_ids, n_ids, n_bins ? n_bins : bytefb_default_bins((uint32_t)vocab_size(), byte_fallback()), accumulate, ms.next());
+  return count_on_lane(*dev_, l.d, device_, (const int32_t *)d_ids, n_ids, n_bins ? n_bins : default_bins(), accumulate, ms.next());
 }
 
 Status BaseEncoder::take_id_counts(void *counts, unsigned long long n_bins, bool to_device) const {
@@ -348,7 +362,7 @@ Status BaseEncoder::take_id_counts(void *counts, unsigned long long n_bins, bool
   if (!dev_) return Status(1, who);
   const Lane0 l(*dev_);
   EncodeLane &d = l.d;
-  if (!dev_->idc.valid || (n_bins ? n_bins : bytefb_default_bins((uint32_t)vocab_size(), byte_fallback())) != dev_->idc.n_bins) return Status(1, who);
+  if (!dev_->idc.valid || (n_bins ? n_bins : default_bins()) != dev_->idc.n_bins) return Status(1, who);
   if (!counts) return Status(2, "id_counts: no output");
   const size_t bytes = ((size_t)dev_->idc.n_bins + 1) * 8;
   return on_device(device_, [&]() -> Status {
@@ -789,6 +803,7 @@ Status BaseEncoder::subword_device(const void *d_bytes, const void *d_offsets, u
   if (n_ids) *n_ids = 0;
   if (n_text_bytes) *n_text_bytes = 0;
   StageClock ms(kernel_ms);
+  if (n_added_tokens() && !byte_fallback()) return Status(1, SUBWORD_UNDER_ADDED_TOKENS);
   const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work, and before the device check: nothing that was pending is touched)
   if (!tokens.ok()) return tokens;
   if (!dev_) return Status(2, "encoder has no device state");
@@ -841,6 +856,7 @@ Status BaseEncoder::spans_device(const void *d_bytes, const void *d_offsets, uns
   if (n_ids) *n_ids = 0;
   StageClock ms(kernel_ms);
   if (byte_fallback()) return Status(1, SPANS_UNDER_BYTE_FALLBACK);
+  if (n_added_tokens()) return Status(1, SPANS_UNDER_ADDED_TOKENS);
   const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work, and before the device check: nothing that was pending is touched)
   if (!tokens.ok()) return tokens;
   if (!dev_) return Status(2, "encoder has no device state");
@@ -897,6 +913,7 @@ Status BaseEncoder::encode_as_ids_spans(const uint8_t *bytes, const unsigned lon
   *spans = nullptr;
   const CfgBind bind(config());
   if (byte_fallback()) return Status(1, SPANS_UNDER_BYTE_FALLBACK);
+  if (n_added_tokens()) return Status(1, SPANS_UNDER_ADDED_TOKENS);
   Status s = check_bos_eos(*this, bos, eos);
   if (!s.ok()) return s;
   if (n_sent && !dev_) return Status(2, "encoder has no device state");

@@ -400,6 +400,10 @@ Status BaseEncoder::set_byte_fallback(bool on) const {
   EncoderDevice &D = *dev_;
   std::lock_guard<std::mutex> lk0(D.lane[0].mu), lk1(D.lane[1].mu);  // (always in this order; a result already pending stays as it is)
   D.bfb.on.store(on);
+  if (D.add.n.load()) {  // (under added tokens the decode table marks [V, V + 256) invalid while the byte fallback is off: it is made again)
+    std::lock_guard<std::mutex> lkd(D.dec_mu);
+    D.dec_ready = D.sub_ready = false;
+  }
   return Status();
 }
 bool BaseEncoder::byte_fallback() const { return dev_ && dev_->bfb.on.load(); }
@@ -421,6 +425,173 @@ Status BaseEncoder::byte_fallback_ids_device(const void *d_ids, const void *d_id
   if (!dev_->bfb.on.load()) return Status(1, "byte_fallback_ids_device: byte fallback is not set");  // (before any work: what was pending stays)
   return bytefb_on_lane(*this, *dev_, l.d, device_, (const int32_t *)d_ids, (const unsigned long long *)d_id_offsets, d_bytes, d_text_offsets, n_sent, n_ids,
                         reverse, false, n_out, ms.next());
+}
+
+// ---- the added tokens (k_added.h; the rule is in include/yttm_mi355x.h) ---------------------------------------------------------------------
+// The split on a lane's stream (which ends synchronised): measure -> scan -> write into cnt / first / off / tok (the lane's, or the encoder's
+// slot).  no_write_without_match: where the text holds no match the write pass is skipped (the refined batch is the batch) and off / tok stay as
+// they were.  *n_sub: the sub-sentences, n_sent + 2 * matches.
+static Status split_on_lane(EncoderDevice &D, EncodeLane &d, const void *d_bytes, const void *d_offsets, unsigned long long n_sent, unsigned long long total_bytes,
+                            bool no_write_without_match, DevBuf<uint32_t> &cnt, DevBuf<unsigned long long> &first, DevBuf<unsigned long long> &off,
+                            DevBuf<int32_t> &tok, unsigned long long *n_sub, double *kernel_ms) {
+  const AddedTable tb = D.add.table();
+  bool skip = false;
+  return two_pass_on_lane(
+      d, n_sent, cnt, first, kernel_ms, n_sub,
+      [&](bool write) {
+        if (write && skip) return;
+        launch_added_split(write, (const uint8_t *)d_bytes, (const unsigned long long *)d_offsets, n_sent, total_bytes, tb, cnt, first, off, tok, d.st);
+      },
+      [] { return Status(); },
+      [&](unsigned long long need) {
+        skip = no_write_without_match && need == n_sent;  // (2 * matches + 1 sub-sentences per sentence: no match anywhere)
+        if (skip) return;
+        off.grow((size_t)need + 1);
+        tok.grow((size_t)need);
+      });
+}
+
+// The join of the refined batch's ids pending on the lane (forward, without bos / eos) into the lane's second pair of buffers, which then becomes
+// the lane's encode result of the caller's n_sent sentences.
+static Status join_on_lane(const BaseEncoder &enc, EncodeLane &d, unsigned long long n_sent, bool bos, bool eos, bool reverse, unsigned long long *n_out,
+                           double *kernel_ms) {
+  const SpecialTokens &sp = enc.bpe_state.special_tokens;
+  const AddedJoin in{d.res.ids, d.res.off, d.ad.tok, d.ad.first, n_sent, (int32_t)added_first((uint32_t)enc.vocab_size()), (int32_t)sp.bos_id, (int32_t)sp.eos_id,
+                     bos ? 1 : 0, eos ? 1 : 0, reverse ? 1 : 0};
+  unsigned long long total = 0;
+  const Status s = two_pass_on_lane(
+      d, n_sent, d.rs.len, d.rs.off, kernel_ms, &total,
+      [&](bool write) { launch_added_join(write, in, d.res.n_ids, d.rs.len, d.rs.off, d.rs.ids, d.st); }, [] { return Status(); },
+      [&](unsigned long long need) {
+        d.rs.ids.grow((size_t)need + 4);
+        if (((uintptr_t)d.rs.ids.p & 15u) != 0) throw GpuError{"added tokens: the output is not 16-byte aligned"};
+      });
+  if (!s.ok()) return s;
+  std::swap(d.res.ids, d.rs.ids);
+  std::swap(d.res.off, d.rs.off);
+  d.res.n_sent = n_sent;
+  d.res.n_ids = total;
+  *n_out = total;
+  return Status();
+}
+
+Status BaseEncoder::set_added_tokens(const uint8_t *blob, const unsigned long long *tok_offsets, unsigned long long n) const {
+  if (!dev_) return Status(2, "encoder has no device state");
+  EncoderDevice &D = *dev_;
+  const CfgBind bind(D.cfg);
+  if (blob) {  // (before any lock: an invalid set leaves the setting as it was)
+    if (!tok_offsets) return Status(1, "set_added_tokens: no offsets");
+    const std::string bad = added_validate(blob, tok_offsets, n, (uint32_t)vocab_size());
+    if (!bad.empty()) return Status(1, bad);
+  }
+  std::lock_guard<std::mutex> lk0(D.lane[0].mu), lk1(D.lane[1].mu);  // (always in this order; a result already pending stays as it is)
+  std::lock_guard<std::mutex> lkd(D.dec_mu);
+  if (!blob) {
+    D.add.n.store(0);
+    D.add.toks.clear();
+    D.add.index.clear();
+    D.dec_ready = D.sub_ready = false;  // (the piece tables are made again, without the tokens' entries)
+    return Status();
+  }
+  const AddedTables t = added_tables(blob, tok_offsets, (uint32_t)n);
+  const size_t n_blob = (size_t)(tok_offsets[n] - tok_offsets[0]);
+  const Status s = on_device(device_, [&]() -> Status {
+    // all are allocated and filled, then handed to the encoder together: a failure on the way leaves the tokens as they were
+    DevBuf<uint32_t> d_one, d_dir;
+    DevBuf<unsigned long long> d_list;
+    DevBuf<uint8_t> d_blob;
+    d_one.alloc(t.one.size());
+    d_dir.alloc(t.dir_off.size());
+    d_list.alloc(t.list.size());
+    d_blob.alloc(n_blob);
+    HIP_CHECK(hipMemcpy(d_one, t.one.data(), t.one.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_dir, t.dir_off.data(), t.dir_off.size() * 4, hipMemcpyHostToDevice));
+    if (!t.list.empty()) HIP_CHECK(hipMemcpy(d_list, t.list.data(), t.list.size() * 8, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_blob, blob + tok_offsets[0], n_blob, hipMemcpyHostToDevice));
+    D.add.one = std::move(d_one);
+    D.add.dir_off = std::move(d_dir);
+    D.add.list = std::move(d_list);
+    D.add.blob = std::move(d_blob);
+    return Status();
+  });
+  if (!s.ok()) return s;
+  for (int i = 0; i < 4; i++) D.add.first[i] = (unsigned long long)t.first[2 * i] | ((unsigned long long)t.first[2 * i + 1] << 32);
+  D.add.toks.clear();
+  D.add.index.clear();
+  for (unsigned long long k = 0; k < n; k++) {
+    D.add.toks.emplace_back((const char *)blob + tok_offsets[k], (size_t)(tok_offsets[k + 1] - tok_offsets[k]));
+    D.add.index.emplace(D.add.toks.back(), (uint32_t)k);
+  }
+  D.add.n.store((uint32_t)n);
+  D.dec_ready = D.sub_ready = false;  // (the piece tables are made again, with the tokens' entries)
+  return Status();
+}
+unsigned long long BaseEncoder::n_added_tokens() const { return dev_ ? dev_->add.n.load() : 0ull; }
+std::vector<std::string> BaseEncoder::added_tokens() const {
+  if (!dev_) return {};
+  std::lock_guard<std::mutex> lk(dev_->dec_mu);
+  return dev_->add.toks;
+}
+void BaseEncoder::added_tokens_stats(unsigned long long out[4]) const {
+  for (int i = 0; i < 4; i++) out[i] = dev_ ? dev_->add.stats[i].load() : 0ull;
+}
+unsigned long long BaseEncoder::id_bound() const { return dev_ ? dev_->id_bound((uint32_t)vocab_size()) : (unsigned long long)vocab_size(); }
+
+Status BaseEncoder::added_split_device(const void *d_bytes, const void *d_offsets, unsigned long long n_sent, unsigned long long total_bytes,
+                                       unsigned long long *n_sub, unsigned long long *n_matches, double *kernel_ms) const {
+  if (n_sub) *n_sub = 0;
+  if (n_matches) *n_matches = 0;
+  StageClock ms(kernel_ms);
+  if (!dev_) return Status(2, "encoder has no device state");
+  if (n_sent && !d_offsets) return Status(2, "added_split_device: no offsets");
+  if (total_bytes && !d_bytes) return Status(2, "added_split_device: no text");
+  const Lane0 l(*dev_);
+  EncoderDevice &D = *dev_;
+  if (!D.add.n.load()) return Status(1, "added_split_device: no added tokens are set");  // (before any work: the slot stays)
+  return on_device(device_, [&]() -> Status {
+    auto &sl = D.add.slot;
+    sl.valid = false;
+    unsigned long long total = 0;
+    if (n_sent) {
+      const Status s = split_on_lane(D, l.d, d_bytes, d_offsets, n_sent, total_bytes, false, sl.cnt, sl.first, sl.off, sl.tok, &total, ms.next());
+      if (!s.ok()) return s;
+    }
+    sl.n_sent = n_sent;
+    sl.n_sub = total;
+    sl.valid = true;
+    if (n_sub) *n_sub = total;
+    if (n_matches) *n_matches = (total - n_sent) / 2;
+    return Status();
+  });
+}
+
+Status BaseEncoder::take_added_split(void *sub_first, void *sub_off, void *tok, unsigned long long n_sent, unsigned long long n_sub, bool to_device) const {
+  const char *who = "added_split: no matching split result";
+  if (!dev_) return Status(1, who);
+  const Lane0 l(*dev_);
+  auto &sl = dev_->add.slot;
+  if (!sl.valid || n_sent != sl.n_sent || n_sub != sl.n_sub) return Status(1, who);
+  return on_device(device_, [&]() -> Status {
+    const auto take = [&](void *dst, const void *src, size_t bytes) {  // (a null destination is skipped)
+      if (!dst || !bytes) return;
+      if (to_device) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, l.d.st));
+      else copy_down(device_, dst, src, bytes, l.d.st);
+    };
+    if (!n_sent) {  // (nothing was launched and no buffer exists: the one entry of sub_first and of sub_offsets is 0)
+      const unsigned long long zero = 0;
+      for (void *dst : {sub_first, sub_off}) {
+        if (dst && to_device) HIP_CHECK(hipMemcpyAsync(dst, &zero, 8, hipMemcpyHostToDevice, l.d.st));
+        else if (dst) *(unsigned long long *)dst = 0;
+      }
+      HIP_CHECK(hipStreamSynchronize(l.d.st));
+      return Status();
+    }
+    take(sub_first, sl.first, (size_t)(n_sent + 1) * 8);
+    take(sub_off, sl.off, (size_t)(n_sub + 1) * 8);
+    take(tok, sl.tok, (size_t)n_sub * 4);
+    HIP_CHECK(hipStreamSynchronize(l.d.st));
+    return Status();
+  });
 }
 
 Status BaseEncoder::set_vocabulary(const uint8_t *allowed, unsigned long long n, unsigned long long *info) const {
@@ -505,11 +676,10 @@ Status BaseEncoder::restrict_ids_device(const void *d_ids, const void *d_offsets
   return restrict_on_lane(*dev_, l.d, device_, (const int32_t *)d_ids, (const unsigned long long *)d_offsets, n_sent, n_ids, reverse, false, n_out, ms.next());
 }
 
-Status encode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_bytes, const void *d_offsets,
-                      unsigned long long n_sent, unsigned long long total_bytes, unsigned long long max_sentence_bytes, bool bos, bool eos, bool reverse,
-                      double dropout_prob, unsigned long long *n_ids_out, double *kernel_ms) {
-  const Status tokens = check_bos_eos(enc, bos, eos);
-  if (!tokens.ok()) return tokens;
+// the encode of a batch as its offsets cut it: K5 (or the word cache), the gather, and the tails of the restriction and the byte fallback
+static Status encode_plain_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_bytes, const void *d_offsets,
+                                   unsigned long long n_sent, unsigned long long total_bytes, unsigned long long max_sentence_bytes, bool bos, bool eos,
+                                   bool reverse, double dropout_prob, unsigned long long *n_ids_out, double *kernel_ms) {
   return on_device(device, [&]() -> Status {
     d.res.n_sent = n_sent;
     d.res.n_ids = 0;
@@ -548,6 +718,54 @@ Status encode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, i
     if (n_ids_out) *n_ids_out = total;
     return tails();
   });
+}
+
+// With added tokens set: split; without a match in the batch the encode as before on the caller's offsets; else the encode of the refined batch
+// (its sentences are every sentence's segments and matches in text order) forward and without bos / eos -- its tails get the refined offsets, so
+// the restriction and the byte fallback compose by construction --, then the join, which leaves the caller's n_sent sentences.
+Status encode_on_lane(const BaseEncoder &enc, EncoderDevice &D, EncodeLane &d, int device, const void *d_bytes, const void *d_offsets,
+                      unsigned long long n_sent, unsigned long long total_bytes, unsigned long long max_sentence_bytes, bool bos, bool eos, bool reverse,
+                      double dropout_prob, unsigned long long *n_ids_out, double *kernel_ms) {
+  const Status tokens = check_bos_eos(enc, bos, eos);
+  if (!tokens.ok()) return tokens;
+  if (!D.add.n.load() || n_sent == 0)
+    return encode_plain_on_lane(enc, D, d, device, d_bytes, d_offsets, n_sent, total_bytes, max_sentence_bytes, bos, eos, reverse, dropout_prob, n_ids_out, kernel_ms);
+  double ms_split = 0, ms_enc = 0, ms_join = 0;
+  unsigned long long n_sub = 0;
+  Status s = on_device(device, [&]() -> Status {
+    return split_on_lane(D, d, d_bytes, d_offsets, n_sent, total_bytes, true, d.ad.cnt, d.ad.first, d.ad.off, d.ad.tok, &n_sub, kernel_ms ? &ms_split : nullptr);
+  });
+  if (!s.ok()) return s;
+  D.add.stats[0] += 1;
+  if (n_sub == n_sent) {
+    D.add.stats[1] += 1;
+    D.add.stats[3] += n_sent;
+    s = encode_plain_on_lane(enc, D, d, device, d_bytes, d_offsets, n_sent, total_bytes, max_sentence_bytes, bos, eos, reverse, dropout_prob, n_ids_out, kernel_ms);
+    if (kernel_ms) *kernel_ms += ms_split;
+    return s;
+  }
+  D.add.stats[2] += (n_sub - n_sent) / 2;
+  D.add.stats[3] += n_sub;
+  unsigned long long n_refined = 0;
+  s = encode_plain_on_lane(enc, D, d, device, d_bytes, d.ad.off.p, n_sub, total_bytes, max_sentence_bytes, false, false, false, dropout_prob, &n_refined,
+                           kernel_ms ? &ms_enc : nullptr);
+  if (s.ok()) {
+    s = on_device(device, [&]() -> Status {
+      unsigned long long n_out = 0;
+      const Status j = join_on_lane(enc, d, n_sent, bos, eos, reverse, &n_out, kernel_ms ? &ms_join : nullptr);
+      if (j.ok() && n_ids_out) *n_ids_out = n_out;
+      return j;
+    });
+  }
+  if (!s.ok()) {  // (a refined batch must not stay pending as if it were the caller's)
+    d.res.n_sent = n_sent;
+    d.res.n_ids = 0;
+    d.res.made = false;
+    if (n_ids_out) *n_ids_out = 0;
+    return s;
+  }
+  if (kernel_ms) *kernel_ms = ms_split + ms_enc + ms_join;
+  return Status();
 }
 
 static size_t staged_from() {
@@ -901,6 +1119,7 @@ Status BaseEncoder::encode_as_subwords(const uint8_t *bytes, const unsigned long
   // ids come from the GPU (forward order, no bos/eos); pieces are a host lookup (bpe.cpp:1597-1613).  The k-th unk id
   // of a sentence is the k-th run of unknown chars, whose text is recovered from the sentence itself.
   const CfgBind bind(config());
+  if (n_added_tokens() && !byte_fallback()) return Status(1, SUBWORD_UNDER_ADDED_TOKENS);
   Status s = check_bos_eos(*this, bos, eos);
   if (!s.ok()) return s;
   std::vector<int32_t> ids;
@@ -949,6 +1168,10 @@ Status BaseEncoder::id_to_subword(int id, std::string *subword, bool replace_spa
     *subword = bytefb_name((uint32_t)(id - vocab_size()));
     return Status();
   }
+  if (added_is_added_id(id, (uint32_t)vocab_size(), (uint32_t)n_added_tokens())) {  // the token verbatim
+    *subword = dev_->add.toks[(size_t)id - added_first((uint32_t)vocab_size())];
+    return Status();
+  }
   if (id < 0 || vocab_size() <= id)
     return Status(1, "id must be in the range [0, vocab_size - 1]. Current value: vocab_size = " + std::to_string(vocab_size()) +
                          "; id=" + std::to_string(id) + ";");
@@ -976,6 +1199,10 @@ int BaseEncoder::subword_to_id(const std::string &token) const {  // bpe.cpp:180
   if (BOS_TOKEN == token) return sp.bos_id;
   if (EOS_TOKEN == token) return sp.eos_id;
   if (byte_fallback() && bytefb_parse_name(token) >= 0) return vocab_size() + bytefb_parse_name(token);
+  if (n_added_tokens()) {
+    auto at = dev_->add.index.find(token);
+    if (at != dev_->add.index.end()) return (int)(added_first((uint32_t)vocab_size()) + at->second);
+  }
   auto it = reversed_recipe.find(token);
   if (it != reversed_recipe.end()) return (int)it->second;
   return sp.unk_id;
@@ -989,6 +1216,11 @@ Status BaseEncoder::decode(const std::vector<int> &ids, std::string *sentence, c
     if (!ignore_ids || ignore_ids->count(id) == 0) {
       if (bytefb_is_byte_id(id, (uint32_t)vocab_size(), byte_fallback())) {  // the raw byte, and no strip rule
         *sentence += (char)(id - vocab_size());
+        first_iter = false;
+        continue;
+      }
+      if (added_is_added_id(id, (uint32_t)vocab_size(), (uint32_t)n_added_tokens())) {  // the token verbatim, and no strip rule
+        *sentence += dev_->add.toks[(size_t)id - added_first((uint32_t)vocab_size())];
         first_iter = false;
         continue;
       }

@@ -127,6 +127,7 @@ Status BaseEncoder::subword_text_device(const void *d_text, unsigned long long n
   if (n_ids) *n_ids = 0;
   if (n_text_bytes) *n_text_bytes = 0;
   StageClock ms(kernel_ms);
+  if (n_added_tokens() && !byte_fallback()) return Status(1, SUBWORD_UNDER_ADDED_TOKENS);
   const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work, and before the device check: nothing that was pending is touched)
   if (!tokens.ok()) return tokens;
   if (!dev_) return Status(2, "encoder has no device state");
@@ -144,6 +145,7 @@ Status BaseEncoder::spans_text_device(const void *d_text, unsigned long long n_b
   if (n_ids) *n_ids = 0;
   StageClock ms(kernel_ms);
   if (byte_fallback()) return Status(1, SPANS_UNDER_BYTE_FALLBACK);
+  if (n_added_tokens()) return Status(1, SPANS_UNDER_ADDED_TOKENS);
   const Status tokens = check_bos_eos(*this, bos, eos);  // (before any work, and before the device check: nothing that was pending is touched)
   if (!tokens.ok()) return tokens;
   if (!dev_) return Status(2, "encoder has no device state");
@@ -535,7 +537,7 @@ Status BaseEncoder::encode_file_counts(const std::string &path, bool bos, bool e
   const CfgBind bind(C);
   const int device = device_;
   EncoderDevice *dev = dev_;
-  const unsigned long long n_bins = bytefb_default_bins((uint32_t)vocab_size(), byte_fallback());  // (the caller's counts hold that many and one more)
+  const unsigned long long n_bins = default_bins();  // (the caller's counts hold that many and one more)
   std::lock_guard<std::mutex> lk0(dev->lane[0].mu), lk1(dev->lane[1].mu);  // (lane 0 first, always: nobody else waits for two lanes)
 
   const Status zeroed = count_on_lane(*dev, dev->lane[0], device, nullptr, 0, n_bins, false, nullptr);  // (an empty file counts nothing into zeroes)
@@ -665,6 +667,7 @@ Status BaseEncoder::encode_file_subword(const std::string &path, const std::stri
   if (n_lines_out) *n_lines_out = 0;
   if (n_ids_out) *n_ids_out = 0;
   if (n_text_out) *n_text_out = 0;
+  if (n_added_tokens() && !byte_fallback()) return Status(1, SUBWORD_UNDER_ADDED_TOKENS);
   const Status tokens = check_bos_eos(*this, bos, eos);
   if (!tokens.ok()) return tokens;
   const int device = device_;

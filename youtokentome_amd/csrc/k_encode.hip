@@ -1168,3 +1168,4 @@ void launch_encode_gather(const int32_t *scratch_ids, const unsigned long long *
 #include "k_blocks.h"    // training blocks of an id array: kernels and launchers of this translation unit
 #include "k_batches.h"   // batches by length under a token budget: kernels and launchers of this translation unit
 #include "k_bytefb.h"    // the byte fallback of an id array: kernel and launcher of this translation unit
+#include "k_added.h"     // the added tokens: the split of a text and the join of the refined batch's ids, kernels and launchers of this translation unit

@@ -482,6 +482,31 @@ void launch_restrict(bool write, const int32_t *ids, const unsigned long long *o
 void launch_bytefb(bool write, const EncModel &m, const SubInput &in, int32_t first, unsigned long long n_ids, uint32_t *out_len, uint32_t *saw,
                    const unsigned long long *out_off, int32_t *out, hipStream_t st);
 
+// ---- the added tokens (k_added.h, compiled with k_encode.hip): the split and the join, each measure -> launch_exclusive_scan -> write ----
+struct AddedTable {  // the matcher's tables (added_plan.h added_tables), only read
+  unsigned long long first[4];  // bit b: a token starts with byte b
+  const uint32_t *one;          // [256] the token that is this one byte, or ADDED_NO_TOKEN
+  const uint32_t *dir_off;      // [ADDED_DIR + 1]
+  const unsigned long long *list;  // added_entry (added_plan.h) of the tokens of two and more bytes, bucket after bucket, longest first
+  const uint8_t *blob;
+};
+// sentence s = text[off[s] .. off[s + 1]) -> cnt[n_sent] = 2 * matches + 1, then (sub_first the exclusive scan of cnt, [n_sent + 1]) the refined
+// offsets sub_off[n_sub + 1] and tok[n_sub]: the token's index for a match, -1 for a segment.  text: any address.  n_bytes sizes the groups.
+void launch_added_split(bool write, const uint8_t *text, const unsigned long long *off, unsigned long long n_sent, unsigned long long n_bytes,
+                        const AddedTable &tb, uint32_t *cnt, const unsigned long long *sub_first, unsigned long long *sub_off, int32_t *tok, hipStream_t st);
+struct AddedJoin {  // the refined batch's ids (forward, without bos / eos) and how its sub-sentences make the caller's sentences
+  const int32_t *rids;
+  const unsigned long long *roff;       // [n_sub + 1]
+  const int32_t *tok;                   // [n_sub]
+  const unsigned long long *sub_first;  // [n_sent + 1]
+  unsigned long long n_sent;
+  int32_t first, bos_id, eos_id;  // first: the id of token 0
+  int bos, eos, reverse;
+};
+// out_len[n_sent], then the ids at out[out_off[s] ..), out_off the exclusive scan of out_len.  out: 16-byte aligned.  n_ids sizes the groups.
+void launch_added_join(bool write, const AddedJoin &in, unsigned long long n_ids, uint32_t *out_len, const unsigned long long *out_off, int32_t *out,
+                       hipStream_t st);
+
 // ---- training blocks (k_blocks.h, compiled with k_encode.hip): flags -> scan -> (whole: orbit) -> measure -> scan -> write (-> keep) ----
 // The sequence a call packs: the open row's m sentences (f ids, open_off[m + 1]) followed by the call's S sentences (off[S + 1], off[0] = 0), as one
 // stream of `total` = f + K ids in which sentence i starts at voff(i).  Only read.

@@ -354,6 +354,19 @@ def byte_fallback_tensor(bpe, ids, text, lengths=None, offsets=None, reverse=Fal
     return _take_encoded(torch, core, dev, n, n_out, padded, width, pad_id)
 
 
+def split_added_tensor(bpe, text, offsets=None):
+    torch = _torch()
+    core = bpe.bpe_cython
+    dev = _device_of(bpe, None)
+    d_bytes, d_off, n, total, _ = _sentences_on(torch, text if offsets is None else (text, offsets), dev)
+    n_sub, _, _ = _synced(torch, dev, core.added_split_device_raw, d_bytes.data_ptr(), d_off.data_ptr(), n, total)
+    first = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    sub_off = torch.zeros(n_sub + 1, dtype=torch.int64, device=dev)
+    tok = torch.empty(n_sub, dtype=torch.int32, device=dev)
+    _synced(torch, dev, core.copy_added_split, first.data_ptr(), sub_off.data_ptr(), tok.data_ptr(), n, n_sub)
+    return first, sub_off, tok
+
+
 def id_counts_tensor(bpe, ids=None, n_bins=None, accumulate=False):
     torch = _torch()
     core = bpe.bpe_cython
